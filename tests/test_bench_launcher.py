@@ -69,3 +69,85 @@ def test_compact_line_of_a_full_measurement():
     assert [e["workload"] for e in d["extra_workloads"]] == [e["workload"] for e in full["extra_workloads"]]
     assert len(d["config"]["workload"]) <= 120 and abs(d["value"] - full["value"]) < 1e-3
     json.dumps(bench._clean(full), allow_nan=False)                  # the detail file is strict JSON as well
+
+
+def test_dump_outputs_is_refused_without_a_timed_path():
+    """--dump-outputs writes what the timed GPU path returned: the --dry stub has no such result, and the option says so."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry", "--dump-outputs", "x"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+
+
+def test_output_dump_arrays(tmp_path):
+    """bench.OutputDump on a made-up gsa_result: every contig's sizes, all rows of a small array, a seeded sample (with row numbers)
+    of a large one, float64 throughout, the same files from the same input, and far below the 64 MB a dump may take."""
+    import ctypes as C
+
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from gsalign_amd import capi
+    B = np.zeros(3, capi.BLOCK_DT); B["score"] = [5, 6, 7]; B["frag_off"] = [0, 10, 2 ** 40]; B["chr"] = [1, 2, 3]
+    R = np.zeros(500_000, capi.REC_DT); R["w0"] = np.arange(R.size); R["w3"] = 2 ** 32 - 1
+    a1 = (np.arange(1_000_000) % 251).astype(np.uint8); a2 = a1[::-1].copy()
+    r = capi.Result(); r.n_blocks = 3; r.n_frags = R.size; r.n_aln = a1.size
+    r.blocks = C.cast(B.ctypes.data, C.POINTER(capi.Block)); r.recs = C.cast(R.ctypes.data, C.POINTER(capi.Rec))
+    r.aln1 = C.cast(a1.ctypes.data, C.POINTER(C.c_char)); r.aln2 = C.cast(a2.ctypes.data, C.POINTER(C.c_char))
+    out = []
+    for rep in range(2):
+        d = bench.OutputDump(str(tmp_path / f"d{rep}"), 2)
+        d.take(1, 123, r); d.take(0, 77, r)                      # (contexts finish in any order)
+        d.write()
+        out.append({fn[:-4]: np.load(tmp_path / f"d{rep}" / fn) for fn in sorted(os.listdir(tmp_path / f"d{rep}"))})
+    x, y = out
+    assert sorted(x) == ["blocks", "records", "sizes", "strings"]
+    assert all(v.dtype == np.float64 and np.array_equal(v, y[k]) for k, v in x.items()) and sum(v.nbytes for v in x.values()) < 64e6
+    assert x["sizes"].tolist() == [[0, 77, 3, 500000, 1000000], [1, 123, 3, 500000, 1000000]]
+    assert x["blocks"].shape == (6, 10) and x["blocks"][2].tolist() == [0, 2, 7, 0, 0, 0, 2 ** 40, 0, 0, 3]
+    per = bench.DUMP_ROWS // 2
+    assert x["records"].shape == (2 * per, 6) and x["strings"].shape == (2 * per, 4)
+    rows = x["records"][:, 1].astype(np.int64)
+    assert np.array_equal(x["records"][:, 2], R["w0"][rows]) and (x["records"][:, 5] == 2 ** 32 - 1).all() and (np.diff(rows[:per]) >= 0).all()
+    off = x["strings"][:, 1].astype(np.int64)
+    assert np.array_equal(x["strings"][:, 2], a1[off]) and np.array_equal(x["strings"][:, 3], a2[off])
+    d = bench.OutputDump(str(tmp_path / "short"), 2); d.take(0, 77, r)
+    try:
+        d.write(); raise AssertionError("a dump that misses a contig of the step must not be written")
+    except RuntimeError:
+        pass
+
+
+def test_set_up_on_threads_gives_the_serial_genomes():
+    """The benchmark generates its contigs on a pool of threads: same seeds, same bytes as the plain loop."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from gsalign_amd import synth
+    wl = dict(bench.WORKLOADS["yeast"], lengths=[40_000, 30_000, 20_000], repeats=True, n_query=2)
+    refs = bench.synth_reference(wl)
+    for i, (name, r) in enumerate(refs):
+        want = synth.fast_genome(wl["lengths"][i], 11000 + i); synth.inject_repeats(want, 11000 + i)
+        assert name == f"chr{i + 1}" and np.array_equal(r, want)
+
+    class Args:
+        fasta_query = ""
+    for k, gq in enumerate(bench.make_queries(wl, refs, Args)):
+        for i, (_, r) in enumerate(refs):
+            assert np.array_equal(gq[i], synth.fast_mutate(r, wl["div"], 7000 + 10 * k + i))
+
+
+def test_cached_index_is_used_only_when_current(tmp_path, monkeypatch):
+    """prepare_inputs() leaves `<workload>_<bases>.done` holding the key of the checkout that built the index; a missing marker,
+    another key or an empty GSA_BENCH_CACHE mean: no cached index, the run builds its own."""
+    sys.path.insert(0, ROOT)
+    import bench
+    wl = bench.WORKLOADS["ecoli"]
+    monkeypatch.setenv("GSA_BENCH_CACHE", str(tmp_path))
+    assert bench.cache_dir() == str(tmp_path) and bench.cached_prefix("ecoli", wl) is None
+    px = tmp_path / "ecoli_5000000"
+    (tmp_path / "ecoli_5000000.done").write_text("0123456789abcdef")
+    assert bench.cached_prefix("ecoli", wl) is None
+    (tmp_path / "ecoli_5000000.done").write_text(bench.cache_key("ecoli", wl))
+    assert bench.cached_prefix("ecoli", wl) == str(px)
+    assert bench.cache_key("ecoli", wl) != bench.cache_key("ecoli", dict(wl, lengths=[5_000_001]))
+    monkeypatch.setenv("GSA_BENCH_CACHE", "")
+    assert bench.cache_dir() is None and bench.cached_prefix("ecoli", wl) is None

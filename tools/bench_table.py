@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU: the numbers table of DESIGN.md section 6 / README.md from a bench.py detail file (gpurun_out/bench_detail.json).
+"""CPU: the numbers table of DESIGN.md section 6 / README.md from the detail file of a `bench.py --full` run.
 usage: tools/bench_table.py <detail.json>"""
 import json
 import sys

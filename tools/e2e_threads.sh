@@ -5,7 +5,8 @@
 ulimit -c 0
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out
 export GSA_BENCH_KEEP=1 GSA_BENCH_TMP=/tmp/gb; mkdir -p $GSA_BENCH_TMP
-timeout 900 python bench.py --workload human_full --steps 2 --warmup 1 --extra "" --no-cpu-baseline --no-side-legs 2>gpurun_out/e2e_threads_bench.err | tail -1 | cut -c1-200
+export GSA_BENCH_CACHE=      # (no cached index: this run builds it into GSA_BENCH_TMP, where the CLI runs below look for it)
+timeout 900 python bench.py --full --workload human_full --steps 2 --warmup 1 --extra "" --no-cpu-baseline --no-side-legs 2>$GSA_BENCH_TMP/e2e_threads_bench.err | tail -1 | cut -c1-200
 IDX=$(ls -d /tmp/gb/human_full_* | head -1); IDX=${IDX%%.*}; Q=/tmp/gb/e2e_human_full_q.fa
 ls -la /tmp/gb | head -20
 for T in ${THREADS:-32 64 96 32 64 96 128}; do

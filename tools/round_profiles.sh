@@ -4,7 +4,8 @@
 ulimit -c 0
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 export GSA_BENCH_TMP=/tmp/gsa_round GSA_BENCH_KEEP=1; mkdir -p $GSA_BENCH_TMP gpurun_out
-timeout 900 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err; cp gpurun_out/bench_detail.json gpurun_out/bench_default_detail.json
+OUT=$(python -c 'import bench; print(bench.os.path.dirname(bench.DETAIL_FILE))')      # (the folder bench.py writes its detail file to)
+timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cp $OUT/bench_detail.json $OUT/bench_default_detail.json
 tail -c 400 gpurun_out/bench_default.json; echo
 for w in ${KW:-human_full human human_like ecoli yeast adversarial}; do
   timeout 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$w -o p -- python bench.py --workload $w --extra "" --no-cpu-baseline --no-side-legs --no-e2e > gpurun_out/prof_$w.log 2>&1

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Pretty-print a bench.py JSON line (stage split, counters, roofline terms, kernels)."""
+"""Pretty-print a `bench.py --full` JSON line (stage split, counters, roofline terms, kernels)."""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 def show(e, name):
