@@ -21,6 +21,7 @@ EXPORTS = [
     "gsa_set_query", "gsa_rewind", "gsa_run_to", "gsa_seed_count", "gsa_get_seeds", "gsa_group_count", "gsa_get_groups", "gsa_get_blocks",
     "gsa_bwt_search_batch", "gsa_ksw2_batch", "gsa_gap_similarity_batch", "gsa_get_counters", "gsa_get_timings", "gsa_set_profiling", "gsa_bind_host_thread",
     "gsa_prefetch_contig", "gsa_prefetch_bundle", "gsa_cancel_prefetch", "gsa_get_wall_sums", "gsa_get_alloc_stats", "gsa_debug_buffers", "gsa_set_option", "gsa_host_register", "gsa_host_unregister",
+    "gsa_call_variants", "gsa_align_many_variants", "gsa_get_variant_timing",
 ]
 
 
@@ -57,6 +58,46 @@ class Rec(C.Structure):
 class Result(C.Structure):
     _fields_ = [("n_blocks", C.c_int32), ("n_frags", C.c_int64), ("n_aln", C.c_int64), ("blocks", C.POINTER(Block)),
                 ("recs", C.POINTER(Rec)), ("aln1", C.POINTER(C.c_char)), ("aln2", C.POINTER(C.c_char))]
+
+
+class Variant(C.Structure):
+    """gsa_variant, 32 bytes (include/gsa_hip.h): kind 0 substitution, 1 / 2 insertion / deletion record, 3 / 4 insertion / deletion inside an aligned gap."""
+    _fields_ = [("rpos", C.c_int64), ("qpos", C.c_int32), ("len", C.c_int32), ("chr", C.c_int32), ("pos", C.c_int32), ("kind", C.c_int32), ("block", C.c_int32)]
+
+
+class Variants(C.Structure):
+    _fields_ = [("n", C.c_int64), ("v", C.POINTER(Variant)), ("n_snv", C.c_int64), ("n_ins", C.c_int64), ("n_del", C.c_int64)]
+
+
+VARIANT_DT = np.dtype([("rpos", "<i8"), ("qpos", "<i4"), ("len", "<i4"), ("chr", "<i4"), ("pos", "<i4"), ("kind", "<i4"), ("block", "<i4")])
+VCF_TYPE = ("SUBSTITUTE", "INSERT", "DELETE", "INSERT", "DELETE")      # by gsa_variant::kind
+
+
+def variants_array(var: "Variants"):
+    """gsa_variants -> (VARIANT_DT array (a copy), (n_snv, n_ins, n_del))."""
+    n = int(var.n)
+    V = np.ctypeslib.as_array(C.cast(var.v, C.POINTER(C.c_uint8)), shape=(n * VARIANT_DT.itemsize,)).view(VARIANT_DT).copy() if n else np.zeros(0, VARIANT_DT)
+    return V, (int(var.n_snv), int(var.n_ins), int(var.n_del))
+
+
+def variant_alleles(V: np.ndarray, ref, query) -> list:
+    """[(REF, ALT)] as bytes for the records V: the numpy form of gsa_variant_alleles (include/gsa_hip.h).  ref = RefSequence (2G bytes), query = the contig."""
+    ref = ref.tobytes() if isinstance(ref, np.ndarray) else bytes(ref)
+    query = query.tobytes() if isinstance(query, np.ndarray) else bytes(query)
+    out = []
+    for v in V:
+        r, q, n, k = int(v["rpos"]), int(v["qpos"]), int(v["len"]) + 1, int(v["kind"])
+        if k == 1:
+            out.append((ref[r:r + 1], query[q:q + n]))
+        elif k == 2:
+            out.append((ref[r:r + n], query[q:q + 1]))
+        elif k == 3:
+            out.append((query[q:q + 1], query[q:q + n]))
+        elif k == 4:
+            out.append((ref[r:r + n], ref[r:r + 1]))
+        else:
+            out.append((ref[r:r + 1], query[q:q + 1]))
+    return out
 
 
 FRAG_DT = np.dtype([("bseed", "<i4"), ("qpos", "<i4"), ("qlen", "<i4"), ("rlen", "<i4"), ("rpos", "<i8"), ("aln_off", "<i8"), ("aln_len", "<i4"), ("_pad", "<i4")])
@@ -144,6 +185,7 @@ def bind_host_thread(device: int = 0) -> None:
 
 
 RESULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(Result))
+RESULT_VAR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(Result), C.POINTER(Variants))
 
 
 class DeviceContig:
@@ -163,25 +205,33 @@ class DeviceContig:
             self.lib.gsa_device_free(self.device, C.c_void_p(self.ptr)); self.ptr = None
 
 
-def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True) -> None:
+def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False) -> None:
     """gsa_align_many: `contigs` (uint8 arrays, or DeviceContig objects -- all of one kind) on the given contexts, one host
     thread per context inside the library.  on_result(contig_index, Result) runs on the worker threads (the Result is valid
     during the call only).  in_order: hand the contigs out as listed (GSA_MANY_IN_ORDER) instead of longest first.
     bundle=False: GSA_MANY_NO_BUNDLE (every contig in a pass of its own; by default short contigs share passes).
     prefetch=False: GSA_MANY_NO_PREFETCH (a contig is uploaded when its turn comes; by default a context uploads its next contig
-    while it aligns the current one)."""
+    while it aligns the current one).
+    variants=True: gsa_align_many_variants -- the worker runs the variant pass first and on_result(contig_index, Result, Variants) gets its records too
+    (variants_array copies them out)."""
     lib = aligners[0].lib
     n = len(contigs)
     ctxs = (C.c_void_p * len(aligners))(*[a.ctx for a in aligners])
     on_dev = n > 0 and isinstance(contigs[0], DeviceContig)
     qs = (C.c_char_p * n)(*[C.cast(c.ptr if on_dev else c.ctypes.data, C.c_char_p) for c in contigs])
     ql = (C.c_int32 * n)(*[int(c.size) for c in contigs])
-    cb = RESULT_FN((lambda user, ci, res: int(on_result(ci, res.contents) or 0)) if on_result else 0)
-    lib.gsa_align_many.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_FN, C.c_void_p]
-    rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16), cb, None)
+    flags = (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16)
+    if variants:
+        cbv = RESULT_VAR_FN(lambda user, ci, res, var: int((on_result(ci, res.contents, var.contents) if on_result else 0) or 0))
+        lib.gsa_align_many_variants.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_VAR_FN, C.c_void_p]
+        rc = lib.gsa_align_many_variants(ctxs, len(aligners), qs, ql, n, flags, cbv, None)
+    else:
+        cb = RESULT_FN((lambda user, ci, res: int(on_result(ci, res.contents) or 0)) if on_result else 0)
+        lib.gsa_align_many.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_FN, C.c_void_p]
+        rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, flags, cb, None)
     if rc != 0:
         msgs = [lib.gsa_last_error(a.ctx).decode() for a in aligners]
-        raise GsaError(f"gsa_align_many -> {rc}: {'; '.join(m for m in msgs if m)}")
+        raise GsaError(f"gsa_align_many{'_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
 
 
 def _p(a, t):
@@ -328,8 +378,8 @@ class Aligner:
         p = self._params(**params)
         self._ck(self.lib.gsa_set_params(self.ctx, C.byref(p)))
 
-    def set_profiling(self, on: bool, count_blocks: bool = False, seed_only: bool = False):
-        self._ck(self.lib.gsa_set_profiling(self.ctx, (1 if on else 0) | (2 if count_blocks else 0) | (4 if seed_only else 0)))
+    def set_profiling(self, on: bool, count_blocks: bool = False, seed_only: bool = False, variants: bool = False):
+        self._ck(self.lib.gsa_set_profiling(self.ctx, (1 if on else 0) | (2 if count_blocks else 0) | (4 if seed_only else 0) | (8 if variants else 0)))
 
     def set_query(self, seq: np.ndarray):
         seq = np.ascontiguousarray(seq, dtype=np.uint8)
@@ -408,6 +458,20 @@ class Aligner:
         a1 = np.ctypeslib.as_array(C.cast(res.aln1, C.POINTER(C.c_uint8)), shape=(na,)).copy() if na else np.zeros(0, np.uint8)
         a2 = np.ctypeslib.as_array(C.cast(res.aln2, C.POINTER(C.c_uint8)), shape=(na,)).copy() if na else np.zeros(0, np.uint8)
         return dict(blocks=blocks, frags=frags, aln1=a1, aln2=a2)
+
+    def call_variants(self, k: int = 0):
+        """gsa_call_variants on the stage-8 result this context holds (contig k of a bundle): (VARIANT_DT array, (n_snv, n_ins, n_del))."""
+        var = Variants()
+        self.lib.gsa_call_variants.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Variants)]
+        self._ck(self.lib.gsa_call_variants(self.ctx, C.c_int32(k), C.byref(var)))
+        return variants_array(var)
+
+    def variant_timing(self):
+        """(device ms summed over the variant passes since set_profiling(..., variants=True), number of passes)."""
+        ms = C.c_double(0); n = C.c_int64(0)
+        self.lib.gsa_get_variant_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        self._ck(self.lib.gsa_get_variant_timing(self.ctx, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def raw_result(self) -> Result:
         """The gsa_result view (pointers into library-owned memory, no copies)."""

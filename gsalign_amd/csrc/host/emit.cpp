@@ -90,6 +90,7 @@ template <class T> void RawArr<T>::assign(const T *src, size_t count)
 }
 template struct RawArr<gsa_rec>;
 template struct RawArr<char>;
+template struct RawArr<gsa_variant>;
 void ContigResult::assign(const gsa_result &r)
 {
 	blocks.assign(r.blocks, r.blocks + r.n_blocks);
@@ -439,6 +440,63 @@ static void variants_of(const HostIndex *idx, int query_idx, const QueryContig &
 				} else { rp++; qp++; }
 			}
 		}
+	}
+}
+
+// The same walk writing gsa_variant records (gsa_hip.h) in the serial order: what gsa_call_variants computes on the device, on the host -- the comparator
+// of the device pass, and the variant caller of a host that holds a gsa_result and no GPU context.  Returns the number of variants (at most `cap` are stored).
+int64_t gsah_variant_records(const HostIndex *idx, const ContigResult &r, gsa_variant *out, int64_t cap, int64_t counts[3])
+{
+	int64_t n = 0; int d, c, g;
+	counts[0] = counts[1] = counts[2] = 0;
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		if (b.bdup) continue;
+		auto put = [&](int kind, int64_t rpos, int qpos, int len) {
+			counts[kind == 0 ? 0 : (kind == 1 || kind == 3 ? 1 : 2)]++;
+			if (n < cap) { gsa_variant &v = out[n]; idx->coordinate(rpos, &d, &c, &g); v.rpos = rpos; v.qpos = qpos; v.len = len; v.chr = b.chr; v.pos = g; v.kind = kind; v.block = (int32_t)bi; }
+			n++;
+		};
+		for (int64_t k = 0; k < b.n_frag; k++) {
+			const gsa_frag f = r.frag(b.frag_off + k);
+			if (f.bseed || (f.qlen == 0 && f.rlen == 0)) continue;
+			if (f.qlen == 0) put(2, f.rpos - 1, f.qpos - 1, f.rlen);
+			else if (f.rlen == 0) put(1, f.rpos - 1, f.qpos - 1, f.qlen);
+			else if (f.qlen == 1 && f.rlen == 1) { const char a1 = r.aln1[f.aln_off], a2 = r.aln2[f.aln_off]; if (nt4(a1) != nt4(a2) && nt4(a2) != 4) put(0, f.rpos, f.qpos, 0); }
+			else {
+				const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+				const int L = f.aln_len; int64_t rp = f.rpos; int qp = f.qpos;
+				for (int i = 0; i < L; i++) {
+					if (x1[i] == '-') { int m = 1; while (i + m < L && x1[i + m] == '-') m++; put(3, rp - 1, qp - 1, m); qp += m; i += m - 1; }
+					else if (x2[i] == '-') { int m = 1; while (i + m < L && x2[i + m] == '-') m++; put(4, rp - 1, qp - 1, m); rp += m; i += m - 1; }
+					else { if (nt4(x1[i]) != nt4(x2[i]) && nt4(x2[i]) != 4) put(0, rp, qp, 0); rp++; qp++; }
+				}
+			}
+		}
+	}
+	return n;
+}
+
+// VarVec from gsa_variant records (gsa_call_variants): the alleles are addressed in RefSequence / the query, as Emitter::variants leaves them
+void Emitter::variants_from(int query_idx, const QueryContig &q, const gsa_variant *v, int64_t n)
+{
+	static const int type_of[5] = { 0, 1, 2, 1, 2 };
+	const char *ref = idx->ref.data(), *qs = q.seq.data();
+	const size_t per = (size_t)1 << 20;
+	for (int64_t at = 0; at < n; at += (int64_t)per) {
+		const size_t m = (size_t)std::min<int64_t>((int64_t)per, n - at);
+		var_chunks.emplace_back();
+		std::vector<Variant> &vc = var_chunks.back(); vc.resize(m);
+		auto one = [&](size_t j0, size_t j1) {
+			for (size_t j = j0; j < j1; j++) {
+				const gsa_variant &g = v[at + (int64_t)j]; Variant &o = vc[j];
+				o.pos = g.pos; o.chr_idx = g.chr; o.query_idx = query_idx; o.type = type_of[g.kind >= 0 && g.kind < 5 ? g.kind : 0];      // (kinds are 0..4 by construction; a record from elsewhere must not index past the table)
+				gsa_variant_alleles(&g, ref, qs, &o.ref_p, &o.ref_n, &o.alt_p, &o.alt_n);
+			}
+		};
+		const size_t parts = m * sizeof(Variant) < par_min_bytes() ? 1 : (size_t)HostPool::global().threads();
+		if (parts <= 1) one(0, m); else HostPool::global().run(parts, [&](size_t k) { one(m * k / parts, m * (k + 1) / parts); });
+		for (size_t j = 0; j < m; j++) { const int t = vc[j].type; if (t == 0) n_snv++; else if (t == 1) n_ins++; else n_del++; }
 	}
 }
 

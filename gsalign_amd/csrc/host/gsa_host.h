@@ -87,6 +87,9 @@ struct ContigResult {
 // both outlive the Emitter's list (the index and the query contigs are loaded once per run)
 struct Variant { int pos, chr_idx, query_idx, type; const char *ref_p, *alt_p; uint32_t ref_n, alt_n; };
 
+// VariantIdentification as gsa_variant records (emit.cpp): the host walk in the layout and order of gsa_call_variants
+int64_t gsah_variant_records(const HostIndex *idx, const ContigResult &r, gsa_variant *out, int64_t cap, int64_t counts[3]);
+
 struct OutBuf;                             // par.h
 
 struct Emitter {
@@ -109,6 +112,8 @@ struct Emitter {
 	bool dotplot(const std::string &gp_path, const std::string &out_prefix, const QueryContig &q, const ContigResult &r, std::vector<std::string> *data_files = nullptr) const;
 	// VariantIdentification (SeqVariant.cpp:12-119); long blocks are dealt to the pool in record ranges
 	void variants(int query_idx, const QueryContig &q, ContigResult &r);
+	// the same list from the records of gsa_call_variants (the walk ran on the GPU): n variants of contig `query_idx`, in their serial order
+	void variants_from(int query_idx, const QueryContig &q, const gsa_variant *v, int64_t n);
 	// OutputSequenceVariants (SeqVariant.cpp:121-143)
 	void vcf(FILE *fp, const std::string &reference_label);
 	void vcf_text(const std::string &reference_label, const std::function<void(OutBuf &&)> &sink);

@@ -4,6 +4,7 @@
 #include <atomic>
 #include <algorithm>
 #include <cstring>
+#include <mutex>
 #include "gsa_host.h"
 #include "exact_sort.h"
 
@@ -119,6 +120,27 @@ int gsah_c_emit_fmt(const char *index_prefix, const char *query_fa, const char *
 	if (!fp) { if (err) strcpy(err, "cannot open VCF output"); return -3; }
 	em.vcf(fp, reference_label); fclose(fp);
 	return 0;
+}
+
+// VariantIdentification (SeqVariant.cpp:12-119) of one finished contig as gsa_variant records, on the host: the records gsa_call_variants gives, in the same
+// order.  out[cap]; returns the number of variants (call with cap = 0 to size `out`), < 0 on error.  counts = {SNVs, insertions, deletions}.  `seq` is not read: the
+// records address the alleles (gsa_variant_alleles).  The index of the last prefix stays loaded, behind a lock: calls from several threads take turns.
+long long gsah_c_variants(const char *index_prefix, const char *seq, int len, const gsa_result *res, gsa_variant *out, long long cap, long long counts[3])
+{
+	static std::mutex mu; static std::string have; static HostIndex *idx = nullptr;
+	std::lock_guard<std::mutex> lock(mu);
+	(void)seq; (void)len;
+	if (!index_prefix || !res || !counts || (cap > 0 && !out)) return -1;
+	if (!idx || have != index_prefix) {
+		delete idx; idx = new HostIndex; have.clear(); std::string e;
+		if (!gsah_load_index(index_prefix, *idx, e)) { delete idx; idx = nullptr; return -2; }
+		have = index_prefix;
+	}
+	ContigResult cr; cr.assign(*res);
+	int64_t cnt[3];
+	const int64_t n = gsah_variant_records(idx, cr, out, cap, cnt);
+	for (int k = 0; k < 3; k++) counts[k] = cnt[k];
+	return n;
 }
 
 // OutputDotplot for one contig: script + data files (no gnuplot run).  Returns 1 if something was written.

@@ -47,7 +47,8 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -no_vcf        do not write the VCF file\n");
 	fprintf(stderr, "         -gpu   LIST    GPU ordinals, comma separated [0]\n");
 	fprintf(stderr, "         -ctx   INT     contexts per GPU working on different query sequences [2]\n");
-	fprintf(stderr, "         -timing        print where the wall time went (one JSON line on stderr)\n\n");
+	fprintf(stderr, "         -timing        print where the wall time went (one JSON line on stderr)\n");
+	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n\n");
 }
 
 static bool check_prefix(const char *p)                     // CheckOutputPrefix (main.cpp:116-138)
@@ -77,7 +78,7 @@ int main(int argc, char *argv[])
 	//  kernel and faulting it in again for the next contig)
 	mallopt(M_MMAP_THRESHOLD, 1 << 30); mallopt(M_TRIM_THRESHOLD, 1 << 30); mallopt(M_TOP_PAD, 256 << 20);
 	gsa_params prm; gsa_default_params(&prm);
-	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, timing = getenv("GSA_TIMING") != NULL;
+	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, timing = getenv("GSA_TIMING") != NULL;
 	std::vector<int> gpus;
 	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL;
 	if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(argv[0], threads, prm, fmt); return 0; }
@@ -106,6 +107,7 @@ int main(int argc, char *argv[])
 		else if (a == "-gpu" && i + 1 < argc) { for (const char *p = argv[++i]; *p;) { gpus.push_back(atoi(p)); while (*p && *p != ',') p++; if (*p == ',') p++; } }
 		else if (a == "-ctx" && i + 1 < argc) { n_ctx_per_gpu = atoi(argv[++i]); if (n_ctx_per_gpu < 1) n_ctx_per_gpu = 1; }
 		else if (a == "-timing") timing = true;
+		else if (a == "-gpuvar") gpuvar = true;
 		else if (a == "-dp") dotplot = true;
 		else if (a == "-gp" && i + 1 < argc) gnuplot_arg = argv[++i];      // main.cpp:285: the path of gnuplot, used as given
 		else if (a == "-d" || a == "-debug") { /* debug printers: not reproduced */ }
@@ -226,8 +228,10 @@ int main(int argc, char *argv[])
 	// finished contigs: copied by the GPU worker that produced them (on_result), taken in contig order by the formatter thread
 	struct Sink {
 		std::mutex mu; std::condition_variable cv; std::vector<ContigResult> res; std::vector<char> ready; bool abort = false; double copy_s = 0;
+		std::vector<RawArr<gsa_variant> > var;      // -gpuvar: the contig's variants as gsa_call_variants left them
 	} sink;
-	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0);
+	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size());
+	const bool var_on_gpu = gpuvar && vcf;          // (-no_vcf: nobody reads the variants)
 	// the MAF file: created by the first contig that has alignments ("w" for contig 0, "a" afterwards: tools.cpp:158-163 -- a run whose
 	// first contig aligns nowhere appends to whatever the file held, as the reference does)
 	int maf_fd = -1; std::unique_ptr<OrderedWriter> maf_w;
@@ -257,7 +261,12 @@ int main(int argc, char *argv[])
 			if (fp) { em.aln(fp, qs[ci], cr); if (ferror(fp) | fclose(fp)) out_failed = true; }
 			else if (!out_failed) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", aln.c_str(), strerror(errno)); }
 		}
-		if (vcf) { const double t = now_s(); em.variants((int)ci, qs[ci], cr); t_var += now_s() - t; }
+		if (vcf) {
+			const double t = now_s();
+			if (var_on_gpu) { em.variants_from((int)ci, qs[ci], sink.var[ci].data(), (int64_t)sink.var[ci].size()); sink.var[ci].reset(); }
+			else em.variants((int)ci, qs[ci], cr);
+			t_var += now_s() - t;
+		}
 		if (dotplot && !gnuplot.empty()) {                               // GSAlign.cpp:546: only when gnuplot was found (main.cpp:324)
 			const std::string gp = std::string(out_prefix) + ".gp";
 			std::vector<std::string> data_files;
@@ -288,14 +297,29 @@ int main(int argc, char *argv[])
 		sk.cv.notify_all();
 		return 0;
 	};
+	// -gpuvar: the worker runs the variant pass in front of the callback (gsa_align_many_variants); the records are copied like the result
+	auto on_result_var = [](void *user, int32_t ci, const gsa_result *res, const gsa_variants *var) -> int {
+		Sink &sk = *(Sink *)user;
+		const double t = now_s();
+		sk.res[(size_t)ci].assign(*res);
+		sk.var[(size_t)ci].assign(var->v, (size_t)var->n);
+		const double dt = now_s() - t;
+		{ std::lock_guard<std::mutex> lk(sk.mu); sk.ready[(size_t)ci] = 1; sk.copy_s += dt; }
+		sk.cv.notify_all();
+		return 0;
+	};
+	if (timing && var_on_gpu) for (gsa_ctx *c : ctxs) (void)gsa_set_profiling(c, 8);      // (the variant passes' device time, for the GSA_VARIANT_PASS line)
 	const double ta = now_s(); t_at_align = ta - T0;
-	const int rc_many = gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
+	const int rc_many = var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
+	                               : gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
 	t_align = now_s() - ta;
 	// where the contexts' host threads spent that time (gsa_get_wall_sums: [0] query set-up / wait for the upload, [s] stage s) and what growing buffers cost them
 	if (timing && getenv("GSA_DUMP_BUFFERS")) for (gsa_ctx *c : ctxs) (void)gsa_debug_buffers(c, 24);
+	double var_dev_ms = 0; long long var_dev_n = 0;      // -gpuvar: device time of the variant passes (hipEvents), all contexts
 	double wall_sum[10] = { 0 }; double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 	for (gsa_ctx *c : ctxs) {
 		double w[10]; int64_t wn = 0; if (gsa_get_wall_sums(c, w, &wn) == GSA_OK) for (int k = 0; k < 9; k++) wall_sum[k] += w[k];
+		double vm = 0; int64_t vn = 0; if (gsa_get_variant_timing(c, &vm, &vn) == GSA_OK) { var_dev_ms += vm; var_dev_n += vn; }
 		double am = 0; int64_t an = 0, ab = 0; if (gsa_get_alloc_stats(c, &am, &an, &ab) == GSA_OK) { alloc_ms += am; alloc_n += an; alloc_bytes += ab; }
 	}
 	{ std::lock_guard<std::mutex> lk(sink.mu); if (rc_many != GSA_OK) sink.abort = true; }
@@ -348,6 +372,7 @@ int main(int argc, char *argv[])
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
 		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9);
 	}
+	if (timing && var_on_gpu) fprintf(stderr, "GSA_VARIANT_PASS {\"device_ms_sum\": %.3f, \"passes\": %lld, \"query_bp\": %lld}\n", var_dev_ms, var_dev_n, [&] { long long b = 0; for (const QueryContig &q : qs) b += (long long)q.seq.size(); return b; }());
 	// (everything is on disk and the GPU is released: the process ends here -- unwinding 20 GB of host buffers and the HIP runtime's own
 	//  teardown cost a second or two of wall time at human scale and produce nothing)
 	if (out_failed) fprintf(stderr, "Error! an output file could not be written completely (disk full?)\n");

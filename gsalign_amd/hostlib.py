@@ -86,3 +86,37 @@ def dotplot(index_prefix: str, query_fa: str, contig: int, gp_path: str, out_pre
     if rc < 0:
         raise RuntimeError(f"gsah_c_dotplot -> {rc}: {err.value.decode()}")
     return rc == 1
+
+
+def result_from_arrays(r: dict, keep: list):
+    """A result dict of capi.Aligner (blocks / frags / aln1 / aln2, records where the blocks' frag_off says) -> a populated capi.Result."""
+    B = np.ascontiguousarray(r["blocks"]); R = capi.pack_recs(r["frags"])
+    a1 = np.ascontiguousarray(r["aln1"]); a2 = np.ascontiguousarray(r["aln2"])
+    keep.extend([B, R, a1, a2])
+    res = capi.Result()
+    res.n_blocks = B.size; res.n_frags = R.size; res.n_aln = a1.size
+    res.blocks = C.cast(B.ctypes.data, C.POINTER(capi.Block)); res.recs = C.cast(R.ctypes.data, C.POINTER(capi.Rec))
+    res.aln1 = C.cast(a1.ctypes.data, C.POINTER(C.c_char)); res.aln2 = C.cast(a2.ctypes.data, C.POINTER(C.c_char))
+    return res
+
+
+def variants(index_prefix: str, seq: np.ndarray, result):
+    """gsah_c_variants: VariantIdentification of one finished contig on the host, as gsa_variant records in the serial order -- what
+    Aligner.call_variants computes on the GPU.  result: a capi.Result, a dump dict (oracle layout) or a result dict of capi.Aligner.
+    Returns (VARIANT_DT array, (n_snv, n_ins, n_del))."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    lib = load()
+    lib.gsah_c_variants.restype = C.c_longlong
+    lib.gsah_c_variants.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.POINTER(capi.Result), C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    cnt = (C.c_longlong * 3)()
+    n = lib.gsah_c_variants(index_prefix.encode(), C.c_void_p(seq.ctypes.data), int(seq.size), C.byref(result), None, 0, cnt)
+    if n < 0:
+        raise RuntimeError(f"gsah_c_variants -> {n}")
+    V = np.zeros(int(n), capi.VARIANT_DT)
+    if n:
+        n2 = lib.gsah_c_variants(index_prefix.encode(), C.c_void_p(seq.ctypes.data), int(seq.size), C.byref(result), C.c_void_p(V.ctypes.data), n, cnt)
+        assert n2 == n
+    return V, (int(cnt[0]), int(cnt[1]), int(cnt[2]))

@@ -268,6 +268,51 @@ int gsa_align_many(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query,
  * gsa_align_many bundles contigs of at most 16 Mb by itself (gsa_set_option "bundle_contig"; bundles of about "bundle_cap" = 64 Mb at most). */
 int gsa_align_bundle(gsa_ctx *ctx, const char *const *query, const int32_t *qlen, int32_t n, uint32_t flags, gsa_result *out);
 
+/* ---- sequence variants ------------------------------------------------------
+ * Replaces VariantIdentification (SeqVariant.cpp:12-119), the step GenomeComparison's caller runs on every finished AlnBlockVec: the
+ * walk over the non-seed pairs of all blocks that are not duplicates (:20-29) -- a pure deletion / insertion gives one record
+ * (:32-51), a 1 x 1 pair a substitution when the two bases differ and the query's is not ambiguous (:52-63), every other pair is
+ * walked column by column over its two gapped strings (:64-115).  The walk runs on the device, on what the alignment left there
+ * (records, op strings, the two sequences): nothing but the variants crosses PCIe.
+ *
+ * one variant, 32 bytes; alleles are pieces of RefSequence / the query, addressed not copied */
+typedef struct { int64_t rpos; int32_t qpos, len, chr, pos, kind, block; } gsa_variant;
+/* kind: 0 substitution       REF = ref[rpos]            ALT = query[qpos]
+         1 insertion record   REF = ref[rpos]            ALT = query[qpos .. qpos+len]     (rpos, qpos = the anchors, i.e. record position - 1)
+         2 deletion record    REF = ref[rpos .. rpos+len]  ALT = query[qpos]
+         3 insertion in an aligned gap   REF = query[qpos] (sic, SeqVariant.cpp:73-76: the anchor is the first byte of the QUERY piece)   ALT = query[qpos .. qpos+len]
+         4 deletion in an aligned gap    REF = ref[rpos .. rpos+len]           ALT = ref[rpos]
+   (a .. b inclusive: len + 1 bytes.)  VCF TYPE = {SUBSTITUTE, INSERT, DELETE, INSERT, DELETE}[kind]; len = 0 for kind 0;
+   chr = the BLOCK's reference sequence (Variant.chr_idx = ABiter->coor.ChromosomeIdx, :24), pos = GenCoordinateInfo(rpos).gPos, the position's own look-up;
+   block = index into gsa_result::blocks.  Order: blocks in result order, records in order, columns in order (the order VarVec grows in). */
+typedef struct { int64_t n; const gsa_variant *v; int64_t n_snv, n_ins, n_del; } gsa_variants;
+static inline void gsa_variant_alleles(const gsa_variant *v, const char *ref, const char *query,
+                                       const char **ref_p, uint32_t *ref_n, const char **alt_p, uint32_t *alt_n)
+{
+	const char *r = ref + v->rpos, *q = query + v->qpos;
+	const uint32_t n = (uint32_t)v->len + 1;
+	switch (v->kind) {
+	case 1:  *ref_p = r; *ref_n = 1; *alt_p = q; *alt_n = n; break;
+	case 2:  *ref_p = r; *ref_n = n; *alt_p = q; *alt_n = 1; break;
+	case 3:  *ref_p = q; *ref_n = 1; *alt_p = q; *alt_n = n; break;
+	case 4:  *ref_p = r; *ref_n = n; *alt_p = r; *alt_n = 1; break;
+	default: *ref_p = r; *ref_n = 1; *alt_p = q; *alt_n = 1; break;
+	}
+}
+/* The variants of the stage-8 result the context holds: valid after gsa_align_contig[_device], gsa_finish_contig, gsa_run_to(8) and
+ * gsa_align_bundle, until the next call that changes the context (GSA_ERR_STATE otherwise, and when a prefetch has overwritten the
+ * contig's device copy; a contig given as a device buffer must still be there).  k = 0 for a single contig, the contig's index for a
+ * bundle: positions and `block` are relative to contig k, i.e. exactly what the single-contig call on query[k] gives; k out of range:
+ * GSA_ERR_ARG.  No blocks: n = 0.  Memory is owned by the context and valid until the next call on it. */
+int gsa_call_variants(gsa_ctx *ctx, int32_t k, gsa_variants *out);
+/* measurement: device time (two hipEvents around the pass on the library's stream) of the gsa_call_variants passes of this context since
+ * gsa_set_profiling(ctx, 8) switched that timing on, and their number; without that flag nothing is recorded and both stay 0 */
+int gsa_get_variant_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+/* gsa_align_many with the variant pass run by the worker in front of the callback: *var is valid during the callback only, like *res */
+typedef int (*gsa_result_var_fn)(void *user, int32_t contig, const gsa_result *res, const gsa_variants *var);
+int gsa_align_many_variants(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
+                            uint32_t flags, gsa_result_var_fn on_result, void *user);
+
 /* ---- one long contig on several GPUs ---------------------------------------
  * IdentifyLocalMEM hands 10 000-bp chunks of the contig to whichever thread is free (GSAlign.cpp:61-94) and seeds never
  * cross a chunk edge, so the seed search of one contig splits by chunk range: every GPU runs gsa_seed_chunks on its range
@@ -360,7 +405,8 @@ int gsa_debug_buffers(gsa_ctx *ctx, int top);
  * which also records, per search, how many Occ blocks the reference's walk reads, so that counters[0]
  * is exact (same seeds either way; the default build leaves counters[0] = 0); bit 2 = time the seed
  * search kernel only (kernel_ms[0]; two events per contig instead of ten); kernel_ms[6] is then the SUM of that time over
- * all contigs since the flag was set (what a benchmark divides by its contig count). */
+ * all contigs since the flag was set (what a benchmark divides by its contig count); bit 3 = time the gsa_call_variants passes
+ * (gsa_get_variant_timing; changes nothing else: bundles stay, kernel_ms[] is not touched). */
 int gsa_set_profiling(gsa_ctx *ctx, int flags);
 /* How the seed search of the last contig went (IdentifyLocalMEM, GSAlign.cpp:51-107):
  * [0] most resolver rounds of a chunk, [1] chunks redone by the dense search (every start position in parallel: the
