@@ -22,6 +22,7 @@ EXPORTS = [
     "gsa_bwt_search_batch", "gsa_ksw2_batch", "gsa_gap_similarity_batch", "gsa_get_counters", "gsa_get_timings", "gsa_set_profiling", "gsa_bind_host_thread",
     "gsa_prefetch_contig", "gsa_prefetch_bundle", "gsa_cancel_prefetch", "gsa_get_wall_sums", "gsa_get_alloc_stats", "gsa_debug_buffers", "gsa_set_option", "gsa_host_register", "gsa_host_unregister",
     "gsa_call_variants", "gsa_align_many_variants", "gsa_get_variant_timing",
+    "gsa_block_cigars", "gsa_get_cigar_timing", "gsa_align_many_ex",
 ]
 
 
@@ -98,6 +99,38 @@ def variant_alleles(V: np.ndarray, ref, query) -> list:
         else:
             out.append((ref[r:r + 1], query[q:q + 1]))
     return out
+
+
+class BlockCigar(C.Structure):
+    """gsa_block_cigar, 32 bytes (include/gsa_hip.h): where a block's ops lie and its columns per class."""
+    _fields_ = [("cig_off", C.c_int64), ("n_cig", C.c_int32), ("n_eq", C.c_int32), ("n_x", C.c_int32), ("n_ins", C.c_int32), ("n_del", C.c_int32), ("_pad", C.c_int32)]
+
+
+class Cigars(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("n_ops", C.c_int64), ("blk", C.POINTER(BlockCigar)), ("ops", C.POINTER(C.c_uint32))]
+
+
+class Extras(C.Structure):
+    _fields_ = [("var", C.POINTER(Variants)), ("cig", C.POINTER(Cigars))]
+
+
+BLOCK_CIGAR_DT = np.dtype([("cig_off", "<i8"), ("n_cig", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"), ("_pad", "<i4")])
+CIGAR_LETTERS = "MIDNSHP=X"      # by BAM op code; the library writes I (1), D (2), = (7) and X (8)
+WANT_VARIANTS, WANT_CIGARS = 1, 2
+
+
+def cigars_arrays(cig: "Cigars"):
+    """gsa_cigars -> (BLOCK_CIGAR_DT array, uint32 ops), both copies."""
+    nb, no = int(cig.n_blocks), int(cig.n_ops)
+    blk = np.ctypeslib.as_array(C.cast(cig.blk, C.POINTER(C.c_uint8)), shape=(nb * BLOCK_CIGAR_DT.itemsize,)).view(BLOCK_CIGAR_DT).copy() if nb else np.zeros(0, BLOCK_CIGAR_DT)
+    ops = np.ctypeslib.as_array(cig.ops, shape=(no,)).copy() if no else np.zeros(0, np.uint32)
+    return blk, ops
+
+
+def cigar_string(ops) -> str:
+    """ops (len << 4 | code) as PAF's cg string: the numpy form of gsa_cigar_string (include/gsa_hip.h)."""
+    ops = np.asarray(ops, dtype=np.uint32)
+    return "".join(f"{int(o) >> 4}{CIGAR_LETTERS[int(o) & 15] if int(o) & 15 < len(CIGAR_LETTERS) else '?'}" for o in ops)
 
 
 FRAG_DT = np.dtype([("bseed", "<i4"), ("qpos", "<i4"), ("qlen", "<i4"), ("rlen", "<i4"), ("rpos", "<i8"), ("aln_off", "<i8"), ("aln_len", "<i4"), ("_pad", "<i4")])
@@ -186,6 +219,7 @@ def bind_host_thread(device: int = 0) -> None:
 
 RESULT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(Result))
 RESULT_VAR_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(Result), C.POINTER(Variants))
+RESULT_EX_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.POINTER(Result), C.POINTER(Extras))
 
 
 class DeviceContig:
@@ -205,7 +239,7 @@ class DeviceContig:
             self.lib.gsa_device_free(self.device, C.c_void_p(self.ptr)); self.ptr = None
 
 
-def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False) -> None:
+def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False) -> None:
     """gsa_align_many: `contigs` (uint8 arrays, or DeviceContig objects -- all of one kind) on the given contexts, one host
     thread per context inside the library.  on_result(contig_index, Result) runs on the worker threads (the Result is valid
     during the call only).  in_order: hand the contigs out as listed (GSA_MANY_IN_ORDER) instead of longest first.
@@ -213,7 +247,9 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     prefetch=False: GSA_MANY_NO_PREFETCH (a contig is uploaded when its turn comes; by default a context uploads its next contig
     while it aligns the current one).
     variants=True: gsa_align_many_variants -- the worker runs the variant pass first and on_result(contig_index, Result, Variants) gets its records too
-    (variants_array copies them out)."""
+    (variants_array copies them out).
+    cigars=True: gsa_align_many_ex with GSA_WANT_CIGARS (and GSA_WANT_VARIANTS when variants=True) -- on_result(contig_index, Result, Variants or None, Cigars)
+    (cigars_arrays copies them out)."""
     lib = aligners[0].lib
     n = len(contigs)
     ctxs = (C.c_void_p * len(aligners))(*[a.ctx for a in aligners])
@@ -221,7 +257,14 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     qs = (C.c_char_p * n)(*[C.cast(c.ptr if on_dev else c.ctypes.data, C.c_char_p) for c in contigs])
     ql = (C.c_int32 * n)(*[int(c.size) for c in contigs])
     flags = (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16)
-    if variants:
+    if cigars:
+        def ex_cb(user, ci, res, ex):
+            e = ex.contents
+            return int((on_result(ci, res.contents, e.var.contents if e.var else None, e.cig.contents if e.cig else None) if on_result else 0) or 0)
+        cbx = RESULT_EX_FN(ex_cb)
+        lib.gsa_align_many_ex.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.c_uint32, RESULT_EX_FN, C.c_void_p]
+        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, WANT_CIGARS | (WANT_VARIANTS if variants else 0), cbx, None)
+    elif variants:
         cbv = RESULT_VAR_FN(lambda user, ci, res, var: int((on_result(ci, res.contents, var.contents) if on_result else 0) or 0))
         lib.gsa_align_many_variants.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_VAR_FN, C.c_void_p]
         rc = lib.gsa_align_many_variants(ctxs, len(aligners), qs, ql, n, flags, cbv, None)
@@ -231,7 +274,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
         rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, flags, cb, None)
     if rc != 0:
         msgs = [lib.gsa_last_error(a.ctx).decode() for a in aligners]
-        raise GsaError(f"gsa_align_many{'_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
+        raise GsaError(f"gsa_align_many{'_ex' if cigars else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
 
 
 def _p(a, t):
@@ -465,6 +508,20 @@ class Aligner:
         self.lib.gsa_call_variants.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Variants)]
         self._ck(self.lib.gsa_call_variants(self.ctx, C.c_int32(k), C.byref(var)))
         return variants_array(var)
+
+    def block_cigars(self, k: int = 0):
+        """gsa_block_cigars on the stage-8 result this context holds (contig k of a bundle): (BLOCK_CIGAR_DT array, one entry per block; uint32 ops)."""
+        cig = Cigars()
+        self.lib.gsa_block_cigars.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Cigars)]
+        self._ck(self.lib.gsa_block_cigars(self.ctx, C.c_int32(k), C.byref(cig)))
+        return cigars_arrays(cig)
+
+    def cigar_timing(self):
+        """(host wall ms inside gsa_block_cigars on this context since it was created, number of calls)."""
+        ms = C.c_double(0); n = C.c_int64(0)
+        self.lib.gsa_get_cigar_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        self._ck(self.lib.gsa_get_cigar_timing(self.ctx, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def variant_timing(self):
         """(device ms summed over the variant passes since set_profiling(..., variants=True), number of passes)."""

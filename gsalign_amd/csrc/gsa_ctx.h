@@ -234,6 +234,10 @@ struct gsa_ctx {
 	// ---- variants (k_variants.hip): block table, per-record counts, per-workgroup sums + kind counters, the output; pinned: block table, header {n, kinds}, output ----
 	DevBuf d_vblk, d_vcnt, d_vwg, d_var, p_vblk, p_vhdr, p_var;
 	bool prof_var = false; hipEvent_t ev_var[2] = {nullptr, nullptr}; double var_ms_sum = 0; long long var_calls = 0;      // device time of the variant passes since gsa_set_profiling (gsa_get_variant_timing)
+	// ---- per-block CIGARs (k_cigar.hip): block table in / out, per-record run-start and column counts, per-workgroup sums, their prefix sums, the run starts {column << 4 | class}, the ops;
+	// pinned: block table in, header {ops, columns, records without a job}, block table out, ops ----
+	DevBuf d_cblk, d_cout, d_ccnt, d_cwg, d_cpre, d_crun, d_cops, p_cblk, p_chdr, p_cout, p_cops;
+	double cig_ms_sum = 0; long long cig_calls = 0;      // host wall time inside gsa_block_cigars (always on: two clock reads per call)
 	// what growing buffers cost this context (dev_ensure / pin_ensure: hipMalloc, hipHostMalloc, the frees and the quiesce in front of them) -- gsa_get_alloc_stats
 	double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 };
@@ -299,6 +303,7 @@ int stage78_extend(gsa_ctx *c);       // k_extend.hip  (S7: classification, DP, 
 int run_gapsim_jobs(gsa_ctx *c, i32 n, const i32 *d_n, const i32 *d_q1, const i32 *d_q2, const i64 *d_r1, const i64 *d_r2, i32 *d_res, const i32 *d_jseed, i32 *d_cut4);   // k_gapsim.hip
 void dp_count_cells(gsa_ctx *c, i32 n_ub, const i32 *len1, const i32 *len2, hipStream_t stream);   // k_dp.hip (profiling)
 int call_variants(gsa_ctx *c, i32 k, gsa_variants *out);   // k_variants.hip  (VariantIdentification over the stage-8 result of contig k)
+int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out);      // k_cigar.hip  (the CIGAR of every block of the stage-8 result of contig k)
 struct LgJob { i32 job, m, n; };
 int launch_stripes(gsa_ctx *c, hipStream_t ss, std::vector<LgJob> &large, const uint8_t *pool1, const i64 *off1, const uint8_t *pool2, const i64 *off2,
                    uint8_t *ops, const i64 *ops_off, i32 *ops_len, uint8_t *rev, int err_slot);   // k_dp.hip

@@ -91,6 +91,8 @@ template <class T> void RawArr<T>::assign(const T *src, size_t count)
 template struct RawArr<gsa_rec>;
 template struct RawArr<char>;
 template struct RawArr<gsa_variant>;
+template struct RawArr<gsa_block_cigar>;
+template struct RawArr<uint32_t>;
 void ContigResult::assign(const gsa_result &r)
 {
 	blocks.assign(r.blocks, r.blocks + r.n_blocks);
@@ -315,6 +317,121 @@ void Emitter::maf(FILE *fp, bool first, const QueryContig &q, ContigResult &r) c
 	maf_text(first, q, r, [&](OutBuf &&o) { if (o.n) fwrite(o.p, 1, o.n, fp); }, [](size_t c) { return OutBuf(c); });
 }
 
+// ---- PAF ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+inline char *put_int(char *p, long long v)
+{
+	char tmp[24]; int n = 0; bool neg = v < 0; unsigned long long u = neg ? 0ull - (unsigned long long)v : (unsigned long long)v;
+	do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
+	if (neg) *p++ = '-';
+	while (n) *p++ = tmp[--n];
+	return p;
+}
+
+inline uint32_t column_class(char a1, char a2)      // gsa_hip.h: reference row, query row
+{
+	if (a1 == '-') return GSA_CIGAR_INS;
+	if (a2 == '-') return GSA_CIGAR_DEL;
+	const int x = nt4((unsigned char)a1);
+	return x < 4 && x == nt4((unsigned char)a2) ? GSA_CIGAR_EQ : GSA_CIGAR_X;
+}
+inline int32_t *class_count(gsa_block_cigar &bc, uint32_t cls) { return cls == GSA_CIGAR_EQ ? &bc.n_eq : (cls == GSA_CIGAR_X ? &bc.n_x : (cls == GSA_CIGAR_INS ? &bc.n_ins : &bc.n_del)); }
+}
+
+void gsah_block_cigars(const char *seq, const ContigResult &r, std::vector<gsa_block_cigar> &blk, std::vector<uint32_t> &ops)
+{
+	blk.assign(r.blocks.size(), gsa_block_cigar());
+	ops.clear();
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		gsa_block_cigar &bc = blk[bi];
+		memset(&bc, 0, sizeof(bc));
+		bc.cig_off = (int64_t)ops.size();
+		uint32_t cur = 0; uint64_t run = 0;
+		auto column = [&](uint32_t cls) {
+			if (cls != cur) { if (run) ops.push_back((uint32_t)(run << 4) | cur); cur = cls; run = 0; }
+			run++; (*class_count(bc, cls))++;
+		};
+		for (int64_t k = 0; k < b.n_frag; k++) {
+			const gsa_frag f = r.frag(b.frag_off + k);
+			if (f.bseed) { for (int i = 0; i < f.qlen; i++) column(seq ? column_class(seq[f.qpos + i], seq[f.qpos + i]) : GSA_CIGAR_EQ); }      // a seed prints the QUERY text on both lines
+			else { const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off; for (int i = 0; i < f.aln_len; i++) column(column_class(x1[i], x2[i])); }
+		}
+		if (run) ops.push_back((uint32_t)(run << 4) | cur);
+		bc.n_cig = (int32_t)((int64_t)ops.size() - bc.cig_off);
+		if (!b.bdir) std::reverse(ops.begin() + bc.cig_off, ops.end());      // SelfComplementarySeq: the two lines are printed back to front
+	}
+}
+
+void gsah_cigar_trim(const uint32_t *ops, int bdir, int64_t ext, std::vector<uint32_t> &out, gsa_block_cigar &bc)
+{
+	int64_t lo = 0, hi = bc.n_cig;      // the ops that stay: [lo, hi), the one at the cut shortened
+	uint32_t edge = 0; bool cut = false;
+	while (ext > 0 && lo < hi) {
+		const int64_t at = bdir ? hi - 1 : lo;
+		const uint32_t cls = ops[at] & 15u; const int64_t len = ops[at] >> 4;
+		const int64_t take = len <= ext ? len : ext;
+		*class_count(bc, cls) -= (int32_t)take; ext -= take;
+		if (take == len) { if (bdir) hi--; else lo++; }
+		else { edge = (uint32_t)((len - take) << 4) | cls; cut = true; }
+	}
+	out.assign(ops + lo, ops + hi);
+	if (cut && !out.empty()) { if (bdir) out.back() = edge; else out.front() = edge; }
+	bc.n_cig = (int32_t)out.size();
+}
+
+void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink) const
+{
+	std::vector<gsa_block_cigar> own_blk; std::vector<uint32_t> own_ops, cut;
+	if (!blk) { gsah_block_cigars(q.seq.data(), r, own_blk, own_ops); blk = own_blk.data(); ops = own_ops.data(); }
+	OutBuf o;
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		gsa_block &b = r.blocks[bi];
+		if (!allow_dup && b.bdup) continue;
+		if (b.n_frag <= 0) continue;
+		const int64_t f0 = b.frag_off;
+		gsa_frag last = r.frag(f0 + b.n_frag - 1);
+		const int ext = extension(*idx, b, last);
+		gsa_block_cigar bc = blk[bi];
+		const uint32_t *bo = ops + bc.cig_off;
+		if (ext > 0) {      // (as maf_block: the block and its last record are shortened for whoever looks at them next -- the variant walk, the dot plot)
+			b.aln_len -= ext; b.score -= ext; last.rlen -= ext; last.qlen -= ext; r.trim(f0 + b.n_frag - 1, ext);
+			gsah_cigar_trim(bo, b.bdir, ext, cut, bc); bo = cut.data();
+		}
+		const long long cols = (long long)bc.n_eq + bc.n_x + bc.n_ins + bc.n_del;
+		const long long qbases = (long long)bc.n_eq + bc.n_x + bc.n_ins, rbases = (long long)bc.n_eq + bc.n_x + bc.n_del;
+		const long long qsize = (long long)q.seq.size();
+		long long qs, qe, ts;
+		if (b.bdir) { qs = r.frag(f0).qpos; qe = qs + qbases; ts = b.gpos - 1; }
+		else {
+			// the MAF line gives start = qlen - (last.qpos + last.qlen) on the '-' strand: on the forward strand the block ends there
+			qe = (long long)last.qpos + last.qlen; qs = qe - qbases;
+			int d, c, g; idx->coordinate(last.rpos + last.rlen - 1, &d, &c, &g); ts = g - 1;
+		}
+		const std::string &rname = idx->chr_name[b.chr];
+		o.reserve(o.n + q.name.size() + rname.size() + 256 + (size_t)bc.n_cig * 11);
+		char *w = o.p + o.n;
+		memcpy(w, q.name.data(), q.name.size()); w += q.name.size(); *w++ = '\t';
+		w = put_int(w, qsize); *w++ = '\t'; w = put_int(w, qs); *w++ = '\t'; w = put_int(w, qe); *w++ = '\t';
+		*w++ = b.bdir ? '+' : '-'; *w++ = '\t';
+		memcpy(w, rname.data(), rname.size()); w += rname.size(); *w++ = '\t';
+		w = put_int(w, idx->chr_len[b.chr]); *w++ = '\t'; w = put_int(w, ts); *w++ = '\t'; w = put_int(w, ts + rbases); *w++ = '\t';
+		w = put_int(w, bc.n_eq); *w++ = '\t'; w = put_int(w, cols); memcpy(w, "\t255\tNM:i:", 10); w += 10;
+		w = put_int(w, (long long)bc.n_x + bc.n_ins + bc.n_del); memcpy(w, "\tAS:i:", 6); w += 6;
+		w = put_int(w, b.bdup ? 1 : b.score); memcpy(w, b.bdup ? "\ttp:A:S\tcg:Z:" : "\ttp:A:P\tcg:Z:", 13); w += 13;
+		w += gsa_cigar_string(bo, bc.n_cig, w, (size_t)bc.n_cig * 11 + 1);
+		*w++ = '\n';
+		o.n = (size_t)(w - o.p);
+		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
+	}
+	if (o.n) sink(std::move(o));
+}
+
+void Emitter::paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops) const
+{
+	paf_text(q, r, blk, ops, [&](OutBuf &&o) { if (o.n) fwrite(o.p, 1, o.n, fp); });
+}
+
 void Emitter::aln(FILE *fp, const QueryContig &q, ContigResult &r) const
 {
 	std::string t1, t2;
@@ -524,17 +641,6 @@ void Emitter::variants(int query_idx, const QueryContig &q, ContigResult &r)
 		});
 		for (size_t k = 0; k < parts; k++) { n_snv += cnts[k][0]; n_ins += cnts[k][1]; n_del += cnts[k][2]; }
 	}
-}
-
-namespace {
-inline char *put_int(char *p, long long v)
-{
-	char tmp[24]; int n = 0; bool neg = v < 0; unsigned long long u = neg ? 0ull - (unsigned long long)v : (unsigned long long)v;
-	do { tmp[n++] = (char)('0' + u % 10); u /= 10; } while (u);
-	if (neg) *p++ = '-';
-	while (n) *p++ = tmp[--n];
-	return p;
-}
 }
 
 // OutputSequenceVariants (SeqVariant.cpp:121-143).  The reference std::sorts VarVec on (chr_idx, pos) -- an incomplete key: the order of

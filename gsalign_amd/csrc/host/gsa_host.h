@@ -90,6 +90,14 @@ struct Variant { int pos, chr_idx, query_idx, type; const char *ref_p, *alt_p; u
 // VariantIdentification as gsa_variant records (emit.cpp): the host walk in the layout and order of gsa_call_variants
 int64_t gsah_variant_records(const HostIndex *idx, const ContigResult &r, gsa_variant *out, int64_t cap, int64_t counts[3]);
 
+// The CIGAR of every block of a finished contig (gsa_block_cigar / ops as in gsa_hip.h), computed from the gapped strings and the seed records themselves,
+// UNTRIMMED: what gsa_block_cigars computes on the device from op strings -- its comparator, and the CIGAR source of a host that holds a gsa_result and no GPU
+// context.  seq (may be NULL) = the query contig: a seed's columns are then classified from its text like any other column, else taken as '='.
+void gsah_block_cigars(const char *seq, const ContigResult &r, std::vector<gsa_block_cigar> &blk, std::vector<uint32_t> &ops);
+// iExtension's trim (tools.cpp:192-202) on a block's ops: the last `ext` columns IN WALK ORDER go -- the last ops of a forward block, the FIRST ones of a
+// reverse-strand block (its ops are in output order).  out = the ops that stay; bc's op count and columns per class are reduced by what was removed.
+void gsah_cigar_trim(const uint32_t *ops, int bdir, int64_t ext, std::vector<uint32_t> &out, gsa_block_cigar &bc);
+
 struct OutBuf;                             // par.h
 
 struct Emitter {
@@ -104,6 +112,10 @@ struct Emitter {
 	// `take(n)` supplies the large buffers (OrderedWriter::take recycles them)
 	void maf_text(bool first, const QueryContig &q, ContigResult &r, const std::function<void(OutBuf &&)> &sink, const std::function<OutBuf(size_t)> &take) const;
 	void maf_block(const QueryContig &q, ContigResult &r, gsa_block &b, OutBuf &small, const std::function<void(OutBuf &&)> &sink, const std::function<OutBuf(size_t)> &take) const;
+	// PAF: one line per block with its cg:Z: CIGAR, blocks selected and trimmed (iExtension) like OutputMAF's; blk / ops = the contig's CIGARs from gsa_block_cigars,
+	// or NULL: computed here (gsah_block_cigars).  Shortens the last record of a block exactly as maf_block does.
+	void paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink) const;
+	void paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops) const;
 	// OutputAlignment (tools.cpp:222-286)
 	void aln(FILE *fp, const QueryContig &q, ContigResult &r) const;
 	// OutputDotplot (DotPloting.cpp:10-71): gnuplot script `gp_path` + one data file per plotted reference sequence

@@ -98,7 +98,7 @@ int gsah_c_emit(const char *index_prefix, const char *query_fa, const char *maf_
 	return gsah_c_emit_fmt(index_prefix, query_fa, maf_path, vcf_path, reference_label, allow_dup, 1, cb, user, err);
 }
 
-// fmt 1: MAF (OutputMAF), fmt 2: ALN (OutputAlignment) -- the -fmt flag of the CLI (main.cpp:284)
+// fmt 1: MAF (OutputMAF), fmt 2: ALN (OutputAlignment) -- the -fmt flag of the CLI (main.cpp:284); fmt 3: PAF, the CIGARs from the host comparator (gsah_block_cigars)
 int gsah_c_emit_fmt(const char *index_prefix, const char *query_fa, const char *maf_path, const char *vcf_path, const char *reference_label,
                     int allow_dup, int fmt, gsah_result_cb cb, void *user, char *err)
 {
@@ -112,7 +112,7 @@ int gsah_c_emit_fmt(const char *index_prefix, const char *query_fa, const char *
 		ContigResult cr; cr.assign(res);
 		FILE *fp = fopen(maf_path, ci == 0 ? "w" : "a");         // tools.cpp:158-163
 		if (!fp) { if (err) strcpy(err, "cannot open MAF output"); return -3; }
-		if (fmt == 2) em.aln(fp, qs[ci], cr); else em.maf(fp, ci == 0, qs[ci], cr);
+		if (fmt == 3) em.paf(fp, qs[ci], cr, nullptr, nullptr); else if (fmt == 2) em.aln(fp, qs[ci], cr); else em.maf(fp, ci == 0, qs[ci], cr);
 		fclose(fp);
 		em.variants((int)ci, qs[ci], cr);
 	}
@@ -141,6 +141,32 @@ long long gsah_c_variants(const char *index_prefix, const char *seq, int len, co
 	const int64_t n = gsah_variant_records(idx, cr, out, cap, cnt);
 	for (int k = 0; k < 3; k++) counts[k] = cnt[k];
 	return n;
+}
+
+// The CIGAR of every block of one finished contig (gsa_block_cigar / ops, gsa_hip.h), on the host, from the gapped strings and seed records, untrimmed: what
+// gsa_block_cigars gives.  blk[res->n_blocks] is always filled; ops[cap]; returns the number of ops (call with cap = 0 to size `ops`), < 0 on error.
+// seq (may be NULL): the query contig -- seed columns are then classified from its text.  Needs no index.
+long long gsah_c_cigars(const char *seq, int len, const gsa_result *res, gsa_block_cigar *blk, uint32_t *ops, long long cap)
+{
+	(void)len;
+	if (!res || (res->n_blocks > 0 && !blk) || (cap > 0 && !ops)) return -1;
+	ContigResult cr; cr.assign(*res);
+	std::vector<gsa_block_cigar> b; std::vector<uint32_t> o;
+	gsah_block_cigars(seq, cr, b, o);
+	if (!b.empty()) memcpy(blk, b.data(), b.size() * sizeof(gsa_block_cigar));
+	const size_t m = std::min<size_t>(o.size(), cap > 0 ? (size_t)cap : 0);
+	if (m) memcpy(ops, o.data(), m * sizeof(uint32_t));
+	return (long long)o.size();
+}
+
+// gsah_cigar_trim on one block's ops (n = bc->n_cig of them): out[n] receives the ops that stay, *bc the reduced counts; returns their number
+int gsah_c_cigar_trim(const uint32_t *ops, int bdir, long long ext, uint32_t *out, gsa_block_cigar *bc)
+{
+	if (!bc || (bc->n_cig > 0 && (!ops || !out))) return -1;
+	std::vector<uint32_t> o;
+	gsah_cigar_trim(ops, bdir, ext, o, *bc);
+	if (!o.empty()) memcpy(out, o.data(), o.size() * sizeof(uint32_t));
+	return (int)o.size();
 }
 
 // OutputDotplot for one contig: script + data files (no gnuplot run).  Returns 1 if something was written.

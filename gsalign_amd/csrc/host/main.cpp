@@ -33,7 +33,7 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "Usage: %s [-i IndexFile Prefix / -r Reference file] -q QueryFile[Fasta]\n\n", prog);
 	fprintf(stderr, "Options: -t     INT     number of threads [%d] (host side: FASTA / index loading, MAF / VCF formatting; the hot path runs on the GPU)\n", t);
 	fprintf(stderr, "         -o     STR     Set the prefix of the output files [output]\n");
-	fprintf(stderr, "         -fmt   INT     Set the output format 1:maf, 2:aln [%d]\n", fmt);
+	fprintf(stderr, "         -fmt   INT     Set the output format 1:maf, 2:aln, 3:paf [%d]\n", fmt);
 	fprintf(stderr, "         -idy   INT     Set the minimal sequence identity (0-100) of a local alignment [%d]\n", p.min_identity);
 	fprintf(stderr, "         -slen  INT     Set the minimal seed length [%d]\n", p.min_seed_len);
 	fprintf(stderr, "         -alen  INT     Set the minimal alignment length [%d]\n", p.min_aln_len);
@@ -216,7 +216,7 @@ int main(int argc, char *argv[])
 		t_create += now_s() - t;
 	}
 
-	const std::string maf = std::string(out_prefix) + ".maf", aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf";
+	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf";
 	Emitter em; em.idx = &idx; em.allow_dup = allow_dup;
 	long long n_aln = 0, tot_len = 0, tot_match = 0, n_dup = 0;
 	fprintf(stderr, "Step2. Sequence analysis for all query chromosomes\n");
@@ -229,8 +229,9 @@ int main(int argc, char *argv[])
 	struct Sink {
 		std::mutex mu; std::condition_variable cv; std::vector<ContigResult> res; std::vector<char> ready; bool abort = false; double copy_s = 0;
 		std::vector<RawArr<gsa_variant> > var;      // -gpuvar: the contig's variants as gsa_call_variants left them
+		std::vector<RawArr<gsa_block_cigar> > cblk; std::vector<RawArr<uint32_t> > cops;      // -fmt 3: the contig's CIGARs as gsa_block_cigars left them
 	} sink;
-	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size());
+	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size());
 	const bool var_on_gpu = gpuvar && vcf;          // (-no_vcf: nobody reads the variants)
 	// the MAF file: created by the first contig that has alignments ("w" for contig 0, "a" afterwards: tools.cpp:158-163 -- a run whose
 	// first contig aligns nowhere appends to whatever the file held, as the reference does)
@@ -244,7 +245,7 @@ int main(int argc, char *argv[])
 		for (size_t b = 0; b < cr.blocks.size(); b++) { len += cr.blocks[b].aln_len; score += cr.blocks[b].score; if (cr.blocks[b].bdup) n_dup++; }
 		n_aln += (long long)cr.blocks.size(); tot_len += len; tot_match += score;
 		fprintf(stderr, "\t\tProduce %d local alignments (length = %lld), ANI=%.2f%%\n", (int)cr.blocks.size(), len, 100 * (1.0 * score / len));
-		if (fmt == 1) {
+		if (fmt == 1 || fmt == 3) {      // (the PAF file is opened, queued and closed as the MAF file is)
 			const double t = now_s();
 			if (maf_fd < 0 || ci == 0) {
 				if (maf_w) { if (!maf_w->close()) out_failed = true; maf_w.reset(); }
@@ -253,7 +254,11 @@ int main(int argc, char *argv[])
 				if (maf_fd >= 0) maf_w.reset(new OrderedWriter(maf_fd));
 				else if (!out_failed) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", maf.c_str(), strerror(errno)); }
 			}
-			if (maf_w) em.maf_text(ci == 0, qs[ci], cr, [&](OutBuf &&o) { maf_w->push(std::move(o)); }, [&](size_t c) { return maf_w->take(c); });
+			if (maf_w && fmt == 3 && sink.cblk[ci].size() != cr.blocks.size()) {      // (never the host comparator in place of a missing device answer)
+				out_failed = true; fprintf(stderr, "Error! %d blocks, CIGARs of %d\n", (int)cr.blocks.size(), (int)sink.cblk[ci].size());
+			} else if (maf_w && fmt == 3) em.paf_text(qs[ci], cr, sink.cblk[ci].data(), sink.cops[ci].data(), [&](OutBuf &&o) { maf_w->push(std::move(o)); });
+			else if (maf_w) em.maf_text(ci == 0, qs[ci], cr, [&](OutBuf &&o) { maf_w->push(std::move(o)); }, [&](size_t c) { return maf_w->take(c); });
+			sink.cblk[ci].reset(); sink.cops[ci].reset();
 			t_maf_fmt += now_s() - t;
 		}
 		if (fmt == 2) {
@@ -308,17 +313,32 @@ int main(int argc, char *argv[])
 		sk.cv.notify_all();
 		return 0;
 	};
+	// -fmt 3: the worker runs the CIGAR pass (and with -gpuvar the variant pass) in front of the callback (gsa_align_many_ex); their records are copied like the result
+	auto on_result_ex = [](void *user, int32_t ci, const gsa_result *res, const gsa_extras *ex) -> int {
+		Sink &sk = *(Sink *)user;
+		const double t = now_s();
+		sk.res[(size_t)ci].assign(*res);
+		if (ex->var) sk.var[(size_t)ci].assign(ex->var->v, (size_t)ex->var->n);
+		if (ex->cig) { sk.cblk[(size_t)ci].assign(ex->cig->blk, (size_t)ex->cig->n_blocks); sk.cops[(size_t)ci].assign(ex->cig->ops, (size_t)ex->cig->n_ops); }
+		const double dt = now_s() - t;
+		{ std::lock_guard<std::mutex> lk(sk.mu); sk.ready[(size_t)ci] = 1; sk.copy_s += dt; }
+		sk.cv.notify_all();
+		return 0;
+	};
 	if (timing && var_on_gpu) for (gsa_ctx *c : ctxs) (void)gsa_set_profiling(c, 8);      // (the variant passes' device time, for the GSA_VARIANT_PASS line)
 	const double ta = now_s(); t_at_align = ta - T0;
-	const int rc_many = var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
+	const int rc_many = fmt == 3 ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, GSA_WANT_CIGARS | (var_on_gpu ? GSA_WANT_VARIANTS : 0u), on_result_ex, &sink)
+	                  : var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
 	                               : gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
 	t_align = now_s() - ta;
 	// where the contexts' host threads spent that time (gsa_get_wall_sums: [0] query set-up / wait for the upload, [s] stage s) and what growing buffers cost them
 	if (timing && getenv("GSA_DUMP_BUFFERS")) for (gsa_ctx *c : ctxs) (void)gsa_debug_buffers(c, 24);
+	double cigar_ms = 0;      // -fmt 3: wall time the workers spent inside gsa_block_cigars, all contexts
 	double var_dev_ms = 0; long long var_dev_n = 0;      // -gpuvar: device time of the variant passes (hipEvents), all contexts
 	double wall_sum[10] = { 0 }; double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 	for (gsa_ctx *c : ctxs) {
 		double w[10]; int64_t wn = 0; if (gsa_get_wall_sums(c, w, &wn) == GSA_OK) for (int k = 0; k < 9; k++) wall_sum[k] += w[k];
+		{ double cm = 0; int64_t cn = 0; if (gsa_get_cigar_timing(c, &cm, &cn) == GSA_OK) cigar_ms += cm; }
 		double vm = 0; int64_t vn = 0; if (gsa_get_variant_timing(c, &vm, &vn) == GSA_OK) { var_dev_ms += vm; var_dev_n += vn; }
 		double am = 0; int64_t an = 0, ab = 0; if (gsa_get_alloc_stats(c, &am, &an, &ab) == GSA_OK) { alloc_ms += am; alloc_n += an; alloc_bytes += ab; }
 	}
@@ -364,11 +384,11 @@ int main(int argc, char *argv[])
 	if (timing) {
 		long long qbp = 0; for (const QueryContig &q : qs) qbp += (long long)q.seq.size();
 		const double total = now_s() - T0;
-		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, "
+		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, \"cigar_s\": %.3f, "
 		        "\"result_copy_s_sum\": %.3f, \"maf_format_s\": %.3f, \"variants_s\": %.3f, \"output_drain_after_align_s\": %.3f, \"maf_write_s\": %.3f, \"maf_bytes\": %llu, "
 		        "\"vcf_s\": %.3f, \"vcf_write_s\": %.3f, \"vcf_bytes\": %llu, \"destroy_s\": %.3f, \"host_threads\": %d, \"contexts\": %d, \"query_bp\": %lld, \"contigs\": %d, \"gbp_per_s_excl_index_build\": %.4f, "
 		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f}\n",
-		        total, t_build, t_index, t_create, t_query, t_pin, t_align, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
+		        total, t_build, t_index, t_create, t_query, t_pin, t_align, cigar_ms / 1e3, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
 		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9);
 	}

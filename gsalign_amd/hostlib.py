@@ -55,7 +55,7 @@ def result_from_dump(d: dict, keep: list):
 
 
 def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, reference_label: str, per_contig, allow_dup: bool = True, fmt: int = 1) -> None:
-    """per_contig(ci, seq_uint8) -> dump dict of the finished contig (stage 8 layout).  fmt 1 = MAF, 2 = ALN (written to maf_path)."""
+    """per_contig(ci, seq_uint8) -> dump dict of the finished contig (stage 8 layout).  fmt 1 = MAF, 2 = ALN, 3 = PAF with the host comparator's CIGARs (written to maf_path)."""
     keep: list = []
 
     def cb(user, ci, seq, ln, out):
@@ -120,3 +120,44 @@ def variants(index_prefix: str, seq: np.ndarray, result):
         n2 = lib.gsah_c_variants(index_prefix.encode(), C.c_void_p(seq.ctypes.data), int(seq.size), C.byref(result), C.c_void_p(V.ctypes.data), n, cnt)
         assert n2 == n
     return V, (int(cnt[0]), int(cnt[1]), int(cnt[2]))
+
+
+def cigars(index_prefix, seq, result):
+    """gsah_c_cigars: the CIGAR of every block of one finished contig on the host, from the gapped strings and seed records, untrimmed -- what
+    Aligner.block_cigars computes on the GPU.  result: a capi.Result, a dump dict (oracle layout) or a result dict of capi.Aligner.  seq: the query
+    contig (seed columns are classified from its text) or None.  index_prefix is not needed by the walk and may be None (kept for symmetry with variants()).
+    Returns (BLOCK_CIGAR_DT array, uint32 ops)."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    lib = load()
+    lib.gsah_c_cigars.restype = C.c_longlong
+    lib.gsah_c_cigars.argtypes = [C.c_void_p, C.c_int, C.POINTER(capi.Result), C.c_void_p, C.c_void_p, C.c_longlong]
+    sp, sn = None, 0
+    if seq is not None:
+        seq = np.ascontiguousarray(seq, dtype=np.uint8); sp, sn = C.c_void_p(seq.ctypes.data), int(seq.size)
+    blk = np.zeros(int(result.n_blocks), capi.BLOCK_CIGAR_DT)
+    n = lib.gsah_c_cigars(sp, sn, C.byref(result), C.c_void_p(blk.ctypes.data), None, 0)
+    if n < 0:
+        raise RuntimeError(f"gsah_c_cigars -> {n}")
+    ops = np.zeros(int(n), np.uint32)
+    if n:
+        n2 = lib.gsah_c_cigars(sp, sn, C.byref(result), C.c_void_p(blk.ctypes.data), C.c_void_p(ops.ctypes.data), n)
+        assert n2 == n
+    return blk, ops
+
+
+def cigar_trim(ops, bdir: bool, ext: int, counts):
+    """gsah_c_cigar_trim: iExtension's trim on ONE block's ops (output order) -- the last `ext` columns in walk order go.  counts = (n_eq, n_x, n_ins, n_del).
+    Returns (ops that stay, reduced counts)."""
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    bc = np.zeros(1, capi.BLOCK_CIGAR_DT)
+    bc["n_cig"] = ops.size; bc["n_eq"], bc["n_x"], bc["n_ins"], bc["n_del"] = counts
+    out = np.zeros(max(ops.size, 1), np.uint32)
+    lib = load()
+    lib.gsah_c_cigar_trim.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]
+    n = lib.gsah_c_cigar_trim(C.c_void_p(ops.ctypes.data), 1 if bdir else 0, int(ext), C.c_void_p(out.ctypes.data), C.c_void_p(bc.ctypes.data))
+    if n < 0:
+        raise RuntimeError(f"gsah_c_cigar_trim -> {n}")
+    assert n == int(bc["n_cig"][0])
+    return out[:n].copy(), (int(bc["n_eq"][0]), int(bc["n_x"][0]), int(bc["n_ins"][0]), int(bc["n_del"][0]))

@@ -313,6 +313,62 @@ typedef int (*gsa_result_var_fn)(void *user, int32_t contig, const gsa_result *r
 int gsa_align_many_variants(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
                             uint32_t flags, gsa_result_var_fn on_result, void *user);
 
+/* ---- per-block CIGARs (PAF's cg:Z:) -------------------------------------------
+ * The CIGAR of a block is the run-length encoding of the columns of the two `s` lines OutputMAF prints for it (tools.cpp:165-216), in the
+ * order they are printed: for a reverse-strand block after SelfComplementarySeq, i.e. in reference-forward order.  The reference row is
+ * PAF's target, the query row PAF's query.  Column classes (BAM op codes):
+ *   I (1)  the reference row holds '-'                D (2)  the query row holds '-'
+ *   = (7)  both rows hold a base and the two are the same one of A/C/G/T, whatever their case
+ *   X (8)  both rows hold a base, in every other case -- N and IUPAC codes on either side included
+ * A seed record is `len` columns of '=' (an exact match over A/C/G/T; OutputMAF prints the query text on both lines for it).  Adjacent runs
+ * of one class merge ACROSS record boundaries: two seeds with nothing between them are one '=' run.  An op is len << 4 | code (len < 2^28).
+ * This is NOT the reference's score rule: CountIdenticalPairs counts N against N (and N against '-') as identical and
+ * CheckFragPairMismatch forgives every ambiguous query base, so the '=' columns of a block may differ from gsa_block::score where
+ * ambiguous bases sit in gaps.
+ * The walk runs on the device, over what the alignment left there (records, op strings, the two sequences).  It describes the result as
+ * gsa_result holds it, UNTRIMMED: the iExtension trim of a block that runs past the end of its reference sequence (tools.cpp:192-202)
+ * is the emitter's business, as it is for MAF text. */
+typedef struct { int64_t cig_off; int32_t n_cig; int32_t n_eq, n_x, n_ins, n_del; int32_t _pad; } gsa_block_cigar;  /* columns per class; one entry per block of gsa_result::blocks, same order */
+typedef struct { int32_t n_blocks; int64_t n_ops; const gsa_block_cigar *blk; const uint32_t *ops; } gsa_cigars;
+#define GSA_CIGAR_INS 1u
+#define GSA_CIGAR_DEL 2u
+#define GSA_CIGAR_EQ  7u
+#define GSA_CIGAR_X   8u
+/* n ops as PAF's cg string (decimal length, then the op letter) into buf[cap], NUL-terminated.  Returns the length of the whole string
+ * without the NUL -- at most 10 bytes per op; when that is >= cap the string was cut and buf holds its first cap - 1 bytes. */
+static inline size_t gsa_cigar_string(const uint32_t *ops, int64_t n, char *buf, size_t cap)
+{
+	static const char letter[16] = { 'M', 'I', 'D', 'N', 'S', 'H', 'P', '=', 'X', '?', '?', '?', '?', '?', '?', '?' };
+	size_t at = 0;
+	for (int64_t i = 0; i < n; i++) {
+		char tmp[12]; int m = 0; uint32_t len = ops[i] >> 4;
+		do { tmp[m++] = (char)('0' + len % 10); len /= 10; } while (len);
+		while (m) { --m; if (at + 1 < cap) buf[at] = tmp[m]; at++; }
+		if (at + 1 < cap) buf[at] = letter[ops[i] & 15u];
+		at++;
+	}
+	if (cap) buf[at < cap ? at : cap - 1] = '\0';
+	return at;
+}
+/* The CIGARs of ALL blocks of the stage-8 result the context holds, duplicates included (the caller filters).  Validity and call order are
+ * those of gsa_call_variants: after gsa_align_contig[_device], gsa_finish_contig, gsa_run_to(8) and gsa_align_bundle, until the next call
+ * that changes the context (GSA_ERR_STATE otherwise, and when a prefetch has overwritten the contig's device copy).  k = 0 for a single
+ * contig, the contig's index for a bundle; k out of range: GSA_ERR_ARG.  No blocks: n_blocks = 0.  blk[b].cig_off indexes `ops`.
+ * Memory is owned by the context and valid until the next call on it. */
+int gsa_block_cigars(gsa_ctx *ctx, int32_t k, gsa_cigars *out);
+/* measurement: host wall time the calling threads spent inside gsa_block_cigars on this context since it was created (launches, the two waits,
+ * the copies home), and the number of calls.  Always on (two clock reads per call). */
+int gsa_get_cigar_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+/* gsa_align_many with optional passes run by the worker in front of the callback -- before the prefetch after next can touch the contig's
+ * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars).  *ex and what it points to are valid during
+ * the callback only, like *res. */
+#define GSA_WANT_VARIANTS 1u
+#define GSA_WANT_CIGARS   2u
+typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;   /* NULL where not asked for */
+typedef int (*gsa_result_ex_fn)(void *user, int32_t contig, const gsa_result *res, const gsa_extras *ex);
+int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
+                      uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user);
+
 /* ---- one long contig on several GPUs ---------------------------------------
  * IdentifyLocalMEM hands 10 000-bp chunks of the contig to whichever thread is free (GSAlign.cpp:61-94) and seeds never
  * cross a chunk edge, so the seed search of one contig splits by chunk range: every GPU runs gsa_seed_chunks on its range
