@@ -23,6 +23,7 @@ EXPORTS = [
     "gsa_prefetch_contig", "gsa_prefetch_bundle", "gsa_cancel_prefetch", "gsa_get_wall_sums", "gsa_get_alloc_stats", "gsa_debug_buffers", "gsa_set_option", "gsa_host_register", "gsa_host_unregister",
     "gsa_call_variants", "gsa_align_many_variants", "gsa_get_variant_timing",
     "gsa_block_cigars", "gsa_get_cigar_timing", "gsa_align_many_ex",
+    "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
 ]
 
 
@@ -208,6 +209,47 @@ def load_library() -> C.CDLL:
         if fn.argtypes is None:
             fn.argtypes = None
     return lib
+
+
+def index_sizes(G: int):
+    """gsa_index_sizes: (bwt_words, n_sa) of the index of a reference of G forward bases -- arithmetic, no device."""
+    lib = load_library()
+    lib.gsa_index_sizes.argtypes = [C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    bw, ns = C.c_uint64(), C.c_uint64()
+    rc = lib.gsa_index_sizes(int(G), C.byref(bw), C.byref(ns))
+    if rc != 0:
+        raise GsaError(f"gsa_index_sizes -> {rc}: {lib.gsa_last_error(None).decode()}")
+    return int(bw.value), int(ns.value)
+
+
+BUILD_INDEX_ARGTYPES = [C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+
+
+def build_index_arrays(pac, G: int, device: int = 0):
+    """gsa_build_index: the .pac bytes of G forward bases -> (hdr uint64[5] = [primary, L2[1..4]], bwt uint32[], sa uint64[]), the arrays of
+    indexio.BwaIndex, suffix-sorted on the GPU.  Raises GsaError (.code = the library's error code) when the library refuses."""
+    lib = load_library()
+    lib.gsa_build_index.argtypes = BUILD_INDEX_ARGTYPES
+    pac = np.ascontiguousarray(pac, dtype=np.uint8)
+    if G <= 0 or pac.size < (G + 3) // 4:
+        raise ValueError("pac holds fewer than G bases")
+    bw, ns = index_sizes(G)
+    bwt = np.zeros(bw, np.uint32); sa = np.zeros(ns, np.uint64)
+    primary = C.c_uint64(); L2 = (C.c_uint64 * 5)()
+    rc = lib.gsa_build_index(int(device), C.c_void_p(pac.ctypes.data), int(G), C.byref(primary), L2, C.c_void_p(bwt.ctypes.data), C.c_void_p(sa.ctypes.data))
+    if rc != 0:
+        e = GsaError(f"gsa_build_index -> {rc}: {lib.gsa_last_error(None).decode()}"); e.code = rc
+        raise e
+    return np.array([primary.value, L2[1], L2[2], L2[3], L2[4]], dtype=np.uint64), bwt, sa
+
+
+def index_build_stats():
+    """gsa_get_index_build_stats: (device ms, doubling rounds) of the calling thread's last gsa_build_index."""
+    lib = load_library()
+    ms, rounds = C.c_double(), C.c_int32()
+    lib.gsa_get_index_build_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    lib.gsa_get_index_build_stats(C.byref(ms), C.byref(rounds))
+    return float(ms.value), int(rounds.value)
 
 
 def bind_host_thread(device: int = 0) -> None:

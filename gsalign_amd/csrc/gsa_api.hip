@@ -152,6 +152,22 @@ static hipError_t h2d_big(void *dst, const void *src, size_t bytes)
 	return hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
 }
 
+// A context with no index (gsa_build_index runs before one exists): the device, one stream, the mailbox the fused passes draw their tickets from; the sort's scratch
+// (tmp) and the look-back status words grow on first use.  No uploader thread, no events, no auxiliary streams.  gsa_destroy frees it like any other context.
+int ctx_create_bare(int device, gsa_ctx **out)
+{
+	gsa_ctx *c = new gsa_ctx();
+	c->device = device;
+	memset(c->kernel_ms, 0, sizeof(c->kernel_ms)); memset(c->counters, 0, sizeof(c->counters));
+	hipError_t e = hipSetDevice(device);
+	if (e == hipSuccess) e = hipStreamCreate(&c->stream);
+	if (e == hipSuccess) e = hipMalloc(&c->d_mail.p, MAIL_N * sizeof(i32));
+	if (e == hipSuccess) { c->d_mail.cap = MAIL_N * sizeof(i32); e = hipMemset(c->d_mail.p, 0, MAIL_N * sizeof(i32)); }
+	if (e != hipSuccess) { (void)hipGetLastError(); gsa_fail(nullptr, GSA_ERR_HIP, std::string("gsa_build_index: device set-up: ") + hipGetErrorString(e)); gsa_destroy(c); return GSA_ERR_HIP; }
+	*out = c;
+	return GSA_OK;
+}
+
 // Device memory set aside for the two largest index tables before the index files are even read (gsa_reserve_index): their sizes follow from the text length
 // alone.  One slot per device; gsa_create on that device adopts what fits (dev_take_reserved), gsa_release_reserved frees what was not used.
 struct ReservedBuf { void *p = nullptr; size_t bytes = 0; };
@@ -1037,6 +1053,41 @@ int gsa_get_cigar_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls)
 {
 	if (!c || !ms_sum || !n_calls) return GSA_ERR_ARG;
 	*ms_sum = c->cig_ms_sum; *n_calls = (int64_t)c->cig_calls;
+	return GSA_OK;
+}
+
+// ---- the index builder (k_index.hip) ----
+int gsa_index_sizes(int64_t G, uint64_t *bwt_words, uint64_t *n_sa)
+{
+	if (G <= 0 || !bwt_words || !n_sa) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_index_sizes: bad argument");
+	const uint64_t S = 2 * (uint64_t)G;
+	*bwt_words = (S + 15) / 16 + ((S + 127) / 128 + 1) * 8;
+	*n_sa = (S + 32) / 32;
+	return GSA_OK;
+}
+
+static thread_local double g_ix_ms = 0; static thread_local int32_t g_ix_rounds = 0;
+int gsa_build_index(int device, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
+{
+	if (!pac || !primary || !L2 || !bwt || !sa || G <= 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_build_index: bad argument");
+	// 32-bit suffix indices, ranks and scatter positions: the text with its '$' has at most 2^31 - 2 suffixes (the bound of the host builder's 32-bit instance)
+	if (2 * G + 1 > (1ll << 31) - 2) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_build_index: the reference is longer than 1 073 741 822 bases (the device builder sorts 32-bit suffix indices)");
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return gsa_fail(nullptr, GSA_ERR_HIP, "no HIP device available (libgsa_hip.so has no CPU path)"); }
+	if (device < 0 || device >= ndev) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_build_index: bad device ordinal");
+	gsa_ctx *c = nullptr;
+	if (int rc = ctx_create_bare(device, &c)) return rc;
+	double ms = 0; int32_t rounds = 0;
+	const int rc = build_index_device(c, pac, G, primary, L2, bwt, sa, &ms, &rounds);
+	if (rc != GSA_OK) g_create_error = c->err; else { g_ix_ms = ms; g_ix_rounds = rounds; }
+	gsa_destroy(c);
+	return rc;
+}
+
+int gsa_get_index_build_stats(double *ms, int32_t *rounds)
+{
+	if (!ms || !rounds) return GSA_ERR_ARG;
+	*ms = g_ix_ms; *rounds = g_ix_rounds;
 	return GSA_OK;
 }
 

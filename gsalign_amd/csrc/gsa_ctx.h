@@ -304,6 +304,8 @@ int run_gapsim_jobs(gsa_ctx *c, i32 n, const i32 *d_n, const i32 *d_q1, const i3
 void dp_count_cells(gsa_ctx *c, i32 n_ub, const i32 *len1, const i32 *len2, hipStream_t stream);   // k_dp.hip (profiling)
 int call_variants(gsa_ctx *c, i32 k, gsa_variants *out);   // k_variants.hip  (VariantIdentification over the stage-8 result of contig k)
 int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out);      // k_cigar.hip  (the CIGAR of every block of the stage-8 result of contig k)
+int ctx_create_bare(int device, gsa_ctx **out);            // gsa_api.hip  (a context with NO index: device, stream, mailbox and scratch -- what the sort and the fused passes need; gsa_destroy frees it)
+int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds);   // k_index.hip  (suffix sort + BWT / Occ / SA samples of forward + reverse complement)
 struct LgJob { i32 job, m, n; };
 int launch_stripes(gsa_ctx *c, hipStream_t ss, std::vector<LgJob> &large, const uint8_t *pool1, const i64 *off1, const uint8_t *pool2, const i64 *off2,
                    uint8_t *ops, const i64 *ops_off, i32 *ops_len, uint8_t *rev, int err_slot);   // k_dp.hip

@@ -54,6 +54,12 @@ bool gsah_load_index_files(const std::string &prefix, HostIndex &idx, std::strin
 bool gsah_unpack_ref(HostIndex &idx, std::string &err, bool keep_pac = false);
 // bwa_idx_build (reference src/BWT_Index/bwtindex.c:77-149): byte-identical .bwt .sa .pac .ann .amb
 bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::string &err);
+// The same with the BWT/SA half supplied by the caller: fn(user, pac, G, &primary, L2, bwt, sa) gets the .pac bytes of the G forward bases and fills primary, L2[0..4]
+// (L2[0] = 0, L2[4] = 2G), the interleaved bwt words and the sampled SA (sa[0] = -1) -- the arrays of gsa_index_view, sized as gsa_index_sizes says -- and returns 0;
+// anything else fails the build before .bwt / .sa are written.  fn = nullptr: the host's own suffix sorters, i.e. gsah_build_index.  gsa_build_index (gsa_hip.h) has
+// this shape behind a device ordinal; this library links no HIP.
+typedef int (*gsah_bwt_fn)(void *user, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa);
+bool gsah_build_index_with(const std::string &fasta, const std::string &prefix, std::string &err, gsah_bwt_fn fn, void *user);
 // LoadQueryFile / TrimChromosomeName / CheckQuerySeq (reference src/main.cpp:35-114)
 bool gsah_load_query(const std::string &path, std::vector<QueryContig> &out, std::string &err);
 

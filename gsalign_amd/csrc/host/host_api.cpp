@@ -85,6 +85,15 @@ int gsah_c_build_index(const char *fasta, const char *prefix, char *err)
 	return -1;
 }
 
+// the builder with the BWT/SA half from a callback (gsah_bwt_fn; NULL: the host path)
+int gsah_c_build_index_with(const char *fasta, const char *prefix, gsah_bwt_fn fn, void *user, char *err)
+{
+	std::string e;
+	if (gsah_build_index_with(fasta, prefix, e, fn, user)) return 0;
+	if (err) { strncpy(err, e.c_str(), 255); err[255] = 0; }
+	return -1;
+}
+
 // Emit MAF + VCF for a whole query FASTA given, per contig, a finished gsa_result.
 // get_result(user, contig_index, seq, len, &result) is called once per contig, in order.
 typedef int (*gsah_result_cb)(void *user, int contig, const char *seq, int len, gsa_result *out);

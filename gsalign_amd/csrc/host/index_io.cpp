@@ -379,7 +379,11 @@ bool gsah_load_index(const std::string &prefix, HostIndex &idx, std::string &err
 }
 
 
-bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::string &err)
+bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::string &err) { return gsah_build_index_with(fasta, prefix, err, nullptr, nullptr); }
+
+// fn = nullptr: the host's suffix sorters; else the caller supplies the BWT/SA half from the .pac bytes (gsah_bwt_fn, gsa_host.h): everything around it -- FASTA
+// parsing, N -> lrand48, .pac / .ann / .amb, the .bwt / .sa writers -- is the same code either way
+bool gsah_build_index_with(const std::string &fasta, const std::string &prefix, std::string &err, gsah_bwt_fn fn, void *user)
 {
 	std::vector<FaRec> recs;
 	if (!read_fasta_gz(fasta, recs) || recs.empty()) { err = "cannot read FASTA " + fasta; return false; }
@@ -406,8 +410,8 @@ bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::
 	const int64_t G = (int64_t)codes.size();
 	if (G <= 0) { err = "empty reference"; return false; }
 	// .pac (forward only; bntseq.c:192-201)
+	std::vector<uint8_t> pac((size_t)((G >> 2) + ((G & 3) ? 1 : 0)), 0);
 	{
-		std::vector<uint8_t> pac((size_t)((G >> 2) + ((G & 3) ? 1 : 0)), 0);
 		for (int64_t l = 0; l < G; l++) pac[l >> 2] |= codes[l] << ((~l & 3) << 1);
 		FILE *fp = fopen((prefix + ".pac").c_str(), "wb"); if (!fp) { err = "cannot write " + prefix + ".pac"; return false; }
 		fput(fp, pac.data(), pac.size());
@@ -431,18 +435,26 @@ bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::
 		for (size_t h = 0; h < holes.size(); h++) fprintf(fp, "%lld %d %c\n", (long long)holes[h].off, holes[h].len, holes[h].amb);
 		fclose(fp);
 	}
-	// ---- text = forward + reverse complement, then '$' ----
 	const int64_t S = 2 * G;
+	uint64_t primary = 0, L2[5] = {0, 0, 0, 0, 0};
+	const uint64_t n_sa = (uint64_t)(S + 32) / 32, n_occ = (uint64_t)(S + 127) / 128 + 1;
+	std::vector<uint64_t> sa; std::vector<uint32_t> bwt;
+	if (fn) {
+		{ std::vector<uint8_t>().swap(codes); }
+		sa.assign(n_sa, 0); bwt.assign((size_t)((S + 15) / 16) + n_occ * 8, 0);
+		const int rc = fn(user, pac.data(), G, &primary, L2, bwt.data(), sa.data());
+		if (rc != 0) { err = "the BWT/SA callback failed (" + std::to_string(rc) + ")"; return false; }
+	} else {
+	{ std::vector<uint8_t>().swap(pac); }
+	// ---- text = forward + reverse complement, then '$' ----
 	std::vector<uint8_t> T((size_t)S + 1);
 	const int nt = index_threads();
 	parallel_ranges(G, nt, [&](int, int64_t a, int64_t b) { for (int64_t i = a; i < b; i++) { T[(size_t)i] = codes[(size_t)i] + 1; T[(size_t)(S - 1 - i)] = (3 - codes[(size_t)i]) + 1; } });
 	T[S] = 0;
 	{ std::vector<uint8_t>().swap(codes); }
 	// ---- suffix array -> BWT without '$', primary, L2, SA samples (bwt_cal_sa, bwt.c:101-123) ----
-	uint64_t primary = 0, L2[5] = {0, 0, 0, 0, 0};
 	std::vector<uint32_t> packed((size_t)((S + 15) / 16), 0);
-	const uint64_t n_sa = (uint64_t)(S + 32) / 32;
-	std::vector<uint64_t> sa(n_sa);
+	sa.assign(n_sa, 0);
 	// (GSA_INDEX_64BIT=1 forces the wide suffix sorter on any input: how the tests reach it with a small fixture)
 	const char *f64 = getenv("GSA_INDEX_64BIT");
 	if (S + 1 < (1ll << 31) - 1 && !(f64 && *f64 && *f64 != '0')) derive_bwt_sa<int32_t>(T, S, packed, primary, sa);
@@ -455,8 +467,7 @@ bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::
 	for (int c = 1; c < 5; c++) L2[c] += L2[c - 1];
 	{ std::vector<uint8_t>().swap(T); }
 	// ---- interleave Occ every 128 (bwt_bwtupdate_core, bwtindex.c:53-75) ----
-	const uint64_t n_occ = (uint64_t)(S + 127) / 128 + 1;
-	std::vector<uint32_t> bwt(packed.size() + n_occ * 8, 0);
+	bwt.assign(packed.size() + n_occ * 8, 0);
 	{
 		// block g (128 symbols = 8 packed words) goes to words [16 g, 16 g + 16): 8 words of running counts, then its symbols;
 		// the counts in front of a thread's first block come from a pass over the per-thread totals
@@ -482,6 +493,7 @@ bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::
 		const size_t k_end = (size_t)n_blk * 8 + packed.size();
 		memcpy(&bwt[k_end], start[(size_t)nt_eff].data(), 32);
 		if (k_end + 8 != bwt.size()) { err = "internal: inconsistent bwt size"; return false; }
+	}
 	}
 	{
 		FILE *fp = fopen((prefix + ".bwt").c_str(), "wb"); if (!fp) { err = "cannot write .bwt"; return false; }

@@ -4,7 +4,8 @@
 // hot path handed to libgsa_hip.so (gsa_align_contig) instead of GenomeComparison's
 // pthread stages.  Extra flags: -gpu LIST (device ordinals, comma separated: the query contigs shard over them with the
 // index replicated), -ctx N (contexts per GPU: gsa_clone, contigs overlap on one device) and -timing
-// (one JSON line on stderr: where the wall time of the run went).
+// (one JSON line on stderr: where the wall time of the run went).  -gpuindex: an index that has to be built (`index`, or -r) gets its BWT/SA half from the
+// GPU (gsa_build_index) instead of the host's suffix sorters; the files are the same bytes.
 // The contigs go through gsa_align_many (the per-contig loop of GSAlign.cpp:483-548).  Round 5: a GPU worker thread only COPIES a finished
 // contig out of the library's memory; ONE formatter thread takes the contigs in contig order (OutputMAF appends per contig, VarVec grows in
 // contig order: GSAlign.cpp:543-546) and formats each with the host pool's threads (par.h: the text lines of a block, the variants of a
@@ -48,7 +49,30 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -gpu   LIST    GPU ordinals, comma separated [0]\n");
 	fprintf(stderr, "         -ctx   INT     contexts per GPU working on different query sequences [2]\n");
 	fprintf(stderr, "         -timing        print where the wall time went (one JSON line on stderr)\n");
-	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n\n");
+	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
+	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index), references up to 1.07 Gbp [false]\n\n", prog);
+}
+
+// the index of `fasta` under `prefix`; on_gpu: the BWT/SA half from gsa_build_index on `device` (a reference over its bound: one line, then the host builder).
+// Returns 0, 1 (the builder's error: printed) or 2 (the GPU's error: printed).
+struct GpuIndexCall { int device, rc; };
+static int gpu_bwt_fn(void *user, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
+{
+	GpuIndexCall *g = (GpuIndexCall *)user;
+	return g->rc = gsa_build_index(g->device, pac, G, primary, L2, bwt, sa);
+}
+static int build_index(const char *fasta, const std::string &prefix, bool on_gpu, int device)
+{
+	std::string e;
+	if (on_gpu) {
+		GpuIndexCall g = { device, GSA_OK };
+		if (gsah_build_index_with(fasta, prefix, e, gpu_bwt_fn, &g)) return 0;
+		if (g.rc == GSA_OK) { fprintf(stderr, "%s\n", e.c_str()); return 1; }
+		if (g.rc != GSA_ERR_LIMIT) { fprintf(stderr, "GPU index build failed (device %d): %s\n", device, gsa_last_error(NULL)); return 2; }
+		fprintf(stderr, "-gpuindex: %s; building the index on the host\n", gsa_last_error(NULL));
+	}
+	if (!gsah_build_index(fasta, prefix, e)) { fprintf(stderr, "%s\n", e.c_str()); return 1; }
+	return 0;
 }
 
 static bool check_prefix(const char *p)                     // CheckOutputPrefix (main.cpp:116-138)
@@ -78,13 +102,15 @@ int main(int argc, char *argv[])
 	//  kernel and faulting it in again for the next contig)
 	mallopt(M_MMAP_THRESHOLD, 1 << 30); mallopt(M_TRIM_THRESHOLD, 1 << 30); mallopt(M_TOP_PAD, 256 << 20);
 	gsa_params prm; gsa_default_params(&prm);
-	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, timing = getenv("GSA_TIMING") != NULL;
+	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, gpuindex = false, timing = getenv("GSA_TIMING") != NULL;
 	std::vector<int> gpus;
 	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL;
 	if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(argv[0], threads, prm, fmt); return 0; }
 	if (strcmp(argv[1], "index") == 0) {
-		if (argc == 4) { std::string e; if (!gsah_build_index(argv[2], argv[3], e)) { fprintf(stderr, "%s\n", e.c_str()); return 1; } }
-		else fprintf(stderr, "usage: %s index ref.fa prefix\n", argv[0]);
+		bool on_gpu = false; int device = 0, a = 2;
+		for (; a < argc && argv[a][0] == '-'; a++) { if (strcmp(argv[a], "-gpuindex") == 0) on_gpu = true; else if (strcmp(argv[a], "-gpu") == 0 && a + 1 < argc) device = atoi(argv[++a]); else break; }
+		if (argc - a == 2) return build_index(argv[a], argv[a + 1], on_gpu, device);
+		fprintf(stderr, "usage: %s index [-gpuindex] [-gpu N] ref.fa prefix\n", argv[0]);
 		return 0;
 	}
 	for (int i = 1; i < argc; i++) {
@@ -108,6 +134,7 @@ int main(int argc, char *argv[])
 		else if (a == "-ctx" && i + 1 < argc) { n_ctx_per_gpu = atoi(argv[++i]); if (n_ctx_per_gpu < 1) n_ctx_per_gpu = 1; }
 		else if (a == "-timing") timing = true;
 		else if (a == "-gpuvar") gpuvar = true;
+		else if (a == "-gpuindex") gpuindex = true;
 		else if (a == "-dp") dotplot = true;
 		else if (a == "-gp" && i + 1 < argc) gnuplot_arg = argv[++i];      // main.cpp:285: the path of gnuplot, used as given
 		else if (a == "-d" || a == "-debug") { /* debug printers: not reproduced */ }
@@ -132,7 +159,7 @@ int main(int argc, char *argv[])
 	else if (ref_fa != NULL && first_char_is_header(ref_fa)) {
 		prefix = ref_fa; size_t p = prefix.find_last_of('.'); if (p != std::string::npos && p > 0) prefix.resize(p);
 		const double t = now_s();
-		if (!gsah_build_index(ref_fa, prefix, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+		if (const int rcb = build_index(ref_fa, prefix, gpuindex, gpus.empty() ? 0 : gpus[0])) return rcb;
 		t_build = now_s() - t;
 	} else { q_loader.join(); if (!q_ok) fprintf(stderr, "Please check the query file: %s\n", query_fa); else fprintf(stderr, "Please specify a valid reference genome\n"); return 0; }
 	// while the files are read: the HIP runtime comes up and the device memory of the two largest tables (their sizes follow from the text length in the .bwt header)

@@ -34,6 +34,49 @@ def build_index(fasta: str, prefix: str) -> None:
         raise RuntimeError(err.value.decode())
 
 
+BWT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64))
+
+
+def build_index_with(fasta: str, prefix: str, fn) -> None:
+    """gsah_build_index_with: the index builder with its BWT/SA half supplied by `fn`.  fn(pac uint8[ceil(G/4)], G) returns
+    (hdr uint64[5] = [primary, L2[1..4]], bwt uint32[], sa uint64[]) -- the arrays of indexio.BwaIndex, sized as capi.index_sizes(G) says;
+    an exception (or arrays of another size) fails the build before .bwt / .sa are written.  fn = None: the host builder (build_index)."""
+    failure: list = []
+
+    def cb(user, pac, G, primary, L2, bwt, sa):
+        try:
+            G = int(G)
+            hdr, b, s = fn(np.ctypeslib.as_array(pac, shape=((G + 3) // 4,)).copy(), G)
+            hdr = np.asarray(hdr, dtype=np.uint64); b = np.ascontiguousarray(b, dtype=np.uint32); s = np.ascontiguousarray(s, dtype=np.uint64)
+            S = 2 * G
+            if hdr.size != 5 or b.size != (S + 15) // 16 + ((S + 127) // 128 + 1) * 8 or s.size != (S + 32) // 32:
+                raise ValueError("the callback's arrays have the wrong size")
+            primary[0] = int(hdr[0]); L2[0] = 0
+            for k in range(1, 5):
+                L2[k] = int(hdr[k])
+            C.memmove(bwt, b.ctypes.data, b.nbytes); C.memmove(sa, s.ctypes.data, s.nbytes)
+            return 0
+        except Exception as e:      # (an exception must not unwind through the C frames)
+            failure.append(e)
+            return 1
+
+    err = C.create_string_buffer(256)
+    lib = load()
+    lib.gsah_c_build_index_with.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_char_p]
+    keep = BWT_FN(cb) if fn is not None else None
+    rc = lib.gsah_c_build_index_with(fasta.encode(), prefix.encode(), C.cast(keep, C.c_void_p) if keep is not None else None, None, err)
+    if rc != 0:
+        e = RuntimeError(err.value.decode() + (f": {failure[0]!r}" if failure else ""))
+        if failure:
+            e.__cause__ = failure[0]
+        raise e
+
+
+def build_index_gpu(fasta: str, prefix: str, device: int = 0) -> None:
+    """The index files of `fasta` with the BWT/SA half built on the GPU (capi.build_index_arrays): the same five files as build_index."""
+    build_index_with(fasta, prefix, lambda pac, G: capi.build_index_arrays(pac, G, device))
+
+
 def result_from_dump(d: dict, keep: list):
     """dict in the oracle/capi 'blocks_as_dump' layout -> a populated capi.Result (arrays appended to `keep`)."""
     nb = d["b_score"].size; nf = d["f_qpos"].size

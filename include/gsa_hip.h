@@ -369,6 +369,20 @@ typedef int (*gsa_result_ex_fn)(void *user, int32_t contig, const gsa_result *re
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
                       uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user);
 
+/* ---- the index itself ---------------------------------------------------------
+ * sizes of the two arrays gsa_build_index fills, for a forward length G: pure arithmetic, no device */
+int gsa_index_sizes(int64_t G, uint64_t *bwt_words, uint64_t *n_sa);
+/* Replaces bwa_idx_build's BWT/SA half (BWT_Index/bwtindex.c:77-149, bwt.c:101-123): pac = the .pac bytes of G bases (bntseq.c:192-201;
+ * only the first ceil(G/4) are read) -> primary, L2[5], the interleaved bwt words and the sampled SA exactly as the .bwt / .sa files and
+ * gsa_index_view hold them.  Host pointers out.  No context needed; thread-safe per device.
+ * The text the suffixes of which are sorted is forward + reverse complement + '$' (2G + 1 suffixes); the device sorts them by prefix doubling on 32-bit
+ * suffix indices, so G <= 1 073 741 822 (GSA_ERR_LIMIT above that, before anything is allocated; ~52 bytes of device memory per suffix, GSA_ERR_NOMEM when
+ * they are not there).  Errors in this order: NULL pointers or G <= 0 GSA_ERR_ARG, G over the bound GSA_ERR_LIMIT, no device GSA_ERR_HIP;
+ * gsa_last_error(NULL) has the text. */
+int gsa_build_index(int device, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa);
+/* measurement: device ms and doubling rounds of the last gsa_build_index of the calling thread */
+int gsa_get_index_build_stats(double *ms, int32_t *rounds);
+
 /* ---- one long contig on several GPUs ---------------------------------------
  * IdentifyLocalMEM hands 10 000-bp chunks of the contig to whichever thread is free (GSAlign.cpp:61-94) and seeds never
  * cross a chunk edge, so the seed search of one contig splits by chunk range: every GPU runs gsa_seed_chunks on its range
