@@ -76,6 +76,7 @@ struct Options {
 	int64_t bundle_contig = 16000000;  // ... contigs up to this length travel in bundles (0: never)
 	int64_t bundle_cap = 64000000;     // ... of about this many bases at most
 	int dp_lane = 512;                 // alignments of at most this many cells go one per lane (k_dp_lane); 0: round 2's tiny / small split
+	int seed_lhop = 0;                 // (test hook) entries of the seed kernel's long-hop table a chunk may use: a power of two below LHOP_N; 0 = all of them
 	int seed_mode = 1;                 // 0 sweep: every chunk through k_dense_sweep; 1: the speculative kernel + dense kernels for what it gives up on; 2: round 2's k_dense_search in place of the sweep
 	int pd_bitmap = 1;                 // 0: groups by the PosDiff sort although MaxIndelSize <= 31 would allow the bitmap scan
 	int sweep_shape = -1;              // k_dense_sweep's launch shape: -1 by the number of dense chunks, 0 = four chunks per two-wave workgroup / 160-start segments, 1 = one chunk per four-wave workgroup / 40-start segments

@@ -41,20 +41,21 @@ enum { M_DONE = 0, M_FM = 1, M_TEXT = 2, M_KMER = 3, M_LOC = 4, M_ADV = 5, M_KLO
 
 // ---- 2-bit packed sequences: base p sits at bits (2*(p&15)) of word p>>4 (LSB first) ----
 __device__ __forceinline__ int q_code(const u32 *qp, int p) { return (qp[p >> 4] >> ((p & 15) << 1)) & 3; }
-__device__ __forceinline__ int q_isn(const u32 *qn, int p) { return (qn[p >> 5] >> (p & 31)) & 1; }
+// (on = false: the chunk has no ambiguous base and keeps no N bitmap -- see SeedLds; the answer is 0 without a read)
+__device__ __forceinline__ int q_isn(const u32 *qn, int p, bool on = true) { return on ? (qn[p >> 5] >> (p & 31)) & 1 : 0; }
 __device__ __forceinline__ u64 funnel64(u32 w0, u32 w1, u32 w2, int sh)      // 64 bits starting sh (even, < 32) bits into w0
 {
 	const u64 lo = (u64)w0 | ((u64)w1 << 32);
 	return sh ? (lo >> sh) | ((u64)w2 << (64 - sh)) : lo;
 }
 __device__ __forceinline__ u64 q_bits64(const u32 *qp, int p) { const int w = p >> 4; return funnel64(qp[w], qp[w + 1], qp[w + 2], (p & 15) << 1); }
-__device__ __forceinline__ u32 q_nbits32(const u32 *qn, int p) { const int w = p >> 5; return (u32)((((u64)qn[w + 1] << 32) | qn[w]) >> (p & 31)); }
+__device__ __forceinline__ u32 q_nbits32(const u32 *qn, int p, bool on = true) { if (!on) return 0u; const int w = p >> 5; return (u32)((((u64)qn[w + 1] << 32) | qn[w]) >> (p & 31)); }
 
 // Unique interval (x2 == 1): how many of the next (at most 32) query bases continue the only
 // occurrence, i.e. pos+t < clen, tp+t < tend, query base t unambiguous and equal to text base t.
 // Equivalent to that many successful bwt_2occ4 steps, which leave x0 and x2 = 1 unchanged
 // (see DESIGN.md section 4).  r0..r2 = packed reference words starting at word tp>>4.
-__device__ __forceinline__ int text_match32(u32 r0, u32 r1, u32 r2, i64 tp, i64 tend, const u32 *qp, const u32 *qn, int pos, int clen)
+__device__ __forceinline__ int text_match32(u32 r0, u32 r1, u32 r2, i64 tp, i64 tend, const u32 *qp, const u32 *qn, int pos, int clen, bool qn_on = true)
 {
 	int avail = clen - pos;
 	if (tend - tp < (i64)avail) avail = (int)(tend - tp);
@@ -62,7 +63,7 @@ __device__ __forceinline__ int text_match32(u32 r0, u32 r1, u32 r2, i64 tp, i64 
 	if (avail <= 0) return 0;
 	const u64 d = funnel64(r0, r1, r2, (int)(tp & 15) << 1) ^ q_bits64(qp, pos);
 	const u64 dm = (d | (d >> 1)) & 0x5555555555555555ull;
-	const u32 nm = q_nbits32(qn, pos);
+	const u32 nm = q_nbits32(qn, pos, qn_on);
 	int n = dm ? (__ffsll((unsigned long long)dm) - 1) >> 1 : 32;
 	const int fn = nm ? __ffs((int)nm) - 1 : 32;
 	n = n < fn ? n : fn;
@@ -99,8 +100,8 @@ __device__ __forceinline__ u32 pres4_bit(u64 qb, int K, int i)      // 0 .. 255:
 // sub-range's exit) differs from where it was entered is re-walked along the memo
 // (new searches only until it merges) until no exit moves.  The result is exactly
 // the reference's chain; the on-path bit per position selects which memoised
-// matches become seeds.  Query (2-bit packed + N bitmap), memo, exits and on-path
-// bits live in LDS.
+// matches become seeds.  Query (2-bit packed + N bitmap), memo and exits live in
+// LDS; so do the on-path bits, in the query's words once the walks are over.
 // ---------------------------------------------------------------------------
 // Exclusive prefix of the per-chunk hit counts (n1 = chunks + 1 entries, the last one is 0), by the workgroup that is through
 // LAST in a seed kernel: the counts were stored with agent-scope atomics and are read the same way (the other workgroups ran on
@@ -164,9 +165,19 @@ __device__ __forceinline__ void wave_exscan_hits(const i32 *hits, i32 *base, int
 #define SEED_MIN_WAVES 5        // waves per SIMD the register allocation must allow: 5 = 96 VGPRs (37 of them spilled into 152 bytes of scratch; the loop wants ~150).  Round 6: what the
                                 // kernel leaves FREE on a CU is worth more than what the spills cost it -- see k_seed_wg.  (3 until round 6: 149 VGPRs, no scratch.)
 #endif
-#ifndef LHOP_N
-#define LHOP_N 1024
+// SEED_LDS_DIET = 1 (an experiment build, NOT the product: DESIGN.md section 8e): a chunk's LDS state cut from 11.5 KB to 8.4 KB -- 512 long-hop entries, and
+// only a chunk with an ambiguous base keeps an N bitmap, in the place of half of them -- so that twelve waves fit the LDS that eight take.
+#ifndef SEED_LDS_DIET
+#define SEED_LDS_DIET 0
 #endif
+#ifndef LHOP_N
+#define LHOP_N (SEED_LDS_DIET ? 512 : 1024)      // entries of the long-hop table
+#endif
+#ifndef LHOP_NN
+#define LHOP_NN (SEED_LDS_DIET ? 256 : LHOP_N)   // ... of a chunk WITH ambiguous bases under the diet; the N bitmap lies behind them (the product: behind the whole table)
+#endif
+#define LHOP_WORDS (LHOP_NN + QN_WORDS > LHOP_N ? LHOP_NN + QN_WORDS : LHOP_N)
+static_assert((LHOP_N & (LHOP_N - 1)) == 0 && (LHOP_NN & (LHOP_NN - 1)) == 0 && LHOP_NN <= LHOP_N, "the long-hop table is indexed with a mask");
 // Round 4: two bits per position.  next(s) - s only ever takes three kinds of value -- 1 (no seed from s), 5 (an accepted match under -sen:
 // GSAlign.cpp:88-91) and len + 1 >= MinSeedLength + 1 (an accepted match) -- so the codes are 0 unknown, 1 -> +1, 2 -> +5, 3 -> the hop sits in the
 // hash table; anything else (hops of 2-4, 6-...: the accounting build, MinSeedLength below 5) goes to the table as well.  5 KB -> 2.5 KB per chunk:
@@ -174,20 +185,20 @@ __device__ __forceinline__ void wave_exscan_hits(const i32 *hits, i32 *base, int
 #define MEMO_WORDS (GSA_CHUNK / 16)
 __device__ __forceinline__ int memo_nib(const u32 *memo, int s) { return (int)((memo[s >> 4] >> ((s & 15) << 1)) & 3u); }      // the code: 0 = unknown
 __device__ __forceinline__ void memo_one(u32 *memo, int s) { atomicOr(&memo[s >> 4], 1u << ((s & 15) << 1)); }
-__device__ __forceinline__ int memo_get(const u32 *memo, const u32 *lhop, int s)
+__device__ __forceinline__ int memo_get(const u32 *memo, const u32 *lhop, u32 lmask, int s)
 {
 	const int v = memo_nib(memo, s);
 	if (v < 2) return v;
 	if (v == 2) return 5;
-	for (u32 h = ((u32)s * 40503u) >> 6;; h++) { const u32 e = lhop[h & (LHOP_N - 1)]; if ((e >> 16) == (u32)s + 1) return (int)(e & 0xffffu); }
+	for (u32 h = ((u32)s * 40503u) >> 6;; h++) { const u32 e = lhop[h & lmask]; if ((e >> 16) == (u32)s + 1) return (int)(e & 0xffffu); }
 }
-__device__ __forceinline__ void memo_set(u32 *memo, u32 *lhop, int s, int d, int *abort_flag)
+__device__ __forceinline__ void memo_set(u32 *memo, u32 *lhop, u32 lmask, int s, int d, int *abort_flag)
 {
 	if (d == 1 || d == 5) { atomicOr(&memo[s >> 4], (d == 1 ? 1u : 2u) << ((s & 15) << 1)); return; }
 	const u32 e = ((u32)(s + 1) << 16) | (u32)d;
 	u32 h = ((u32)s * 40503u) >> 6;
-	for (int tries = 0; tries < LHOP_N; tries++, h++) {
-		const u32 old = atomicCAS(&lhop[h & (LHOP_N - 1)], 0u, e);
+	for (u32 tries = 0; tries <= lmask; tries++, h++) {
+		const u32 old = atomicCAS(&lhop[h & lmask], 0u, e);
 		if (old == 0 || old == e) { atomicOr(&memo[s >> 4], 3u << ((s & 15) << 1)); return; }      // (two walks that reach the same start store the same hop: next(s) is a function of s)
 	}
 	*(volatile int *)abort_flag = 1;                                // table full: the chunk is redone by the dense kernels
@@ -248,13 +259,17 @@ struct SeedLds {
 	static constexpr int NV = NCH * NSUB;
 	u32 s_ncand[NCH], s_queue, s_hits[NCH];
 	int changed, s_abort;
-	u32 qp[NCH][QP_WORDS], qn[NCH][QN_WORDS];
-	// next(s) - s per position as 2-bit codes + a hash table for the long hops (memo_get / memo_set above); a full table (never
-	// seen) sends the chunk to the dense kernels like an exhausted budget does.
+	// The query as 2-bit codes.  Dead once the walks are over: the on-path bitmap (PATH_WORDS words, set by the resolved chain behind the loop) then takes its place.
+	u32 qp[NCH][QP_WORDS];
+	// next(s) - s per position as 2-bit codes + a hash table for the long hops (memo_get / memo_set above); a full table sends the
+	// chunk to the dense kernels like an exhausted budget does.
 	u32 memo[NCH][MEMO_WORDS];
-	u32 lhop[NCH][LHOP_N];            // (s + 1) << 16 | hop, 0 = free
+	// (s + 1) << 16 | hop, 0 = free: LHOP_N entries, and behind entry LHOP_NN the N bitmap (QN_WORDS words).  The product: LHOP_NN = LHOP_N, the two simply lie
+	// one behind the other.  SEED_LDS_DIET: a chunk without an ambiguous base (nearly all of them) uses all LHOP_N entries and has NO N bitmap -- its flags are all zero
+	// and q_nbits32 says so without a read; a chunk with one hashes into the first LHOP_NN entries only.  At 1-2 % divergence a chunk stores 200-300 long hops (its
+	// accepted matches plus one per speculative sub-range), so such a chunk's table runs full and may hand the chunk over: the slower, still exact road.
+	u32 lhop[NCH][LHOP_WORDS];
 	uint16_t mblk[COUNT ? GSA_CHUNK : 1];   // Occ blocks the search from s read (accounting build only: NCH = 1)
-	u32 bits[NCH][PATH_WORDS];
 	uint16_t entry_of[NV], exit_of[NV];
 	uint16_t pend_it[SEED_WG];                          // items to walk for real in this pass
 	uint16_t jmp[2][NV], walked_from[NV];               // pointer-jumping buffers; entry of the last real walk of a re-walked sub-range
@@ -271,11 +286,9 @@ struct SeedLds {
 #define changed sl_.changed
 #define s_abort sl_.s_abort
 #define qp sl_.qp
-#define qn sl_.qn
 #define memo sl_.memo
 #define lhop sl_.lhop
 #define mblk sl_.mblk
-#define bits sl_.bits
 #define entry_of sl_.entry_of
 #define exit_of sl_.exit_of
 #define pend_it sl_.pend_it
@@ -288,7 +301,7 @@ struct SeedLds {
 template <bool COUNT, bool E16, int NCH, int WPW>
 __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__restrict__ q, i32 qlen, const Params &prm, u64 *cnt,
                                                       i32 *cand_s, i32 *cand_len, u64 *cand_x0, i32 *cand_freq, u32 cand_cap, u32 *cand_cnt, u32 *onpath, i32 *chunk_hits, u64 *hcnt,
-                                                      u32 budget, u32 *heavy_list, i32 *chunk_base, const int chunk0, const u32 n_chunks, SeedLds<COUNT, NCH> &sl_)
+                                                      u32 budget, u32 *heavy_list, i32 *chunk_base, const int chunk0, const u32 n_chunks, const u32 lhop_cap, SeedLds<COUNT, NCH> &sl_)
 {
 	constexpr int NV = NCH * NSUB;                     // virtual items
 	static_assert(!COUNT || NCH == 1, "the accounting build walks one chunk per wave");
@@ -306,22 +319,35 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 	const int nitems_all = NCH == 1 ? nitems[0] : nitems[0] + nitems[NCH - 1];
 #define CH_SEL(ARR, CH) (NCH == 1 ? ARR[0] : ((CH) ? ARR[NCH - 1] : ARR[0]))
 	// stage the chunks: 32 bases per lane per pass -> two code words + one N word (16-byte global loads)
+	// (the N words go into the zeroed hop table's tail, and only those that have a flag set: hence the table first)
 #pragma unroll
 	for (int ch = 0; ch < NCH; ch++) {
+		for (int p = j; p < MEMO_WORDS; p += SEED_WG) memo[ch][p] = 0;
+		for (int p = j; p < LHOP_WORDS; p += SEED_WG) lhop[ch][p] = 0;
+		for (int it = j; it < nitems[ch]; it += SEED_WG) entry_of[ch * NSUB + it] = (uint16_t)(it * S[ch]);
+		if (j == 0) { s_ncand[ch] = 0; s_hits[ch] = 0; }
+	}
+	SEED_SYNC();
+	int hasn[NCH];                                      // (wave-uniform) the chunk has an ambiguous base: N bitmap behind LHOP_NN hop entries
+#pragma unroll
+	for (int ch = 0; ch < NCH; ch++) {
+		bool anyn = false;
 		for (int g = j; g < QN_WORDS; g += SEED_WG) {
 			u32 w0 = 0, w1 = 0, wn = 0;
 			const int p0 = g << 5;
 			if (p0 < clen[ch]) stage32(q + c0[ch] + p0, p0, clen[ch], w0, w1, wn);
 			if (2 * g < QP_WORDS) qp[ch][2 * g] = w0;
 			if (2 * g + 1 < QP_WORDS) qp[ch][2 * g + 1] = w1;
-			qn[ch][g] = wn;
+			// (stage32 flags the positions behind the chunk's end as N.  Nobody asks about those -- every reader bounds itself by clen first -- and
+			//  they must not make the short last chunk of every contig an N chunk)
+			if (p0 + 32 > clen[ch]) wn = p0 < clen[ch] ? wn & ((1u << (clen[ch] - p0)) - 1u) : 0u;
+			if (wn) { lhop[ch][LHOP_NN + g] = wn; anyn = true; }
 		}
-		for (int p = j; p < MEMO_WORDS; p += SEED_WG) memo[ch][p] = 0;
-		for (int p = j; p < LHOP_N; p += SEED_WG) lhop[ch][p] = 0;
-		for (int p = j; p < PATH_WORDS; p += SEED_WG) bits[ch][p] = 0;
-		for (int it = j; it < nitems[ch]; it += SEED_WG) entry_of[ch * NSUB + it] = (uint16_t)(it * S[ch]);
-		if (j == 0) { s_ncand[ch] = 0; s_hits[ch] = 0; }
+		hasn[ch] = !SEED_LDS_DIET || __any(anyn) ? 1 : 0;      // (the product reads the bitmap whatever it holds)
 	}
+#define QN_OF(CH) ((const u32 *)&lhop[CH][LHOP_NN])
+	// (lhop_cap: a power of two, the entries a test lets the table use -- gsa_set_option "seed_lhop"; LHOP_N otherwise)
+#define LMASK_OF(CH) ((SEED_LDS_DIET && CH_SEL(hasn, CH) && lhop_cap > (u32)LHOP_NN ? (u32)LHOP_NN : lhop_cap) - 1u)
 	if (j == 0) { s_queue = 0; s_npend = 0; s_abort = 0; }
 	if (j < (NV + 31) / 32) rewalked[j] = 0;
 	u32 all_blocks = 0, rounds = 0, iters = 0;
@@ -340,7 +366,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 		// memory latency.
 		int item = -1, s = 0, bend = 0, pos = 0, mode = M_ADV; u32 kid = 0, pid = 0, pext = 0;
 		int lclen = 0;                                        // length of the chunk my item belongs to
-		const u32 *qp_l = qp[0], *qn_l = qn[0]; u32 *memo_l = memo[0], *lhop_l = lhop[0];      // ... and that chunk's arrays
+		const u32 *qp_l = qp[0], *qn_l = QN_OF(0); u32 *memo_l = memo[0], *lhop_l = lhop[0]; u32 lmask_l = LMASK_OF(0); bool hasn_l = CH_SEL(hasn, 0) != 0;      // ... and that chunk's arrays
 		FmIntv ik = {0, 0, 0}; u32 blk = 0; i64 tp = 0;
 		// Round 4: an interval of 2 .. SEED_MULTI rows is finished WITHOUT further Occ steps.  Its rows are suffix-array rows x0 .. x0 + x2 - 1,
 		// sorted by suffix; extending the match by base c keeps the rows whose text continues with c -- a contiguous run, and the reference's
@@ -425,7 +451,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 #pragma unroll
 					for (int k2 = 0; k2 < PLOOK; k2++) {
 						if (s >= bend || memo_nib(memo_l, s)) break;
-						const u32 nb = q_nbits32(qn_l, s);
+						const u32 nb = q_nbits32(qn_l, s, hasn_l);
 						if (s + prm.MinSeedLength > lclen || (nb & (L == 32 ? ~0u : (1u << L) - 1)) != 0) break;
 						if (k2 == 0 ? PRES4_TEST(1) : k2 == 1 ? PRES4_TEST(2) : PRES4_TEST(3)) break;          // occurs: needs its table entry (next iteration)
 						memo_one(memo_l, s); s += 1;
@@ -445,7 +471,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 				malive = (1u << (int)ik.x2) - 1u; mode = M_MTEXT;
 			} else if (!COUNT && SEED_MULTI > 1 && mode == M_MTEXT) {
 				int g0 = -1, g1 = -1, g2 = -1, g3 = -1;
-#define MT_ROW(G, W, P) { int got = text_match32(W.a, W.b, W.c, P, (i64)di.seq_len, qp_l, qn_l, pos, lclen); if (got == 32) got += text_match32(W.c, W.d, W.e, P + 32, (i64)di.seq_len, qp_l, qn_l, pos + 32, lclen); G = got; }
+#define MT_ROW(G, W, P) { int got = text_match32(W.a, W.b, W.c, P, (i64)di.seq_len, qp_l, qn_l, pos, lclen, hasn_l); if (got == 32) got += text_match32(W.c, W.d, W.e, P + 32, (i64)di.seq_len, qp_l, qn_l, pos + 32, lclen, hasn_l); G = got; }
 				if (malive & 1u) MT_ROW(g0, w5, mp[0])
 				if (malive & 2u) MT_ROW(g1, w5b, mp[1])
 				if (malive & 4u) MT_ROW(g2, w5c, mp[2])
@@ -463,12 +489,12 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 				} else malive = na;
 				if (mode == M_MTEXT && !ended && malive != na) malive = na;
 			} else if (mode == M_TEXT) {
-				int got = text_match32(r0, r1, r2, tp, (i64)di.seq_len, qp_l, qn_l, pos, lclen);
-				if (got == 32) got += text_match32(r2, r3, r4, tp + 32, (i64)di.seq_len, qp_l, qn_l, pos + 32, lclen);
+				int got = text_match32(r0, r1, r2, tp, (i64)di.seq_len, qp_l, qn_l, pos, lclen, hasn_l);
+				if (got == 32) got += text_match32(r2, r3, r4, tp + 32, (i64)di.seq_len, qp_l, qn_l, pos + 32, lclen, hasn_l);
 				pos += got; tp += got;
 				ended = got < 64;
 			} else if (mode == M_FM) {
-				const bool can = pos < lclen && !q_isn(qn_l, pos < lclen ? pos : 0);
+				const bool can = pos < lclen && !q_isn(qn_l, pos < lclen ? pos : 0, hasn_l);
 				const bool ok = can && fm_extend_loaded(di, ik, q_code(qp_l, pos < lclen ? pos : 0), bk, bl, kk, ll, kn, ln, blk);
 				ended = !ok;
 				if (ok) { pos++; if (!COUNT && ik.x2 == 1) mode = M_LOC; else if (!COUNT && SEED_MULTI > 1 && ik.x2 <= SEED_MULTI) mode = M_MLOC; }
@@ -484,7 +510,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 					else cnt[CNT_OVERFLOW] = 1;
 					d = prm.bSensitive ? 5 : len + 1;
 				}
-				memo_set(memo_l, lhop_l, s, d, &s_abort); if (COUNT) mblk[s] = (uint16_t)blk;
+				memo_set(memo_l, lhop_l, lmask_l, s, d, &s_abort); if (COUNT) mblk[s] = (uint16_t)blk;
 				all_blocks += blk;
 				s += d; mode = M_ADV;
 			}
@@ -509,14 +535,14 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 					need_item = false;
 					if (item < 0) { mode = M_DONE; break; }
 					const int ch = NCH == 1 ? 0 : (item >= NSUB ? NCH - 1 : 0), li = item - ch * NSUB;
-					lclen = CH_SEL(clen, ch); qp_l = qp[ch]; qn_l = qn[ch]; memo_l = memo[ch]; lhop_l = lhop[ch];
+					lclen = CH_SEL(clen, ch); qp_l = qp[ch]; qn_l = QN_OF(ch); memo_l = memo[ch]; lhop_l = lhop[ch]; lmask_l = LMASK_OF(ch); hasn_l = CH_SEL(hasn, ch) != 0;
 					const int S_l = CH_SEL(S, ch);
 					s = entry_of[item]; bend = (li + 1) * S_l < lclen ? (li + 1) * S_l : lclen;
 				}
 				if (s >= bend) { exit_of[item] = (uint16_t)s; need_item = true; continue; }
-				const int m_ = memo_get(memo_l, lhop_l, s);
+				const int m_ = memo_get(memo_l, lhop_l, lmask_l, s);
 				if (m_) { s += m_; continue; }
-				const u32 nb = q_nbits32(qn_l, s);
+				const u32 nb = q_nbits32(qn_l, s, hasn_l);
 				const int L = prm.MinSeedLength < 32 ? prm.MinSeedLength : 32;
 				if (nb & 1u) { memo_one(memo_l, s); if (COUNT) mblk[s] = 0; s += 1; }
 				else if (!COUNT && (s + prm.MinSeedLength > lclen || (nb & (L == 32 ? ~0u : (1u << L) - 1)) != 0)) { memo_one(memo_l, s); s += 1; }      // cannot reach MinSeedLength
@@ -609,12 +635,20 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 		}
 		SEED_SYNC();
 	}
-	// mark the true path and count the Occ blocks the reference's walk reads
+	// mark the true path and count the Occ blocks the reference's walk reads.  The walks are over (every way out of the loop is behind a SEED_SYNC), nobody
+	// reads the query again: the on-path bits take the first PATH_WORDS words of its place
+	static_assert(PATH_WORDS <= QP_WORDS, "the on-path bitmap lies in the query's words");
+#define bits qp
 	u32 alg_blocks = 0;
+	if (!heavy) {
+#pragma unroll
+		for (int ch = 0; ch < NCH; ch++) for (int p = j; p < PATH_WORDS; p += SEED_WG) bits[ch][p] = 0;
+		SEED_SYNC();
+	}
 	if (!heavy) for (int v = j; v < NV; v += SEED_WG) if (V_LIVE(v)) {
 		const int ch = v >= NSUB ? NCH - 1 : 0, li = v - ch * NSUB;
 		const int bend = (li + 1) * CH_SEL(S, ch) < CH_SEL(clen, ch) ? (li + 1) * CH_SEL(S, ch) : CH_SEL(clen, ch);
-		for (int s = entry_of[v]; s < bend;) { atomicOr(&bits[ch][s >> 5], 1u << (s & 31)); if (COUNT) alg_blocks += mblk[s]; s += memo_get(memo[ch], lhop[ch], s); }
+		for (int s = entry_of[v]; s < bend;) { atomicOr(&bits[ch][s >> 5], 1u << (s & 31)); if (COUNT) alg_blocks += mblk[s]; s += memo_get(memo[ch], lhop[ch], LMASK_OF(ch), s); }
 	}
 #undef V_LIVE
 	for (int o = 32; o; o >>= 1) { alg_blocks += __shfl_down(alg_blocks, o); all_blocks += __shfl_down(all_blocks, o); }
@@ -650,6 +684,9 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 			if (s_hits[ch]) atomicAdd((unsigned long long *)&cnt[CNT_HITS], (unsigned long long)s_hits[ch]);      // the contig's total: all the host needs to go on
 		}
 	}
+#undef bits
+#undef QN_OF
+#undef LMASK_OF
 #undef CH_SEL
 	// the workgroup that is through last puts the counters into pinned memory (the host waits for this kernel, nothing
 	// else) and leaves them at zero for the next contig
@@ -672,11 +709,9 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 #undef changed
 #undef s_abort
 #undef qp
-#undef qn
 #undef memo
 #undef lhop
 #undef mblk
-#undef bits
 #undef entry_of
 #undef exit_of
 #undef pend_it
@@ -695,7 +730,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 // workgroups' worth of LDS and wave slots whatever the contig's size (what it leaves free the kernels of other contexts can take).
 #define SEED_TICKET 16
 #ifndef SEED_PERSIST
-#define SEED_PERSIST 12        // (A/B builds with SEED_WPW = 1 only: one-wave workgroups per CU of round 5's launch shape -- what the LDS admits at 12.8 KB per chunk)
+#define SEED_PERSIST 12        // (A/B builds with SEED_WPW = 1 only: one-wave workgroups per CU of round 5's launch shape -- what the LDS admitted at 12.8 KB per chunk)
 #endif
 #ifndef SEED_NCH
 #define SEED_NCH 1              // chunks per wave of the production kernel (2: measured slower, see seed_chunk; the accounting build: always 1)
@@ -704,7 +739,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 // vector registers (3 waves per SIMD x 152), for a kernel that issues VALU in 20 % of its cycles and waits for memory in 54 %.  Nothing else fitted beside it -- not a
 // striped-DP workgroup (13 - 55 KB of LDS, 48 VGPRs), not a fused pass (four waves of ~100 VGPRs) -- so with four contexts in flight the CUs were handed back and forth
 // between kernels that each use a fraction of them, and the step was the SUM of the stages (52 + 46 ms of the 98).  Now:
-//  * a workgroup is SEED_WPW = 8 INDEPENDENT waves, each with its own SeedLds and its own tickets, and asks for more than half a CU's LDS (102 KB), so exactly ONE
+//  * a workgroup is SEED_WPW = 8 INDEPENDENT waves, each with its own SeedLds and its own tickets, and asks for more than half a CU's LDS (102 400 B), so exactly ONE
 //    workgroup fits a CU and a launch of n_cus workgroups lands on EVERY CU (the dispatcher fills a CU before it moves on: a short grid of one-wave workgroups meant
 //    fewer CUs, not thinner ones);
 //  * the register budget is 96 VGPRs per wave (SEED_MIN_WAVES = 5; the LDS is a launch parameter because with static LDS the compiler knows that the LDS holds the kernel
@@ -714,21 +749,29 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 // chunks per CU instead of twelve, spills), the STEP 98.7 -> 93.1 ms; 250 Mb contigs 35.7 -> 38.2 Gbp/s.  Either half alone does nothing: 8 waves at 155 VGPRs 98.7 ms,
 // 12 one-wave workgroups at 96 VGPRs 97.9 ms.
 #ifndef SEED_WPW
-#define SEED_WPW 8              // waves (= chunks in flight) per workgroup = per CU (7 / 9 / 10: 96.9 / 95.2 / 94.7 ms; 1 = round 5's twelve one-wave workgroups per CU, an A/B build)
+#define SEED_WPW (SEED_LDS_DIET ? 12 : 8)      // waves (= chunks in flight) per workgroup = per CU (7 / 9 / 10 at 12.8 KB per chunk: 96.9 / 95.2 / 94.7 ms -- the LDS grew with the count; 12: what
+                                // fits the same 102 400 B at SEED_LDS_DIET's 8.4 KB per chunk, an experiment build; 1 = round 5's twelve one-wave workgroups per CU, an A/B build)
 #endif
 #ifndef SEED_WGS_PER_CU
 #define SEED_WGS_PER_CU 1       // fat workgroups per CU (the LDS a workgroup asks for is more than 160 KB / (SEED_WGS_PER_CU + 1): one more never fits)
 #endif
 #define SEED_WG_LDS_MIN ((160 * 1024) / (SEED_WGS_PER_CU + 1) + 2048)
+#ifndef SEED_WG_LDS
+#define SEED_WG_LDS 102400      // what a fat workgroup asks for, whatever its waves need (until the on-path bits moved into the query's words it was what eight waves needed: 8 x 12 800): the
+                                // 58 KB beside it are what the other contexts' kernels live on
+#endif
+static_assert(SEED_WPW == 1 || (SEED_WG_LDS >= SEED_WG_LDS_MIN && SEED_WG_LDS <= 160 * 1024), "a fat workgroup's LDS: more than half a CU's, so that two never share one");
 #define SEED_LB_WAVES(COUNT_) ((COUNT_) ? 1 : SEED_MIN_WAVES)
 template <bool COUNT, bool E16>
 __global__ void __launch_bounds__(SEED_WG * (COUNT ? 1 : SEED_WPW), SEED_LB_WAVES(COUNT)) k_seed_wg(DevIndex di, const uint8_t *__restrict__ q, i32 qlen, Params prm, u64 *cnt,
                                                       i32 *cand_s, i32 *cand_len, u64 *cand_x0, i32 *cand_freq, u32 cand_cap, u32 *cand_cnt, u32 *onpath, i32 *chunk_hits, u64 *hcnt,
-                                                      u32 budget, u32 *heavy_list, i32 *chunk_base, u64 tk_base, u32 n_chunks)
+                                                      u32 budget, u32 *heavy_list, i32 *chunk_base, u64 tk_base, u32 n_chunks, u32 lhop_cap)
 {
 	constexpr int NCH = COUNT ? 1 : SEED_NCH;
 	constexpr int WPW = COUNT ? 1 : SEED_WPW;
 	typedef SeedLds<COUNT, NCH> Lds;
+	static_assert(WPW == 1 || sizeof(Lds) * WPW <= SEED_WG_LDS, "SeedLds has outgrown the workgroup's LDS: SEED_WPW waves no longer fit SEED_WG_LDS bytes");
+	static_assert(sizeof(Lds) % 4 == 0, "one SeedLds per wave, back to back");
 	extern __shared__ __attribute__((aligned(16))) unsigned char seed_dyn_lds[];      // (a launch parameter: see the kernel's header)
 	Lds *lds = (Lds *)seed_dyn_lds;
 	Lds &L = lds[WPW == 1 ? 0 : (threadIdx.x >> 6)];
@@ -737,7 +780,7 @@ __global__ void __launch_bounds__(SEED_WG * (COUNT ? 1 : SEED_WPW), SEED_LB_WAVE
 		if ((threadIdx.x & 63) == 0) unit = (u32)(atomicAdd((unsigned long long *)&cnt[SEED_TICKET], 1ull) - tk_base);
 		unit = (u32)__builtin_amdgcn_readfirstlane((int)unit);
 		if ((u64)unit * NCH >= n_chunks) return;
-		seed_chunk<COUNT, E16, NCH, WPW>(di, q, qlen, prm, cnt, cand_s, cand_len, cand_x0, cand_freq, cand_cap, cand_cnt, onpath, chunk_hits, hcnt, budget, heavy_list, chunk_base, (int)(unit * NCH), n_chunks, L);
+		seed_chunk<COUNT, E16, NCH, WPW>(di, q, qlen, prm, cnt, cand_s, cand_len, cand_x0, cand_freq, cand_cap, cand_cnt, onpath, chunk_hits, hcnt, budget, heavy_list, chunk_base, (int)(unit * NCH), n_chunks, lhop_cap, L);
 	}
 }
 
@@ -1924,10 +1967,11 @@ int stage1_seed(gsa_ctx *c)
 			}
 			const u64 tk_base = c->seed_ticket; c->seed_ticket += (u64)n_units + (u64)grid * (u64)wpw;      // (every wave's last draw is the one that fails)
 			const size_t dl_count = sizeof(SeedLds<true, 1>);
-			size_t dl = sizeof(SeedLds<false, SEED_NCH>) * SEED_WPW; if (SEED_WPW > 1 && dl < SEED_WG_LDS_MIN) dl = SEED_WG_LDS_MIN;      // (more than half a CU's LDS: two fat workgroups never share a CU)
-			if (c->count_blocks) hipLaunchKernelGGL((k_seed_wg<true, false>), dim3(grid), dim3(SEED_WG), dl_count, st, GSA_SEED_ARGS, tk_base, (u32)n_chunks);
-			else if (c->di.kmer_e16) hipLaunchKernelGGL((k_seed_wg<false, true>), dim3(grid), dim3(SEED_WG * SEED_WPW), dl, st, GSA_SEED_ARGS, tk_base, (u32)n_chunks);
-			else hipLaunchKernelGGL((k_seed_wg<false, false>), dim3(grid), dim3(SEED_WG * SEED_WPW), dl, st, GSA_SEED_ARGS, tk_base, (u32)n_chunks);
+			size_t dl = sizeof(SeedLds<false, SEED_NCH>) * SEED_WPW; if (SEED_WPW > 1 && dl < SEED_WG_LDS) dl = SEED_WG_LDS;      // (more than half a CU's LDS -- two fat workgroups never share a CU -- and the same footprint whatever the waves need: k_seed_wg asserts that they fit)
+			const u32 lhop_cap = c->opt.seed_lhop > 0 && c->opt.seed_lhop < LHOP_N ? (u32)c->opt.seed_lhop : (u32)LHOP_N;
+			if (c->count_blocks) hipLaunchKernelGGL((k_seed_wg<true, false>), dim3(grid), dim3(SEED_WG), dl_count, st, GSA_SEED_ARGS, tk_base, (u32)n_chunks, lhop_cap);
+			else if (c->di.kmer_e16) hipLaunchKernelGGL((k_seed_wg<false, true>), dim3(grid), dim3(SEED_WG * SEED_WPW), dl, st, GSA_SEED_ARGS, tk_base, (u32)n_chunks, lhop_cap);
+			else hipLaunchKernelGGL((k_seed_wg<false, false>), dim3(grid), dim3(SEED_WG * SEED_WPW), dl, st, GSA_SEED_ARGS, tk_base, (u32)n_chunks, lhop_cap);
 #undef GSA_SEED_ARGS
 			if (c->profiling || c->prof_seed) hipEventRecord(c->ev[1], st);
 			// (the counters are in pinned memory when the seed kernel is done; the host waits for that, not for the scan of the

@@ -172,6 +172,7 @@ void gsa_release_reserved(int device);
  *                    10 000-bp chunk): 1 (default) = through a byte per value, plain stores, packed into the bitmap by a pass of its own, when there are at least
  *                    512 hits per chunk, at most 256 values per hit and at most 2^32 values (2 GB per context for a 64 Mb bundle against a 12 Mb reference); 0 = always with atomics
  *                    on the bitmap; 2 = always through the bytes (tests).  Results do not depend on it
+ *   "seed_lhop"      test hook: entries of the seed kernel's long-hop table that a chunk may use (a power of two >= 16; 0 = all of them)
  *   "dp_safe", "dp_fake_timeout"   test hooks: one striped DP job per launch; the next n contigs report a stripe hand-off time-out once
  * Unknown names and values outside an option's range (negative sizes, seed_budget 0, ...): GSA_ERR_ARG, nothing changed.
  * Until round 4 some of these were environment variables read by the library (GSA_SPLIT_MIN, GSA_BUNDLE_CONTIG, GSA_BUNDLE_CAP, GSA_SEED_BUDGET,
