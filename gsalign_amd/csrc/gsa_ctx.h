@@ -86,7 +86,7 @@ struct Options {
 	int64_t pd_two_level_min = 2000000;   // PosDiff bitmaps of more blocks than this (a reference above ~1 Gbp) are scanned in two passes: list the touched blocks, count those (tests: 0)
 	int dp_occupancy = 0;              // > 0: at most this many striped-DP workgroups per CU (LDS padding): leaves wave slots for the passes beside it (experiment; 0 = off)
 	int pd_bytes = 1;                  // the PosDiff bitmap of a contig (bundle) whose hits scatter (-sen: thousands of chance hits per chunk) is filled through a byte per value, plain stores, and packed
-	                                   // afterwards -- no device-scope atomics (k_pd_pack, k_seed.hip); 1 = when the hit count says so, 0 = never, 2 = always (tests)
+	                                   // afterwards -- no device-scope atomics (k_pd_pack, k_seed_select.hip); 1 = when the hit count says so, 0 = never, 2 = always (tests)
 	int pres_from_kmer = 1;            // the presence table is derived from the k-mer jump table when both hold k-mers of one length (0: always from a scan of the text; a test compares the two)
 	int kmer_k = 0;                    // gsa_create_opts (GSA_CREATE_KMER_K): length of the jump table's k-mers (0: by text length and free memory)
 };
@@ -100,6 +100,7 @@ struct gsa_ctx {
 	hipEvent_t ev_seed_fork = nullptr;
 	u64 seed_ticket = 0;                    // value of the seed kernel's ticket counter (d_cnt[16]) before the next launch
 	int n_cus = 0;
+	bool seed_lds_checked = false;       // stage1_seed compared the LDS its launch asks for with the device's per-block limit
 	hipStream_t stream_aux[4] = {nullptr, nullptr, nullptr, nullptr};   // [3]: the striped DP's lower size class beside its upper one (option dp_side); [0] early striped DP, [1] tiny DP + strings + sums, [2] records to the host (four streams in all: one per hardware queue)
 	std::string err;
 	Params prm;
@@ -284,15 +285,18 @@ template <class T> static inline T *pin_ensure(gsa_ctx *c, DevBuf &b, size_t n)
 }
 
 // stage drivers (one per translation unit)
-int build_dense_sa(gsa_ctx *c, u64 n_sa);   // k_seed.hip
-int unpack_pac(gsa_ctx *c, const uint8_t *d_pac, i64 G, uint8_t *d_ref);   // k_seed.hip  (GSA_CREATE_REF_PAC: RefSequence from the .pac bytes, on the device)
-int build_occ(gsa_ctx *c, const void *ref_layout, u64 n_blocks128);   // k_seed.hip: the device's Occ blocks from the reference's layout
-int build_presence(gsa_ctx *c);             // k_seed.hip  (after MinSeedLength changed)
+int build_dense_sa(gsa_ctx *c, u64 n_sa);   // k_tables.hip
+int unpack_pac(gsa_ctx *c, const uint8_t *d_pac, i64 G, uint8_t *d_ref);   // k_tables.hip  (GSA_CREATE_REF_PAC: RefSequence from the .pac bytes, on the device)
+int build_occ(gsa_ctx *c, const void *ref_layout, u64 n_blocks128);   // k_tables.hip: the device's Occ blocks from the reference's layout
+int build_presence(gsa_ctx *c);             // k_tables.hip  (after MinSeedLength changed)
 int stage1_seed(gsa_ctx *c);          // k_seed.hip
-int stage1_import_hits(gsa_ctx *c, const u64 *keys, const u32 *vals, i64 n);   // k_seed.hip
-int stage1_finish_split(gsa_ctx *c);  // k_seed.hip
-int stage1_restore_pdbm(gsa_ctx *c);  // k_seed.hip  (the PosDiff bitmap again from the hits a finished stage 2 left in d_key_a)
-int seed_view_sort(gsa_ctx *c);       // k_seed.hip  (PosDiff-sorted seeds + groups: stage-1 view, or front of stage 2 without the PosDiff bitmap)
+int stage1_dense(gsa_ctx *c, hipStream_t st, const uint8_t *d_q, i32 qlen, i64 n_chunks, u64 n_heavy, bool dense_all, bool sweep_all, size_t ccap, u64 &hits, u64 &maxcand, u64 &occ_all);   // k_seed_dense.hip  (stage1_seed's dense kernels: launch, wait, counters)
+int prepare_pd_bitmap(gsa_ctx *c, i64 n_hits, i64 n_chunks = 0);   // k_seed_select.hip  (whether this contig keeps the bitmap of occupied PosDiff values, cleared)
+int stage1_select(gsa_ctx *c, i64 n_chunks, i64 n_hits, size_t ccap, u64 contig_maxcand, i32 s_off, u64 occ_all);   // k_seed_select.hip  (stage1_seed's tail: hits located and keyed, groups)
+int stage1_import_hits(gsa_ctx *c, const u64 *keys, const u32 *vals, i64 n);   // k_seed_select.hip
+int stage1_finish_split(gsa_ctx *c);  // k_seed_select.hip
+int stage1_restore_pdbm(gsa_ctx *c);  // k_seed_select.hip  (the PosDiff bitmap again from the hits a finished stage 2 left in d_key_a)
+int seed_view_sort(gsa_ctx *c);       // k_seed_select.hip  (PosDiff-sorted seeds + groups: stage-1 view, or front of stage 2 without the PosDiff bitmap)
 int stage2_chain(gsa_ctx *c);         // k_chain.hip
 int launch_early_dp(gsa_ctx *c);      // k_chain.hip  (striped DP for the large gaps listed at the end of stage 2)
 int stage2_fetch_host(gsa_ctx *c);    // k_chain.hip  (counts + S2 block table for the stage-2 view)

@@ -31,7 +31,7 @@ __device__ __forceinline__ int gsa_nt4(uint8_t c)
 //   c = counts of A, C, G, T in front of the block as u32, relative to the block's SUPER-block (2^occ_shift blocks; its 64-bit
 //       base counts in di.occ_base, a table of a few entries; no table = no base: texts below 2^32 rows),
 //   w = 64 symbols in the reference's bit order (first symbol in the top bits of w.x; w.x, w.y = the first 32).
-// Built from the uploaded reference layout by k_occ_relayout (k_seed.hip); the counts are the reference's numbers regrouped, so
+// Built from the uploaded reference layout by k_occ_relayout (k_tables.hip); the counts are the reference's numbers regrouped, so
 // every Occ value -- and the number of 128-row blocks the reference would have touched (row arithmetic) -- is unchanged.
 struct FmBlock { uint4 c, w; u64 ba, bc, bg, bt; };
 
