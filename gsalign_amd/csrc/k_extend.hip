@@ -86,7 +86,7 @@ struct OpSlotsT {
 			i32 qg = it.qn - (it.q + it.len); if (qg < 0) qg = 0;
 			i64 rg64 = it.rn - (it.r + it.len); i32 rg = rg64 < 0 ? 0 : (i32)rg64;
 			gsa_frag g; g.bseed = 0; g.qpos = it.q + it.len; g.rpos = it.r + it.len; g.qlen = qg; g.rlen = rg; g.aln_off = 0; g.aln_len = 0; g._pad = 0;
-			// (class, mismatch count and the link to an early DP launch: k_gap_class, one thread per record)
+			// (class, mismatch count and the link to an early DP launch: k_gap_class)
 			frag[p + 1] = g; ftype[p + 1] = FT_DP; fmism[p + 1] = 0;
 			fearly[p + 1] = it.early;
 		}
@@ -94,20 +94,79 @@ struct OpSlotsT {
 	__device__ void done(const i32 *t) const { mail[M_NF] = t[0]; }
 };
 
-// class of every gap record (GenerateFragAlignment :311-342) -- a kernel of its own, one thread per record: the
-// mismatch count of an equal-length gap is a serial loop over its bases, too heavy for a thread of a fused pass
-// -- and the link to a large DP gap stage 2 launched early: the result counts only if this is exactly the gap
-// it listed.
-__global__ void k_gap_class(i64 ub, const i32 *__restrict__ mail, const gsa_frag *__restrict__ frag, const uint8_t *__restrict__ query, const uint8_t *__restrict__ ref,
-                            const i32 *__restrict__ e_list, const i64 *__restrict__ e_off1, const i64 *__restrict__ e_off2, i32 *ftype, i32 *fmism, i32 *fearly, i32 *e_rec)
+// ---- a tile of 256 records laid out column by column (k_gap_class, k_materialize) ----
+// Record t of the tile owns L columns (one per base pair it compares, or per position of its gapped strings); the
+// exclusive scan of L over the tile numbers the columns, and a wavefront takes them 64 at a time: consecutive lanes
+// then touch consecutive bytes of a record instead of 64 different records.  s_start[t]: the columns in front of
+// record t, s_start[256]: all of them.  (Ends in a barrier: whatever the threads put into LDS in front of the call is
+// visible after it.)
+__device__ __forceinline__ void tile_scan(i32 L, i32 *s_start, i32 *s_wsum)
 {
-	GID(ub);
-	if (i >= mail[M_NF] || ftype[i] == FT_SEED) return;
-	const gsa_frag g = frag[i];
-	i32 mism; const i32 t = classify_gap(query, ref, g.qpos, g.rpos, g.qlen, g.rlen, mism);
+	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+	i32 s = L;
+	for (int d = 1; d < 64; d <<= 1) { const i32 a = __shfl_up(s, d); if (lane >= d) s += a; }
+	if (lane == 63) s_wsum[wv] = s;
+	__syncthreads();
+	i32 base = 0;
+	for (int w = 0; w < 3; w++) if (w < wv) base += s_wsum[w];
+	s_start[tid] = base + s - L;
+	if (tid == 255) s_start[256] = base + s;
+	__syncthreads();
+}
+// the record of column col < s_start[256]: the last r with s_start[r] <= col (a record without columns is never the last), 8 probes
+__device__ __forceinline__ int tile_find(const i32 *s_start, i32 col)
+{
+	int lo = 0, hi = 256;
+#pragma unroll
+	for (int st = 0; st < 8; st++) { const int m = (lo + hi) >> 1; if (s_start[m] <= col) lo = m; else hi = m; }
+	return lo;
+}
+// the lanes of a 64-column chunk that hold columns of this lane's record up to its own: p is the lane's position in the
+// record.  A segmented inclusive sum of a flag over the chunk is the population count of the flag's ballot under this mask.
+__device__ __forceinline__ u64 seg_mask(i32 p, int lane)
+{
+	const int dist = p < lane ? (int)p : lane;      // lanes of the same record in front of this one
+	return ((2ull << lane) - 1) & ~((1ull << (lane - dist)) - 1);
+}
+
+// class of every gap record (GenerateFragAlignment :311-342) -- a kernel of its own -- and the link to a large DP gap
+// stage 2 launched early: the result counts only if this is exactly the gap it listed.  A workgroup settles a tile of
+// 256 records.  Only a gap of equal lengths needs the sequences (CheckFragPairMismatch): those gaps are laid out column
+// by column, a lane compares one base pair (positions where the QUERY is ambiguous are skipped) and a segmented count
+// gives every record its mismatches.  This is the FULL count where classify_gap (gsa_gap.h; OpEarlyGaps still calls
+// it) stops counting once GSA_MAX_MISMATCH is passed: the class is the same, and so is fmism wherever the class is
+// FT_EQ, the only place it is read.
+__global__ void __launch_bounds__(TPB) k_gap_class(i64 ub, const i32 *__restrict__ mail, const gsa_frag *__restrict__ frag, const uint8_t *__restrict__ query, const uint8_t *__restrict__ ref,
+                                                    const i32 *__restrict__ e_list, const i64 *__restrict__ e_off1, const i64 *__restrict__ e_off2, i32 *ftype, i32 *fmism, i32 *fearly, i32 *e_rec)
+{
+	__shared__ i32 s_start[257], s_wsum[4], s_qpos[TPB], s_mism[TPB];
+	__shared__ i64 s_rpos[TPB];
+	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+	const i64 nf = mail[M_NF] < ub ? mail[M_NF] : ub, i = (i64)blockIdx.x * TPB + tid;
+	if ((i64)blockIdx.x * TPB >= nf) return;
+	const bool gap = i < nf && ftype[i] != FT_SEED;
+	i32 qpos = 0, qg = 0, rg = 0; i64 rpos = 0;
+	if (gap) { qpos = frag[i].qpos; qg = frag[i].qlen; rg = frag[i].rlen; rpos = frag[i].rpos; }
+	const i32 L = (qg > 0 && qg == rg) ? qg : 0;
+	s_qpos[tid] = qpos; s_rpos[tid] = rpos; s_mism[tid] = 0;
+	tile_scan(L, s_start, s_wsum);
+	const i32 T = s_start[256];
+	for (i32 c0 = wv << 6; c0 < T; c0 += TPB) {
+		const i32 col = c0 + lane; const bool act = col < T;
+		const int r = tile_find(s_start, act ? col : T - 1);
+		const i32 p = col - s_start[r];
+		bool bad = false;
+		if (act) { const int a = gsa_nt4(query[s_qpos[r] + p]); bad = a != 4 && a != gsa_nt4(ref[s_rpos[r] + p]); }
+		const u64 bm = __ballot(bad);
+		if (act && (lane == 63 || col + 1 == s_start[r + 1])) { const i32 m = __popcll(bm & seg_mask(p, lane)); if (m) atomicAdd(&s_mism[r], m); }
+	}
+	__syncthreads();
+	if (!gap) return;
+	const i32 mism = s_mism[tid];
+	const i32 t = qg == 0 ? FT_DEL : rg == 0 ? FT_INS : (qg == rg && mism <= GSA_MAX_MISMATCH) ? FT_EQ : FT_DP;
 	ftype[i] = t; fmism[i] = mism;
 	i32 e = fearly[i];
-	if (e >= 0 && !(t == FT_DP && e_off2[e] == g.qpos && e_off1[e] == g.rpos && e_list[3 * e + 1] == g.rlen && e_list[3 * e + 2] == g.qlen)) e = -1;
+	if (e >= 0 && !(t == FT_DP && e_off2[e] == qpos && e_off1[e] == rpos && e_list[3 * e + 1] == rg && e_list[3 * e + 2] == qg)) e = -1;
 	fearly[i] = e; if (e >= 0) e_rec[e] = (i32)i;
 }
 
@@ -204,20 +263,24 @@ __device__ i32 write_dp_record_wg(i64 i, i32 L, const uint8_t *__restrict__ op, 
 }
 
 // Gapped strings and the per-block sums of the records' (aln_len, score) contributions.  MAT_WGS workgroups, each over one
-// contiguous range of the records in tiles of 256: a thread settles its own record when it is a seed or a short gap (the bulk:
-// median gap 11 bases); longer gaps are queued in LDS and written by whole wavefronts.  The sums stay in registers while the
-// tiles lie in one block and are added with one atomic pair when the block changes (a contig has a handful of blocks); a tile
-// that straddles a block edge adds per record.  (Round 2 stored the contributions per record and summed them in a second
-// kernel, k_block_reduce: 8 bytes written and read per record and 0.8 ms on the tail of every human-sized contig.)
-#define MAT_SERIAL 32
+// contiguous range of the records in tiles of 256.  A tile: every thread loads the descriptor of its own record into LDS
+// (coalesced, once); the string columns of the records that are not seeds or large DP jobs are numbered by tile_scan, and
+// every wavefront writes its share of them in chunks of 64 -- a lane per column, so the lanes of a load or store touch
+// consecutive bytes.  (Until round 6 a thread wrote a whole record of up to 32 columns: 160 byte-wide memory instructions
+// per 64 records, each over up to 64 cache lines.)  A column of a DP record needs the reference and query bases consumed in
+// front of it: the segmented count of the op flags over the chunk, plus a carry for the record that began in an earlier
+// chunk.  The sums stay in registers while the tiles lie in one block and are added with one atomic pair when the block
+// changes (a contig has a handful of blocks); a tile that straddles a block edge adds per record.  (Round 2 stored the
+// contributions per record and summed them in a second kernel, k_block_reduce: 8 bytes written and read per record and
+// 0.8 ms on the tail of every human-sized contig.)
 #define MAT_WGS 2048
 __global__ void __launch_bounds__(256) k_materialize(i32 nfb, const i32 *__restrict__ nf_ptr, const i32 *__restrict__ fragbase, const i32 *__restrict__ ftype, const i32 *__restrict__ fmism, const i32 *__restrict__ fjob,
                                                       const i32 *__restrict__ jlarge, const i32 *__restrict__ nops, const i32 *__restrict__ alen, const i64 *__restrict__ aoff, const uint8_t *__restrict__ ops,
                                                       const i64 *__restrict__ opsoff, const uint8_t *__restrict__ query, const uint8_t *__restrict__ ref,
-                                                      gsa_frag *frag, uint8_t *aln1, uint8_t *aln2, i32 *bl_len, i32 *bl_score)
+                                                      gsa_frag *frag, uint8_t *__restrict__ aln1, uint8_t *__restrict__ aln2, i32 *bl_len, i32 *bl_score)
 {
-	__shared__ i32 s_list[256];
-	__shared__ int s_n;
+	__shared__ i32 s_start[257], s_wsum[4], s_kind[256], s_qpos[256], s_score[256];
+	__shared__ i64 s_aoff[256], s_rpos[256], s_ops[256];
 	__shared__ i32 s_len[4], s_sc[4];
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const i64 nf = nf_ptr[0];
@@ -238,92 +301,68 @@ __global__ void __launch_bounds__(256) k_materialize(i32 nfb, const i32 *__restr
 		const i32 kf = find_block(fragbase, nfb, w0), kl = find_block(fragbase, nfb, w1 - 1);
 		const bool straddle = kf != kl;
 		if (!straddle && kf != cur) { flush(); cur = kf; }
-		// a record's contribution: into the running sums, or -- on a tile with a block edge inside -- straight to its block
-		auto add = [&](i64 i, i32 L, i32 score) {
-			if (!straddle) { l_acc += L; sc_acc += score; }
-			else { const i32 b = find_block(fragbase, nfb, i); if (L) atomicAdd(&bl_len[b], L); if (score) atomicAdd(&bl_score[b], score); }
-		};
-		if (tid == 0) s_n = 0;
-		__syncthreads();
-		{
-			const i64 i = w0 + tid;
-			if (i < nf) {
-				const i32 t = ftype[i];
-				const i32 fj = fjob[i];
-				const i32 Lr = t == FT_DP ? ((fj < 0 || jlarge[fj]) ? -1 : nops[fj]) : alen[i];       // -1: a large DP job, written after the striped kernel
-				if (t == FT_SEED) { const i32 l = frag[i].qlen; add(i, l, l); }
-				else if (Lr < 0) { }
-				else if (Lr > MAT_SERIAL) s_list[atomicAdd(&s_n, 1)] = tid;
-				else {
-					const gsa_frag f = frag[i];
-					const i64 o = aoff[i]; const i32 L = Lr;
-					const uint8_t *qs = query + f.qpos, *rs = ref + f.rpos;
-					i32 score = 0;
-					// All the loads of a record first, then its stores: the string pools are byte pointers like the sources, so a store in
-					// between holds every later load back until it is through -- 32 dependent round trips per record where two will do.
-					uint8_t a1[MAT_SERIAL], a2[MAT_SERIAL];
-					if (t == FT_DP) {
-						// ops are forward M/D/I; 'D' puts '-' into aln1, 'I' into aln2 (ksw2_alignment.cpp:264-272)
-						const uint8_t *op = ops + opsoff[fj];
-						uint8_t ch[MAT_SERIAL];
-#pragma unroll
-						for (i32 p = 0; p < MAT_SERIAL; p++) ch[p] = p < L ? op[p] : (uint8_t)0;
-						i32 i1 = 0, i2 = 0;
-#pragma unroll
-						for (i32 p = 0; p < MAT_SERIAL; p++) {
-							const bool c1 = ch[p] == 'M' || ch[p] == 'I', c2 = ch[p] == 'M' || ch[p] == 'D';
-							a1[p] = c1 ? rs[i1] : (uint8_t)'-'; a2[p] = c2 ? qs[i2] : (uint8_t)'-';
-							i1 += c1; i2 += c2;
-						}
-#pragma unroll
-						for (i32 p = 0; p < MAT_SERIAL; p++) if (p < L) score += (gsa_nt4(a1[p]) == gsa_nt4(a2[p]));             // CountIdenticalPairs (:38-47)
-					} else {
-#pragma unroll
-						for (i32 p = 0; p < MAT_SERIAL; p++) {
-							a1[p] = (t != FT_INS && p < L) ? rs[p] : (uint8_t)'-';
-							a2[p] = (t != FT_DEL && p < L) ? qs[p] : (uint8_t)'-';
-						}
-						if (t == FT_EQ) score = f.qlen - fmism[i];
+		// ---- the tile's descriptors: record w0 + tid.  Everything that does not hang on the job number is loaded at once, for seeds and large
+		// jobs too (they need only ftype, fjob and qlen): no load waits for the record's kind.  These loads are what bounds the kernel now
+		// (DESIGN.md section 6); keeping the seed lanes out of alen / aoff / fmism / rpos -- half the lanes -- is the next saving, at the price of a
+		// second round trip for the gaps.  (nops / opsoff of a large job are read and dropped: the striped kernel may still be writing them.) ----
+		const i64 i = w0 + tid, ic = i < nf ? i : nf - 1;
+		const i32 t = ftype[ic], fj = fjob[ic], al = alen[ic], fm = fmism[ic], qpos = frag[ic].qpos, qlen = frag[ic].qlen;
+		const i64 rpos = frag[ic].rpos, ao = aoff[ic];
+		i32 L = 0, cl = 0, sc = 0;                      // string columns to write here; the record's (aln_len, score) as far as known before the columns
+		i64 oo = 0;
+		if (i < nf) {
+			if (t == FT_SEED) { cl = qlen; sc = qlen; }
+			else if (t == FT_DP) { if (fj >= 0) { const i32 lg = jlarge[fj], no = nops[fj]; oo = opsoff[fj]; if (!lg) L = no; } }      // (a large DP job: written after the striped kernel, counts as zero here)
+			else { L = al; if (t == FT_EQ) sc = qlen - fm; }
+			if (L < 0) L = 0;
+			if (t != FT_SEED) cl = L;
+		}
+		s_kind[tid] = t; s_qpos[tid] = qpos; s_rpos[tid] = rpos; s_aoff[tid] = ao; s_ops[tid] = oo; s_score[tid] = sc;
+		tile_scan(L, s_start, s_wsum);
+		// ---- the columns: a contiguous share of the chunks per wavefront, so the carry of a DP record runs from chunk to chunk ----
+		const i32 T = s_start[256], nch = (T + 63) >> 6, cw = (nch + 3) >> 2;
+		const i32 c_beg = wv * cw, c_end = c_beg + cw < nch ? c_beg + cw : nch;
+		i32 car1 = 0, car2 = 0;                         // reference / query bases the record of lane 0 consumed in front of the chunk
+		for (i32 ch = c_beg; ch < c_end; ch++) {
+			const i32 col = (ch << 6) + lane; const bool act = col < T;
+			const int r = tile_find(s_start, act ? col : T - 1);
+			const i32 p = col - s_start[r], kind = s_kind[r];
+			const bool dp = act && kind == FT_DP;
+			const uint8_t *op = ops + s_ops[r], *rs = ref + s_rpos[r], *qs = query + s_qpos[r];
+			if (ch == c_beg) {
+				// the share begins inside a DP record: count what the ops in front of it consumed (a small job has at most 129 ops)
+				const i32 p0 = __builtin_amdgcn_readfirstlane(p), k0 = __builtin_amdgcn_readfirstlane(kind);
+				if (k0 == FT_DP && p0 > 0) {
+					const uint8_t *op0 = ops + s_ops[__builtin_amdgcn_readfirstlane(r)];
+					for (i32 b = 0; b < p0; b += 64) {
+						const uint8_t x = b + lane < p0 ? op0[b + lane] : (uint8_t)0;
+						car1 += __popcll(__ballot(x == 'M' || x == 'I')); car2 += __popcll(__ballot(x == 'M' || x == 'D'));
 					}
-#pragma unroll
-					for (i32 p = 0; p < MAT_SERIAL; p++) if (p < L) { aln1[o + p] = a1[p]; aln2[o + p] = a2[p]; }
-					add(i, L, score);
 				}
 			}
+			// ops are forward M/D/I; 'D' puts '-' into aln1, 'I' into aln2 (ksw2_alignment.cpp:264-272)
+			const uint8_t x = dp ? op[p] : (uint8_t)0;
+			const bool d1 = dp && (x == 'M' || x == 'I'), d2 = dp && (x == 'M' || x == 'D');
+			const u64 sm = seg_mask(p, lane), b1 = __ballot(d1), b2 = __ballot(d2);
+			const bool cont = p > lane;                 // the record began in front of this chunk
+			const i32 n1 = __popcll(b1 & sm) + (cont ? car1 : 0), n2 = __popcll(b2 & sm) + (cont ? car2 : 0);
+			const bool c1 = dp ? d1 : (act && kind != FT_INS), c2 = dp ? d2 : (act && kind != FT_DEL);
+			uint8_t a1 = '-', a2 = '-';
+			if (c1) a1 = rs[dp ? n1 - 1 : p];
+			if (c2) a2 = qs[dp ? n2 - 1 : p];
+			if (act) { const i64 o = s_aoff[r] + p; aln1[o] = a1; aln2[o] = a2; }
+			const u64 bm = __ballot(dp && gsa_nt4(a1) == gsa_nt4(a2));             // CountIdenticalPairs (:38-47)
+			if (dp && (lane == 63 || col + 1 == s_start[r + 1])) { const i32 m = __popcll(bm & sm); if (m) atomicAdd(&s_score[r], m); }
+			car1 = __builtin_amdgcn_readlane(n1, 63); car2 = __builtin_amdgcn_readlane(n2, 63);
 		}
 		__syncthreads();
-		const int nlist = s_n;
-		for (int g = wv; g < nlist; g += 4) {
-			const i64 i = w0 + s_list[g];
-			const i32 t = ftype[i];
-			const gsa_frag f = frag[i];
-			const i64 o = aoff[i]; const i32 L = t == FT_DP ? nops[fjob[i]] : alen[i];
-			const uint8_t *qs = query + f.qpos, *rs = ref + f.rpos;
-			i32 score = 0;
-			if (t == FT_DEL) { for (i32 p = lane; p < L; p += 64) { aln1[o + p] = rs[p]; aln2[o + p] = '-'; } }
-			else if (t == FT_INS) { for (i32 p = lane; p < L; p += 64) { aln1[o + p] = '-'; aln2[o + p] = qs[p]; } }
-			else if (t == FT_EQ) { for (i32 p = lane; p < L; p += 64) { aln1[o + p] = rs[p]; aln2[o + p] = qs[p]; } score = f.qlen - fmism[i]; }
-			else {
-				const uint8_t *op = ops + opsoff[fjob[i]];
-				i32 i1 = 0, i2 = 0;                      // consumed bases of the reference / query fragment so far
-				for (i32 base = 0; base < L; base += 64) {
-					const i32 p = base + lane;
-					const uint8_t ch = p < L ? op[p] : 0;
-					const int c1 = (ch == 'M' || ch == 'I') ? 1 : 0, c2 = (ch == 'M' || ch == 'D') ? 1 : 0;
-					int s1 = c1, s2 = c2;                 // inclusive wave prefix sums
-					for (int d = 1; d < 64; d <<= 1) { int a = __shfl_up(s1, d), b = __shfl_up(s2, d); if (lane >= d) { s1 += a; s2 += b; } }
-					if (p < L) {
-						const uint8_t a1 = c1 ? rs[i1 + s1 - 1] : '-', a2 = c2 ? qs[i2 + s2 - 1] : '-';
-						aln1[o + p] = a1; aln2[o + p] = a2;
-						score += (gsa_nt4(a1) == gsa_nt4(a2));
-					}
-					i1 += __shfl(s1, 63); i2 += __shfl(s2, 63);
-				}
-				for (int d = 32; d; d >>= 1) score += __shfl_xor(score, d);
-			}
-			if (lane == 0) add(i, L, score);
+		// ---- a record's contribution: into the running sums, or -- on a tile with a block edge inside -- straight to its block ----
+		if (i < nf) {
+			const i32 score = s_score[tid];
+			if (!straddle) { l_acc += cl; sc_acc += score; }
+			else if (cl | score) { const i32 b = find_block(fragbase, nfb, i); if (cl) atomicAdd(&bl_len[b], cl); if (score) atomicAdd(&bl_score[b], score); }
 		}
-		__syncthreads();      // (s_list / s_n are reused by the next tile)
+		__syncthreads();      // (the descriptors in LDS are replaced by the next tile's)
 	}
 	flush();
 }
