@@ -93,8 +93,9 @@ template struct RawArr<char>;
 template struct RawArr<gsa_variant>;
 template struct RawArr<gsa_block_cigar>;
 template struct RawArr<uint32_t>;
-void ContigResult::assign(const gsa_result &r)
+void ContigResult::assign(const gsa_result &r, bool summary_mode)
 {
+	summary = summary_mode;
 	blocks.assign(r.blocks, r.blocks + r.n_blocks);
 	recs.assign(r.recs, (size_t)r.n_frags);
 	aln1.assign(r.aln1, (size_t)r.n_aln); aln2.assign(r.aln2, (size_t)r.n_aln);
@@ -383,19 +384,21 @@ void gsah_cigar_trim(const uint32_t *ops, int bdir, int64_t ext, std::vector<uin
 void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink) const
 {
 	std::vector<gsa_block_cigar> own_blk; std::vector<uint32_t> own_ops, cut;
+	if (!blk && r.summary) return;      // (the comparator walks records and strings a summary result does not hold)
 	if (!blk) { gsah_block_cigars(q.seq.data(), r, own_blk, own_ops); blk = own_blk.data(); ops = own_ops.data(); }
 	OutBuf o;
 	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
 		gsa_block &b = r.blocks[bi];
 		if (!allow_dup && b.bdup) continue;
 		if (b.n_frag <= 0) continue;
-		const int64_t f0 = b.frag_off;
-		gsa_frag last = r.frag(f0 + b.n_frag - 1);
+		// the block's first and last record: where frag_off / n_frag say, or -- summary mode -- the block's two ends
+		const int64_t f0 = r.summary ? 2 * (int64_t)bi : b.frag_off, fl = r.summary ? 2 * (int64_t)bi + 1 : b.frag_off + b.n_frag - 1;
+		gsa_frag last = r.frag(fl);
 		const int ext = extension(*idx, b, last);
 		gsa_block_cigar bc = blk[bi];
 		const uint32_t *bo = ops + bc.cig_off;
 		if (ext > 0) {      // (as maf_block: the block and its last record are shortened for whoever looks at them next -- the variant walk, the dot plot)
-			b.aln_len -= ext; b.score -= ext; last.rlen -= ext; last.qlen -= ext; r.trim(f0 + b.n_frag - 1, ext);
+			b.aln_len -= ext; b.score -= ext; last.rlen -= ext; last.qlen -= ext; r.trim(fl, ext);
 			gsah_cigar_trim(bo, b.bdir, ext, cut, bc); bo = cut.data();
 		}
 		const long long cols = (long long)bc.n_eq + bc.n_x + bc.n_ins + bc.n_del;

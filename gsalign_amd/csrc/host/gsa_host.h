@@ -84,7 +84,8 @@ struct ContigResult {
 	std::vector<gsa_block> blocks;
 	RawArr<gsa_rec> recs;                  // the 16-byte records as they arrived; frag(i) is record i as a FragPair_t
 	RawArr<char> aln1, aln2;
-	void assign(const gsa_result &r);      // the copies only: what a GPU worker thread does inside the result callback
+	bool summary = false;                  // a summary result: recs = the block ends, recs[2b] / recs[2b + 1] the first / last record of block b; no strings
+	void assign(const gsa_result &r, bool summary_mode = false);      // the copies only: what a GPU worker thread does inside the result callback (aln1 == NULL with n_aln == 0 is fine)
 	gsa_frag frag(int64_t i) const { gsa_frag f; gsa_rec_expand(recs.data(), i, &f); return f; }
 	void trim(int64_t i, int ext);         // iExtension (tools.cpp:192-202): record i loses its last `ext` bases
 };
@@ -119,7 +120,8 @@ struct Emitter {
 	void maf_text(bool first, const QueryContig &q, ContigResult &r, const std::function<void(OutBuf &&)> &sink, const std::function<OutBuf(size_t)> &take) const;
 	void maf_block(const QueryContig &q, ContigResult &r, gsa_block &b, OutBuf &small, const std::function<void(OutBuf &&)> &sink, const std::function<OutBuf(size_t)> &take) const;
 	// PAF: one line per block with its cg:Z: CIGAR, blocks selected and trimmed (iExtension) like OutputMAF's; blk / ops = the contig's CIGARs from gsa_block_cigars,
-	// or NULL: computed here (gsah_block_cigars).  Shortens the last record of a block exactly as maf_block does.
+	// or NULL: computed here (gsah_block_cigars).  Shortens the last record of a block exactly as maf_block does.  A summary result (ContigResult::summary) must
+	// bring its CIGARs: the first and last record of block bi are recs[2 bi] and recs[2 bi + 1], and no string is touched.
 	void paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink) const;
 	void paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops) const;
 	// OutputAlignment (tools.cpp:222-286)

@@ -131,6 +131,40 @@ int gsah_c_emit_fmt(const char *index_prefix, const char *query_fa, const char *
 	return 0;
 }
 
+// PAF from SUMMARY results (ContigResult::summary): per contig the callback supplies the FULL result; its CIGARs come from the host comparator and its
+// block ends (first and last record of every block, as they lie in the full result) are taken out of it, and the PAF is then formatted from a ContigResult that holds only
+// the blocks and those ends.  No VCF: the host variant walk needs the strings.
+int gsah_c_emit_summary(const char *index_prefix, const char *query_fa, const char *paf_path, int allow_dup, gsah_result_cb cb, void *user, char *err)
+{
+	std::string e; HostIndex idx; std::vector<QueryContig> qs;
+	if (!gsah_load_index(index_prefix, idx, e) || !gsah_load_query(query_fa, qs, e)) { if (err) { strncpy(err, e.c_str(), 255); err[255] = 0; } return -1; }
+	Emitter em; em.idx = &idx; em.allow_dup = allow_dup != 0;
+	for (size_t ci = 0; ci < qs.size(); ci++) {
+		gsa_result res; memset(&res, 0, sizeof(res));
+		if (cb(user, (int)ci, qs[ci].seq.data(), (int)qs[ci].seq.size(), &res) != 0) { if (err) strcpy(err, "result callback failed"); return -2; }
+		if (res.n_blocks == 0) continue;
+		std::vector<gsa_block_cigar> cb_blk; std::vector<uint32_t> cb_ops;
+		std::vector<gsa_rec> ends((size_t)2 * (size_t)res.n_blocks);
+		{
+			ContigResult full; full.assign(res);
+			gsah_block_cigars(qs[ci].seq.data(), full, cb_blk, cb_ops);
+			for (int32_t b = 0; b < res.n_blocks; b++) {
+				const gsa_block &bl = res.blocks[b];
+				if (bl.n_frag <= 0) { memset(&ends[2 * (size_t)b], 0, 2 * sizeof(gsa_rec)); continue; }
+				ends[2 * (size_t)b] = res.recs[bl.frag_off]; ends[2 * (size_t)b + 1] = res.recs[bl.frag_off + bl.n_frag - 1];
+			}
+		}
+		gsa_result sum; memset(&sum, 0, sizeof(sum));
+		sum.n_blocks = res.n_blocks; sum.blocks = res.blocks; sum.n_frags = (int64_t)ends.size(); sum.recs = ends.data();      // n_aln = 0, aln1 = aln2 = NULL
+		ContigResult cr; cr.assign(sum, true);
+		FILE *fp = fopen(paf_path, ci == 0 ? "w" : "a");
+		if (!fp) { if (err) strcpy(err, "cannot open PAF output"); return -3; }
+		em.paf(fp, qs[ci], cr, cb_blk.data(), cb_ops.data());
+		fclose(fp);
+	}
+	return 0;
+}
+
 // VariantIdentification (SeqVariant.cpp:12-119) of one finished contig as gsa_variant records, on the host: the records gsa_call_variants gives, in the same
 // order.  out[cap]; returns the number of variants (call with cap = 0 to size `out`), < 0 on error.  counts = {SNVs, insertions, deletions}.  `seq` is not read: the
 // records address the alleles (gsa_variant_alleles).  The index of the last prefix stays loaded, behind a lock: calls from several threads take turns.

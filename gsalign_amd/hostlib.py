@@ -97,9 +97,13 @@ def result_from_dump(d: dict, keep: list):
     return r
 
 
-def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, reference_label: str, per_contig, allow_dup: bool = True, fmt: int = 1) -> None:
-    """per_contig(ci, seq_uint8) -> dump dict of the finished contig (stage 8 layout).  fmt 1 = MAF, 2 = ALN, 3 = PAF with the host comparator's CIGARs (written to maf_path)."""
+def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, reference_label: str, per_contig, allow_dup: bool = True, fmt: int = 1, summary: bool = False) -> None:
+    """per_contig(ci, seq_uint8) -> dump dict of the finished contig (stage 8 layout).  fmt 1 = MAF, 2 = ALN, 3 = PAF with the host comparator's CIGARs (written to maf_path).
+    summary=True (fmt 3 only; gsah_c_emit_summary): the PAF is formatted from a summary result -- blocks and block ends, taken out of the full dump, with the
+    comparator's CIGARs -- and no VCF is written (vcf_path is not opened)."""
     keep: list = []
+    if summary and fmt != 3:
+        raise ValueError("summary=True formats PAF only (fmt=3)")
 
     def cb(user, ci, seq, ln, out):
         s = np.frombuffer(C.string_at(seq, ln), dtype=np.uint8)
@@ -108,6 +112,11 @@ def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, referen
         return 0
 
     err = C.create_string_buffer(256)
+    if summary:
+        rc = load().gsah_c_emit_summary(index_prefix.encode(), query_fa.encode(), maf_path.encode(), 1 if allow_dup else 0, RESULT_CB(cb), None, err)
+        if rc != 0:
+            raise RuntimeError(f"gsah_c_emit_summary -> {rc}: {err.value.decode()}")
+        return
     rc = load().gsah_c_emit_fmt(index_prefix.encode(), query_fa.encode(), maf_path.encode(), vcf_path.encode(), reference_label.encode(),
                                 1 if allow_dup else 0, fmt, RESULT_CB(cb), None, err)
     if rc != 0:
