@@ -298,7 +298,7 @@ int gsa_create_opts(int device, const gsa_index_view *idx, const gsa_params *prm
 }
 
 // every device buffer a context can own (gsa_destroy frees them; gsa_debug_buffers lists them)
-#define GSA_DEVBUFS(X) X(d_bwt) X(d_bwt_ref) X(d_occ_base) X(d_sa) X(d_ref) X(d_chr_end) X(d_chr_of_end) X(qs[0].d_query) X(qs[1].d_query) X(qs[0].d_bndtab) X(qs[1].d_bndtab) X(tmp) X(d_cnt) X(d_zero) X(d_mail) X(d_lb_status[0]) X(d_lb_status[1]) X(d_sa_dense) X(d_kmer) X(d_kmer_lo) X(d_pres) X(d_ref2) X(d_cand_s) X(d_cand_len) X(d_cand_x0) X(d_cand_freq) X(d_onpath) X(d_cand_cnt) X(d_heavy) X(dn_lf) X(dn_x0) X(d_chunk_hits) X(d_chunk_base) X(d_key_a) X(d_key_b) X(d_val_a) X(d_val_b) X(s_q) X(s_len) X(s_r) X(s_gid) X(d_flag) X(d_scan) X(g_beg) X(w_j0) X(d_pdbm) X(d_pdby) X(d_pdcb) X(d_gpre) X(d_key_c) X(d_val_c) X(a_q) X(a_len) X(a_r) X(a_gb) X(a_ge) X(a_uniq) X(a_cu) X(a_alive) X(a_ws) X(a_wid) X(a_next) X(a_brk) X(a_aurank) X(a_aulist) X(a_runinfo) X(w_best) X(w_sum) X(w_n) X(d_btab) X(d_flag2) X(d_scan2) X(d_i64a) X(b_q) X(b_len) X(b_r) X(b_gb) X(b_ge) X(c_q) X(c_len) X(c_r) X(c_gb) X(c_ge) X(c_bid) X(blk_beg) X(blk_end) X(blk_score) X(r_q) X(r_len) X(r_r) X(r_bid) X(r_tmp_q) X(r_tmp_len) X(r_tmp_r) X(r_tmp_bid) X(r_cut4) X(r_cut5) X(r_simjob) X(r_simres) X(d_leaf) X(fb_seedbase) X(fb_sbeg) X(fb_fragbase) X(f_rec) X(f_rec16) X(f_type) X(f_mism) X(f_alnlen) X(f_job) X(f_score) X(d_dp_tiny) X(d_dp_bnd) X(d_dp_ctr) X(d_dp_jobs) X(d_dp_large) X(d_tail) X(e_id) X(e_rec) X(e_list) X(e_off1) X(e_off2) X(e_opsoff) X(e_nops) X(e_ops) X(e_rev) X(r_head) X(f_early) X(r_orig) X(r_tmp_orig) X(j_frag) X(j_opsoff) X(j_nops) X(d_ops) X(j_cells) X(d_alnoff) X(bl_alnlen) X(bl_score) X(d_bblk) X(d_dp_arena) X(d_vblk) X(d_vcnt) X(d_vwg) X(d_var) X(d_cblk) X(d_cout) X(d_ccnt) X(d_cwg) X(d_cpre) X(d_crun) X(d_cops) X(leaf[0]) X(leaf[1]) X(leaf[2]) X(leaf[3]) X(leaf[4]) X(leaf[5]) X(leaf[6]) X(leaf[7]) X(leaf[8])
+#define GSA_DEVBUFS(X) X(d_bwt) X(d_bwt_ref) X(d_occ_base) X(d_sa) X(d_ref) X(d_chr_end) X(d_chr_of_end) X(qs[0].d_query) X(qs[1].d_query) X(qs[0].d_bndtab) X(qs[1].d_bndtab) X(tmp) X(d_cnt) X(d_zero) X(d_mail) X(d_lb_status[0]) X(d_lb_status[1]) X(d_sa_dense) X(d_kmer) X(d_kmer_lo) X(d_pres) X(d_ref2) X(d_cand_s) X(d_cand_len) X(d_cand_x0) X(d_cand_freq) X(d_onpath) X(d_cand_cnt) X(d_heavy) X(dn_lf) X(dn_x0) X(d_chunk_hits) X(d_chunk_base) X(d_key_a) X(d_key_b) X(d_val_a) X(d_val_b) X(s_q) X(s_len) X(s_r) X(s_gid) X(d_flag) X(d_scan) X(g_beg) X(w_j0) X(d_pdbm) X(d_pdby) X(d_pdcb) X(d_gpre) X(d_key_c) X(d_val_c) X(a_q) X(a_len) X(a_r) X(a_gb) X(a_ge) X(a_uniq) X(a_cu) X(a_alive) X(a_ws) X(a_wid) X(a_next) X(a_brk) X(a_aurank) X(a_aulist) X(a_runinfo) X(w_best) X(w_sum) X(w_n) X(d_btab) X(d_flag2) X(d_scan2) X(d_i64a) X(b_q) X(b_len) X(b_r) X(b_gb) X(b_ge) X(c_q) X(c_len) X(c_r) X(c_gb) X(c_ge) X(c_bid) X(blk_beg) X(blk_end) X(blk_score) X(r_q) X(r_len) X(r_r) X(r_bid) X(r_tmp_q) X(r_tmp_len) X(r_tmp_r) X(r_tmp_bid) X(r_cut4) X(r_cut5) X(r_simjob) X(r_simres) X(d_leaf) X(fb_seedbase) X(fb_sbeg) X(fb_fragbase) X(f_rec) X(f_rec16) X(f_type) X(f_mism) X(f_alnlen) X(f_job) X(f_score) X(d_dp_lane_order) X(d_dp_bnd) X(d_dp_ctr) X(d_dp_jobs) X(d_dp_large) X(d_tail) X(e_id) X(e_rec) X(e_list) X(e_off1) X(e_off2) X(e_opsoff) X(e_nops) X(e_ops) X(e_rev) X(r_head) X(f_early) X(r_orig) X(r_tmp_orig) X(j_frag) X(j_opsoff) X(j_nops) X(d_ops) X(j_cells) X(d_alnoff) X(bl_alnlen) X(bl_score) X(d_bblk) X(d_dp_arena) X(d_vblk) X(d_vcnt) X(d_vwg) X(d_var) X(d_cblk) X(d_cout) X(d_ccnt) X(d_cwg) X(d_cpre) X(d_crun) X(d_cops) X(leaf[0]) X(leaf[1]) X(leaf[2]) X(leaf[3]) X(leaf[4]) X(leaf[5]) X(leaf[6]) X(leaf[7]) X(leaf[8])
 void gsa_destroy(gsa_ctx *c)
 {
 	if (!c) return;
@@ -504,14 +504,12 @@ int gsa_set_option(gsa_ctx *c, const char *name, int64_t value)
 	else if (k == "bundle_contig") { if (!in(0, BIG)) return gsa_fail(c, GSA_ERR_ARG, "bundle_contig: 0 (no bundles) .. 2^40 bases"); c->opt.bundle_contig = value; }
 	else if (k == "bundle_cap") { if (!in(1, BIG)) return gsa_fail(c, GSA_ERR_ARG, "bundle_cap: 1 .. 2^40 bases"); c->opt.bundle_cap = value; }
 	else if (k == "seed_budget") { if (!in(1, 0xffffffffll)) return gsa_fail(c, GSA_ERR_ARG, "seed_budget: 1 .. 2^32 - 1 wave-iterations"); c->seed_budget = (u32)value; }
-	else if (k == "dp_lane") { if (!in(0, 1 << 20)) return gsa_fail(c, GSA_ERR_ARG, "dp_lane: 0 (round 2's tiny / small split) .. 2^20 cells"); c->opt.dp_lane = (int)value; }
+	else if (k == "dp_lane") { if (!in(0, 1 << 20)) return gsa_fail(c, GSA_ERR_ARG, "dp_lane: 0 (no lane class: one per wavefront) .. 2^20 cells"); c->opt.dp_lane = (int)value; }
 	else if (k == "seed_mode") { if (value < 0 || value > 2) return gsa_fail(c, GSA_ERR_ARG, "seed_mode: 0 sweep, 1 speculative, 2 search"); c->opt.seed_mode = (int)value; }
 	else if (k == "seed_lhop") { if (value != 0 && (!in(16, 1 << 16) || (value & (value - 1)))) return gsa_fail(c, GSA_ERR_ARG, "seed_lhop: 0 or a power of two >= 16"); c->opt.seed_lhop = (int)value; }    // (test hook: a smaller long-hop table)
 	else if (k == "pd_bitmap") c->opt.pd_bitmap = value != 0;
 	else if (k == "dp_side") c->opt.dp_side = value != 0;
-	else if (k == "dp_small_side") c->opt.dp_small_side = value != 0;
 	else if (k == "pd_two_level_min") { if (!in(0, BIG)) return gsa_fail(c, GSA_ERR_ARG, "pd_two_level_min: >= 0 blocks"); c->opt.pd_two_level_min = value; }
-	else if (k == "dp_occupancy") { if (!in(0, 16)) return gsa_fail(c, GSA_ERR_ARG, "dp_occupancy: 0 (off) .. 16 workgroups per CU"); c->opt.dp_occupancy = (int)value; }
 	else if (k == "pd_bytes") { if (!in(0, 2)) return gsa_fail(c, GSA_ERR_ARG, "pd_bytes: 0 never, 1 by the hit count, 2 always"); c->opt.pd_bytes = (int)value; }
 	else if (k == "pres_from_kmer") c->opt.pres_from_kmer = value != 0;      // (takes effect at the next gsa_set_params that rebuilds the table)
 	else if (k == "walk_chain_min") { if (!in(0, BIG)) return gsa_fail(c, GSA_ERR_ARG, "walk_chain_min: >= 0 seeds"); c->opt.walk_chain_min = value; }

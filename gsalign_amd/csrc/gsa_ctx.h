@@ -24,7 +24,7 @@ struct Leaf {
 
 // Device "mailbox" (i32[MAIL_N]) of the counts the stages produce; the host reads the whole
 // box in ONE pinned copy where it needs them instead of one read-back per count.
-enum { M_NB = 0, M_NC = 1, M_NBLK = 2, M_NG = 3, M_NR = 4, M_NJ = 5, M_NL = 6, M_LBERR = 7, M_ANY = 8, M_NTINY = 40, M_TICKET = 48, M_NBRAW = 49, M_NR2 = 50, M_NF = 51, M_NJOB = 52, M_OPSTOT = 53, M_NALN = 54, M_DPERR = 64, M_NLARGE = 65, M_DPERR2 = 66, M_CELLS = 68 /* two u64: sum m*n, sum m+n */ /* 64..71: cleared together, one aligned 32-byte fill */, M_DPERR3 = 41, M_LBDONE = 42, M_LFSTEPS = 44 /* u64, accounting build */, M_NEARLY = 62, M_EOPS = 63, M_NTOUCH = 46 /* touched PosDiff-bitmap blocks (OpPdTouched) */, M_MAXBLK = 56 /* u64 {score, number} of the best-scoring stage-2 block */, MAIL_N = 72 };
+enum { M_NB = 0, M_NC = 1, M_NBLK = 2, M_NG = 3, M_NR = 4, M_NJ = 5, M_NL = 6, M_LBERR = 7, M_ANY = 8, M_NLANE = 40, M_TICKET = 48, M_NBRAW = 49, M_NR2 = 50, M_NF = 51, M_NJOB = 52, M_OPSTOT = 53, M_NALN = 54, M_DPERR = 64, M_NLARGE = 65, M_DPERR2 = 66, M_CELLS = 68 /* two u64: sum m*n, sum m+n */ /* 64..71: cleared together, one aligned 32-byte fill */, M_DPERR3 = 41, M_LBDONE = 42, M_LFSTEPS = 44 /* u64, accounting build */, M_NEARLY = 62, M_EOPS = 63, M_NTOUCH = 46 /* touched PosDiff-bitmap blocks (OpPdTouched) */, M_MAXBLK = 56 /* u64 {score, number} of the best-scoring stage-2 block */, MAIL_N = 72 };
 #define LEAF_CHUNK 1024      // leaves copied together with the mailbox (more -> a second copy)
 
 struct HostBlock {       // one entry of the reference's AlnBlockVec, as leaf range
@@ -75,16 +75,14 @@ struct Options {
 	int64_t split_min = 20000000;      // gsa_align_many: a contig of at least this many bases may be seeded by chunk range on several contexts
 	int64_t bundle_contig = 16000000;  // ... contigs up to this length travel in bundles (0: never)
 	int64_t bundle_cap = 64000000;     // ... of about this many bases at most
-	int dp_lane = 512;                 // alignments of at most this many cells go one per lane (k_dp_lane); 0: round 2's tiny / small split
+	int dp_lane = 512;                 // alignments of at most this many cells go one per lane (k_dp_lane); 0: no lane class, every job below the striped kernel runs one per wavefront (k_dp_small)
 	int seed_lhop = 0;                 // (test hook) entries of the seed kernel's long-hop table a chunk may use: a power of two below LHOP_N; 0 = all of them
 	int seed_mode = 1;                 // 0 sweep: every chunk through k_dense_sweep; 1: the speculative kernel + dense kernels for what it gives up on; 2: round 2's k_dense_search in place of the sweep
 	int pd_bitmap = 1;                 // 0: groups by the PosDiff sort although MaxIndelSize <= 31 would allow the bitmap scan
 	int sweep_shape = -1;              // k_dense_sweep's launch shape: -1 by the number of dense chunks, 0 = four chunks per two-wave workgroup / 160-start segments, 1 = one chunk per four-wave workgroup / 40-start segments
-	int dp_small_side = 0;             // 1: k_dp_small on a stream of its own (stream_aux[3]) so that the late striped launch starts beside it instead of behind it on the caller's stream (experiment; results do not depend on it)
 	int dp_side = 0;                   // 1: the striped DP's lower size class on a stream of its own, beside the upper class (0: behind it)
 	int64_t walk_chain_min = 100000;   // contigs with more seeds than this walk their window chain in slices (k_walk_chain) instead of one workgroup's LDS (k_walk_windows); tests: 0
 	int64_t pd_two_level_min = 2000000;   // PosDiff bitmaps of more blocks than this (a reference above ~1 Gbp) are scanned in two passes: list the touched blocks, count those (tests: 0)
-	int dp_occupancy = 0;              // > 0: at most this many striped-DP workgroups per CU (LDS padding): leaves wave slots for the passes beside it (experiment; 0 = off)
 	int pd_bytes = 1;                  // the PosDiff bitmap of a contig (bundle) whose hits scatter (-sen: thousands of chance hits per chunk) is filled through a byte per value, plain stores, and packed
 	                                   // afterwards -- no device-scope atomics (k_pd_pack, k_seed_select.hip); 1 = when the hit count says so, 0 = never, 2 = always (tests)
 	int pres_from_kmer = 1;            // the presence table is derived from the k-mer jump table when both hold k-mers of one length (0: always from a scan of the text; a test compares the two)
@@ -214,7 +212,7 @@ struct gsa_ctx {
 	DevBuf f_rec16;                                // the same as 16-byte gsa_rec: what goes to the host
 	DevBuf f_type, f_mism, f_alnlen, f_job, f_score;
 	DevBuf j_frag, j_opsoff, j_nops, d_ops, j_cells;
-	DevBuf d_dp_tiny;                              // order array of the four-per-wavefront DP kernel
+	DevBuf d_dp_lane_order;                        // k_dp_lane: its order array (the jobs of the one-per-lane class)
 	DevBuf d_dp_arena;                             // k_dp_lane: direction nibbles of the alignments in flight (per-wave regions)
 	DevBuf d_dp_bnd, d_dp_ctr, d_dp_jobs, d_dp_large;   // striped DP: boundary granules, tickets, job descriptors, (job,m,n) of the large jobs
 	// large DP gaps are known once the leaf table exists: they are launched there (stream_aux[0]) and run under stages 6-7
@@ -313,7 +311,9 @@ int ctx_create_bare(int device, gsa_ctx **out);            // gsa_api.hip  (a co
 int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds);   // k_index.hip  (suffix sort + BWT / Occ / SA samples of forward + reverse complement)
 struct LgJob { i32 job, m, n; };
 int launch_stripes(gsa_ctx *c, hipStream_t ss, std::vector<LgJob> &large, const uint8_t *pool1, const i64 *off1, const uint8_t *pool2, const i64 *off2,
-                   uint8_t *ops, const i64 *ops_off, i32 *ops_len, uint8_t *rev, int err_slot);   // k_dp.hip
+                   uint8_t *ops, const i64 *ops_off, i32 *ops_len, uint8_t *rev, int err_slot);   // k_dp_stripe.hip
+int launch_small_dp(gsa_ctx *c, hipStream_t st, i32 nlane, const i32 *order_lane, i32 nsmall, const i32 *order_small, const uint8_t *pool1, const i64 *off1, const i32 *len1,
+                    const uint8_t *pool2, const i64 *off2, const i32 *len2, uint8_t *ops, const i64 *ops_off, i32 *ops_len, const i32 *jfrag, gsa_frag *frag);   // k_dp_small.hip  (k_dp_lane + k_dp_small beside `st`; ev[12] marks their end)
 struct Ksw2Launch { i32 n = 0, nsmall = 0, nlarge = 0; bool small_in_flight = false; };      // what run_ksw2_jobs left running
 int run_ksw2_jobs(gsa_ctx *c, i32 n_ub, const uint8_t *pool1, const i64 *off1, const i32 *len1,
                   const uint8_t *pool2, const i64 *off2, const i32 *len2, uint8_t *ops, const i64 *ops_off, i32 *ops_len, i64 ops_total, Ksw2Launch *out,

@@ -32,24 +32,13 @@ __device__ __forceinline__ int dp_cell(int xt1, int vt1, int ut, int yt, int a_,
 	return d;
 }
 
-// the traceback automaton (ksw_backtrack :25-68); with the full band the force_state paths never fire
-__device__ __forceinline__ int dp_bt_step(u32 tmp, int &state, int &i, int &j)
+// the traceback automaton (ksw_backtrack :38-52), branch-free: the state after a cell (0: M, 1: D, 2: I), given
+// the state before it and the cell's flag byte; with the full band the force_state paths never fire
+__device__ __forceinline__ int dp_bt_next(int state, u32 flags)
 {
-	if (state == 0) state = tmp & 7;
-	else if (!((tmp >> (state + 2)) & 1)) state = 0;
-	if (state == 0) state = tmp & 7;
-	if (state == 0) { --i; --j; return 'M'; }
-	if (state == 1 || state == 3) { --i; return 'D'; }
-	--j; return 'I';
-}
-
-// number of cells on diagonals < r of an m x n problem (diagonal-major direction matrix)
-__device__ __forceinline__ i64 dp_rowoff(i64 r, i64 m, i64 n)
-{
-	const i64 a = m < n ? m : n, b = m < n ? n : m;
-	if (r <= a) return r * (r + 1) / 2;
-	if (r <= b) return a * (a + 1) / 2 + (r - a) * a;
-	return a * (a + 1) / 2 + (b - a) * a + (r - b) * (m + n - 1) - (b + r - 1) * (r - b) / 2;
+	if (state != 0 && !((flags >> (state + 2)) & 1)) state = 0;
+	if (state == 0) state = (int)(flags & 7);
+	return state;
 }
 
 // shift a value one lane up across the whole 64-lane wave (lane t receives lane t-1's value;

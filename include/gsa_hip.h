@@ -156,7 +156,7 @@ void gsa_release_reserved(int device);
  *   "split_min"      bases; gsa_align_many seeds a contig of at least this length on several contexts when contexts would idle (20 000 000)
  *   "bundle_contig"  bases; contigs up to this length share passes (16 000 000; 0 = never)      "bundle_cap"  bases per bundle, about (64 000 000)
  *   "seed_budget"    wave-iterations a 10 000-bp chunk may take in the speculative seed kernel before the dense kernels redo it (256)
- *   "dp_lane"        cells; gap alignments up to this size run one per lane (512; 0 = one per wavefront / quarter wavefront)
+ *   "dp_lane"        cells; gap alignments up to this size run one per lane (512; 0 = no lane class: every gap alignment below the striped kernel runs one per wavefront)
  *   "seed_mode"      1 = speculative kernel + dense kernels for the chunks it gives up on (default), 0 = every chunk through the
  *                    right-to-left sweep, 2 = one search per start instead of the sweep
  *   "pd_bitmap"      0 = seed groups by the PosDiff sort (SeedGrouping as written, GSAlign.cpp:126-143) even where the bitmap scan applies

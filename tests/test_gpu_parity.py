@@ -78,8 +78,8 @@ def test_ksw2_leaf_operator_edge_shapes(oracle_built, cx_index, seed):
 def test_ksw2_leaf_operator_small_classes(oracle_built, golden_dir, lane):
     """The classes below the striped kernel: 3000 pairs over every corner of n <= 64, m + n - 1 <= 128 (tools/dp_fuzz.py,
     make_small_pairs) against the oracle's ksw2 (ksw2_alignment.cpp:74-95) -- one alignment per lane up to GSA_DP_LANE cells
-    (k_dp_lane; default 512), one per wavefront above (k_dp_small); 64 and 8192 move the border to both ends of the domain, 0 is
-    round 2's split (four per wavefront / one per wavefront).  Twice: the second call reuses the arena and the sorted tiles."""
+    (k_dp_lane; default 512), one per wavefront above (k_dp_small; both in k_dp_small.hip); 64 and 8192 move the border to both ends of
+    the domain, 0 means no lane class: every pair goes through k_dp_small.  Twice: the second call reuses the arena and the sorted tiles."""
     import json
     import subprocess
     import sys
