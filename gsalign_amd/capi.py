@@ -24,6 +24,7 @@ EXPORTS = [
     "gsa_call_variants", "gsa_align_many_variants", "gsa_get_variant_timing",
     "gsa_block_cigars", "gsa_get_cigar_timing", "gsa_align_many_ex",
     "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
+    "gsa_create_from_pac", "gsa_export_index_table",
 ]
 
 
@@ -407,8 +408,46 @@ class Aligner:
         flags = (1 if wide else 0) | ((kmer_k & 15) << 8) | ((prio & 3) << 16) | (4 if pac is not None else 0)
         rc = self.lib.gsa_create_opts(device, C.byref(v), C.byref(p), flags, C.byref(self.ctx))
         if rc != 0:
-            raise GsaError(f"gsa_create -> {rc}: {self.lib.gsa_last_error(None).decode()}")
+            e = GsaError(f"gsa_create -> {rc}: {self.lib.gsa_last_error(None).decode()}"); e.code = rc
+            raise e
         self._options_from_env()
+
+    @classmethod
+    def from_reference(cls, pac, G: int, chr_len, device: int = 0, wide: bool = False, kmer_k: int = 0, **params) -> "Aligner":
+        """gsa_create_from_pac: a context from the .pac bytes of the G forward bases and the sequence lengths (hostlib.reference_from_fasta gives them) -- the index is
+        built in device memory, no index file and no host index array exists (self.idx is None).  Raises GsaError (.code = the library's error code)."""
+        self = cls.__new__(cls)
+        self.lib = load_library()
+        self.idx = None
+        self._pinned = []
+        self._devbufs = []
+        self.lib.gsa_create_from_pac.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(Params), C.c_uint32, C.POINTER(C.c_void_p)]
+        pac = np.ascontiguousarray(pac, dtype=np.uint8); chr_len = np.ascontiguousarray(chr_len, dtype=np.int32)
+        wide = wide or os.environ.get("GSA_FORCE_WIDE", "0") not in ("", "0")
+        kmer_k = kmer_k or int(os.environ.get("GSA_KMER_K", "0") or 0)
+        prio = int(os.environ.get("GSA_PRIO", "0") or 0)
+        flags = (1 if wide else 0) | ((kmer_k & 15) << 8) | ((prio & 3) << 16)
+        self.ctx = C.c_void_p()
+        p = self._params(**params)
+        rc = self.lib.gsa_create_from_pac(int(device), C.c_void_p(pac.ctypes.data), int(G), C.c_void_p(chr_len.ctypes.data), int(chr_len.size), C.byref(p), flags, C.byref(self.ctx))
+        if rc != 0:
+            e = GsaError(f"gsa_create_from_pac -> {rc}: {self.lib.gsa_last_error(None).decode()}"); e.code = rc
+            raise e
+        self._options_from_env()
+        return self
+
+    TABLES = {"header": 0, "occ": 1, "occ_base": 2, "sa_dense": 3, "sa": 4, "kmer": 5, "kmer_lo": 6, "pres": 7, "ref": 8, "ref2": 9}      # GSA_TABLE_* (include/gsa_hip.h)
+
+    def index_table(self, which) -> np.ndarray:
+        """gsa_export_index_table: the raw bytes of one device table of this context (a name of TABLES or its number); an absent table is empty."""
+        w = self.TABLES[which] if isinstance(which, str) else int(which)
+        self.lib.gsa_export_index_table.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        n = C.c_uint64(0)
+        self._ck(self.lib.gsa_export_index_table(self.ctx, w, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), np.uint8)
+        if out.size:
+            self._ck(self.lib.gsa_export_index_table(self.ctx, w, C.c_void_p(out.ctypes.data), out.size, C.byref(n)))
+        return out
 
     def clone(self) -> "Aligner":
         """A further context on the same GPU sharing this one's device index (gsa_clone)."""

@@ -179,6 +179,29 @@ void *dev_take_reserved(int device, size_t bytes, size_t *got)
 	return nullptr;
 }
 
+// ChrLocMap (bwt_index.cpp:240-253) as a sorted table of last coordinates, host and device; the error text goes to gsa_last_error(NULL) (the caller destroys c)
+static int ctx_chr_tables(gsa_ctx *c, const int32_t *chr_len, int32_t n_chr, i64 G, const char *who)
+{
+	c->G = G;
+	i64 tot = 0; std::vector<std::pair<i64, i32> > ends;
+	for (int i = 0; i < n_chr; i++) {
+		c->h_chr_len.push_back(chr_len[i]); c->h_chr_fwd.push_back(tot); tot += chr_len[i];
+		ends.push_back(std::make_pair(c->h_chr_fwd[i] + chr_len[i] - 1, i));
+		ends.push_back(std::make_pair(2 * G - tot + chr_len[i] - 1, i));
+	}
+	if (tot != G) return gsa_fail(nullptr, GSA_ERR_ARG, std::string(who) + ": sum(chr_len) != G");
+	std::sort(ends.begin(), ends.end());
+	for (size_t i = 0; i < ends.size(); i++) { c->h_chr_end.push_back(ends[i].first); c->h_chr_of_end.push_back(ends[i].second); }
+	c->d_chr_end.cap = c->h_chr_end.size() * 8; c->d_chr_of_end.cap = c->h_chr_of_end.size() * 4;
+	hipError_t e = hipMalloc(&c->d_chr_end.p, c->h_chr_end.size() * 8);
+	if (e == hipSuccess) e = hipMemcpy(c->d_chr_end.p, c->h_chr_end.data(), c->h_chr_end.size() * 8, hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = hipMalloc(&c->d_chr_of_end.p, c->h_chr_of_end.size() * 4);
+	if (e == hipSuccess) e = hipMemcpy(c->d_chr_of_end.p, c->h_chr_of_end.data(), c->h_chr_of_end.size() * 4, hipMemcpyHostToDevice);
+	if (e != hipSuccess) { (void)hipGetLastError(); return gsa_fail(nullptr, GSA_ERR_HIP, std::string(who) + ": chromosome tables: " + hipGetErrorString(e)); }
+	c->di.chr_end = c->d_chr_end.as<i64>(); c->di.chr_of_end = c->d_chr_of_end.as<i32>(); c->di.n_ends = (i32)c->h_chr_end.size();
+	return GSA_OK;
+}
+
 extern "C" {
 
 void gsa_default_params(gsa_params *p)
@@ -260,27 +283,11 @@ int gsa_create_opts(int device, const gsa_index_view *idx, const gsa_params *prm
 		if (rcu) { g_create_error = c->err; gsa_destroy(c); return rcu; }
 	} else
 	CK(h2d_big(c->d_ref.p, idx->ref, (size_t)2 * idx->G));
-	// ChrLocMap (bwt_index.cpp:240-253) as a sorted table of last coordinates
-	c->G = idx->G;
-	{
-		i64 tot = 0; std::vector<std::pair<i64, i32> > ends;
-		for (int i = 0; i < idx->n_chr; i++) {
-			c->h_chr_len.push_back(idx->chr_len[i]); c->h_chr_fwd.push_back(tot); tot += idx->chr_len[i];
-			ends.push_back(std::make_pair(c->h_chr_fwd[i] + idx->chr_len[i] - 1, i));
-			ends.push_back(std::make_pair(2 * idx->G - tot + idx->chr_len[i] - 1, i));
-		}
-		if (tot != idx->G) { gsa_fail(nullptr, GSA_ERR_ARG, "gsa_create: sum(chr_len) != G"); gsa_destroy(c); return GSA_ERR_ARG; }
-		std::sort(ends.begin(), ends.end());
-		for (size_t i = 0; i < ends.size(); i++) { c->h_chr_end.push_back(ends[i].first); c->h_chr_of_end.push_back(ends[i].second); }
-	}
-	c->d_chr_end.cap = c->h_chr_end.size() * 8; c->d_chr_of_end.cap = c->h_chr_of_end.size() * 4;
-	CK(hipMalloc(&c->d_chr_end.p, c->h_chr_end.size() * 8)); CK(hipMemcpy(c->d_chr_end.p, c->h_chr_end.data(), c->h_chr_end.size() * 8, hipMemcpyHostToDevice));
-	CK(hipMalloc(&c->d_chr_of_end.p, c->h_chr_of_end.size() * 4)); CK(hipMemcpy(c->d_chr_of_end.p, c->h_chr_of_end.data(), c->h_chr_of_end.size() * 4, hipMemcpyHostToDevice));
+	if (int rcc = ctx_chr_tables(c, idx->chr_len, idx->n_chr, idx->G, "gsa_create")) { gsa_destroy(c); return rcc; }
 #undef CK
 	c->di.primary = idx->primary; for (int i = 0; i < 5; i++) c->di.L2[i] = idx->L2[i]; c->di.L2[0] = 0;
 	c->di.seq_len = idx->L2[4];
 	c->di.bwt = nullptr; c->di.occ_base = nullptr; c->di.occ_shift = 0; c->di.sa = c->d_sa.as<u64>(); c->di.ref = c->d_ref.as<uint8_t>(); c->di.G = idx->G;
-	c->di.chr_end = c->d_chr_end.as<i64>(); c->di.chr_of_end = c->d_chr_of_end.as<i32>(); c->di.n_ends = (i32)c->h_chr_end.size();
 	c->di.sa32 = nullptr; c->di.sa64 = nullptr; c->di.kmer = nullptr; c->di.kmer_k = 0; c->di.kmer_lo = nullptr; c->di.kmer_lo_k = 0; c->di.kmer_e16 = 0; c->di.ref2 = nullptr; c->di.pres = nullptr; c->di.pres_k = 0;
 	{
 		const int rco = build_occ(c, c->d_bwt_ref.p, bwt_bytes / 64);
@@ -294,6 +301,79 @@ int gsa_create_opts(int device, const gsa_index_view *idx, const gsa_params *prm
 	gsa_release_reserved(device);      // (a reservation that did not fit this index)
 	if (const unsigned long long ov = gsa_take_grid_overflow()) { gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_create: a table build needed a launch of " + std::to_string(ov) + " work-items (>= 2^32)"); gsa_destroy(c); return GSA_ERR_LIMIT; }
 	*out = c;
+	return GSA_OK;
+}
+
+// The context gsa_create_opts makes from the index files of a sequence, from the sequence itself: bwa_idx_build (bwtindex.c:77-149) and bwa_idx_load + RestoreReferenceInfo
+// (bwt_index.cpp:147-264) in one pass over device memory.  The suffix sort of gsa_build_index runs on the new context's own stream; its SA array BECOMES the dense SA
+// (k_densify_sa's LF walk is not launched), the file layout of the .bwt words lives in a device buffer only until build_occ has regrouped it, the SA samples are written where
+// the context keeps them.  The remaining tables are built by the code gsa_create_opts runs (build_tables_from_pac, k_index.hip; build_ref2 / build_kmer_table, k_tables.hip).
+int gsa_create_from_pac(int device, const uint8_t *pac, int64_t G, const int32_t *chr_len, int32_t n_chr, const gsa_params *prm, uint32_t flags, gsa_ctx **out)
+{
+	if (!pac || !chr_len || !out || G <= 0 || n_chr <= 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_create_from_pac: bad argument");
+	{ int64_t tot = 0; for (int i = 0; i < n_chr; i++) { if (chr_len[i] <= 0) { tot = -1; break; } tot += chr_len[i]; } if (tot != G) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_create_from_pac: sum(chr_len) != G"); }
+	if (flags & ~(uint32_t)(GSA_CREATE_WIDE | GSA_CREATE_KMER_K(15) | GSA_CREATE_PRIO(3) | GSA_CREATE_REF_PAC)) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_create_from_pac: unknown flag");
+	{ const uint32_t kk = (flags >> 8) & 15u; if (kk == 1) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_create_from_pac: GSA_CREATE_KMER_K takes 2 .. 15 (0: chosen by text length and free memory)"); }
+	// the bound of the device builder (gsa_build_index): 32-bit suffix indices
+	if (2 * G + 1 > (1ll << 31) - 2) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_create_from_pac: the reference is longer than 1 073 741 822 bases (the device builder sorts 32-bit suffix indices)");
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return gsa_fail(nullptr, GSA_ERR_HIP, "no HIP device available (libgsa_hip.so has no CPU path)"); }
+	if (device < 0 || device >= ndev) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_create_from_pac: bad device ordinal");
+	gsa_ctx *c = new gsa_ctx();
+	c->device = device; c->force_wide = (flags & GSA_CREATE_WIDE) != 0; c->opt.kmer_k = (int)((flags >> 8) & 15u); c->prio_mode = (int)((flags >> 16) & 3u);
+	memset(c->kernel_ms, 0, sizeof(c->kernel_ms)); memset(c->counters, 0, sizeof(c->counters));
+	// (an error whose text is in c->err: moved to gsa_last_error(NULL) before the context goes)
+	auto fail = [&](int rc) { if (!c->err.empty()) g_create_error = c->err; gsa_destroy(c); return rc; };
+	if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); gsa_fail(nullptr, GSA_ERR_HIP, "gsa_create_from_pac: hipSetDevice"); return fail(GSA_ERR_HIP); }
+	(void)hipSetDeviceFlags(hipDeviceScheduleSpin); (void)hipGetLastError();
+	gsa_release_reserved(device);      // (a reservation is for the tables of gsa_create: the builder needs the room, and the dense SA is its own array)
+	if (int rc = ctx_private_init(c)) return fail(rc);
+	if (hipMalloc(&c->d_ref.p, (size_t)2 * G + 64) != hipSuccess) { (void)hipGetLastError(); gsa_fail(nullptr, GSA_ERR_NOMEM, "gsa_create_from_pac: hipMalloc (RefSequence)"); return fail(GSA_ERR_NOMEM); }
+	c->d_ref.cap = (size_t)2 * G + 64;
+	if (int rc = ctx_chr_tables(c, chr_len, n_chr, G, "gsa_create_from_pac")) return fail(rc);
+	c->di.bwt = nullptr; c->di.occ_base = nullptr; c->di.occ_shift = 0; c->di.sa = nullptr; c->di.ref = c->d_ref.as<uint8_t>(); c->di.G = G;
+	c->di.sa32 = nullptr; c->di.sa64 = nullptr; c->di.kmer = nullptr; c->di.kmer_k = 0; c->di.kmer_lo = nullptr; c->di.kmer_lo_k = 0; c->di.kmer_e16 = 0; c->di.ref2 = nullptr; c->di.pres = nullptr; c->di.pres_k = 0;
+	if (int rc = build_tables_from_pac(c, pac, G)) return fail(rc);
+	if (int rc = build_ref2(c)) return fail(rc);
+	if (int rc = build_kmer_table(c)) return fail(rc);
+	gsa_params dp; gsa_default_params(&dp);
+	if (int rc = gsa_set_params(c, prm ? prm : &dp)) return fail(rc);
+	if (const unsigned long long ov = gsa_take_grid_overflow()) { gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_create_from_pac: a table build needed a launch of " + std::to_string(ov) + " work-items (>= 2^32)"); c->err.clear(); return fail(GSA_ERR_LIMIT); }
+	*out = c;
+	return GSA_OK;
+}
+
+// Test support: one device table of a context, as it lies in device memory, to the host -- its DEFINED extent, not the allocation's slack.
+int gsa_export_index_table(gsa_ctx *c, int which, void *dst, uint64_t cap, uint64_t *bytes)
+{
+	if (!c || !bytes) return GSA_ERR_ARG;
+	const DevIndex &di = c->di;
+	uint64_t hdr[6] = { di.primary, di.L2[0], di.L2[1], di.L2[2], di.L2[3], di.L2[4] };
+	uint64_t bw = 0, ns = 0;
+	if (di.G <= 0 || gsa_index_sizes(di.G, &bw, &ns) != GSA_OK) return gsa_fail(c, GSA_ERR_STATE, "gsa_export_index_table: the context holds no index");
+	const uint64_t n_blocks = 2 * ((bw + 15) / 16);      // build_occ: 64-row blocks, two uint4 each
+	const void *src = nullptr; uint64_t n = 0; bool host = false;
+	switch (which) {
+	case GSA_TABLE_HEADER:   src = hdr; n = sizeof(hdr); host = true; break;
+	case GSA_TABLE_OCC:      src = di.bwt; n = 2 * n_blocks * sizeof(uint4); break;
+	case GSA_TABLE_OCC_BASE: src = di.occ_base; n = 4 * ((n_blocks >> di.occ_shift) + 1) * sizeof(u64); break;
+	case GSA_TABLE_SA_DENSE: src = di.sa32 ? (const void *)di.sa32 : (const void *)di.sa64; n = (di.seq_len + 1) * (di.sa32 ? 4 : 8); break;
+	case GSA_TABLE_SA:       src = di.sa; n = ns * 8; break;
+	case GSA_TABLE_KMER:     src = di.kmer; n = ((uint64_t)(di.kmer_e16 ? 16 : 32)) << (2 * di.kmer_k); break;
+	case GSA_TABLE_KMER_LO:  src = di.kmer_lo; n = ((uint64_t)(di.kmer_e16 ? 16 : 32)) << (2 * di.kmer_lo_k); break;
+	case GSA_TABLE_PRES:     src = di.pres; n = di.pres_k >= 3 ? ((uint64_t)32 << (2 * (di.pres_k - 3))) : 0; break;
+	case GSA_TABLE_REF:      src = di.ref; n = 2 * (uint64_t)di.G; break;
+	case GSA_TABLE_REF2:     src = di.ref2; n = (di.seq_len / 16 + 8) * 4; break;
+	default: return gsa_fail(c, GSA_ERR_ARG, "gsa_export_index_table: unknown table");
+	}
+	if (!src) n = 0;      // (an absent table)
+	*bytes = n;
+	if (!dst || n == 0) return GSA_OK;
+	if (cap < n) return gsa_fail(c, GSA_ERR_ARG, "gsa_export_index_table: the buffer is too small");
+	if (host) { memcpy(dst, src, n); return GSA_OK; }
+	GSA_CHECK(c, hipSetDevice(c->device));
+	GSA_CHECK(c, hipStreamSynchronize(c->stream));
+	GSA_CHECK(c, hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
 	return GSA_OK;
 }
 

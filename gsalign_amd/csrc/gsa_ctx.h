@@ -283,10 +283,14 @@ template <class T> static inline T *pin_ensure(gsa_ctx *c, DevBuf &b, size_t n)
 }
 
 // stage drivers (one per translation unit)
-int build_dense_sa(gsa_ctx *c, u64 n_sa);   // k_tables.hip
+int build_dense_sa(gsa_ctx *c, u64 n_sa);   // k_tables.hip  (gsa_create_opts: build_ref2, densify_sa, build_kmer_table)
+int build_ref2(gsa_ctx *c);                 // k_tables.hip  (the 2-bit copy of RefSequence)
+int densify_sa(gsa_ctx *c, u64 n_sa);       // k_tables.hip  (the dense SA by LF walks from the samples)
+int build_kmer_table(gsa_ctx *c);           // k_tables.hip  (needs the Occ blocks and the dense SA; its size comes from the free device memory)
 int unpack_pac(gsa_ctx *c, const uint8_t *d_pac, i64 G, uint8_t *d_ref);   // k_tables.hip  (GSA_CREATE_REF_PAC: RefSequence from the .pac bytes, on the device)
 int build_occ(gsa_ctx *c, const void *ref_layout, u64 n_blocks128);   // k_tables.hip: the device's Occ blocks from the reference's layout
 int build_presence(gsa_ctx *c);             // k_tables.hip  (after MinSeedLength changed)
+int build_tables_from_pac(gsa_ctx *c, const uint8_t *pac, i64 G);   // k_index.hip  (gsa_create_from_pac: Occ blocks, both SAs and RefSequence from the suffix sort, nothing copied home)
 int stage1_seed(gsa_ctx *c);          // k_seed.hip
 int stage1_dense(gsa_ctx *c, hipStream_t st, const uint8_t *d_q, i32 qlen, i64 n_chunks, u64 n_heavy, bool dense_all, bool sweep_all, size_t ccap, u64 &hits, u64 &maxcand, u64 &occ_all);   // k_seed_dense.hip  (stage1_seed's dense kernels: launch, wait, counters)
 int prepare_pd_bitmap(gsa_ctx *c, i64 n_hits, i64 n_chunks = 0);   // k_seed_select.hip  (whether this contig keeps the bitmap of occupied PosDiff values, cleared)

@@ -60,6 +60,10 @@ bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::
 // this shape behind a device ordinal; this library links no HIP.
 typedef int (*gsah_bwt_fn)(void *user, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa);
 bool gsah_build_index_with(const std::string &fasta, const std::string &prefix, std::string &err, gsah_bwt_fn fn, void *user);
+// The reference half of an index WITHOUT the index: the builder's FASTA pass (read_fasta, srand48(11) / lrand48 for ambiguous bases, the .pac packing) into idx -- G, chr_name
+// (as the .ann round trip delivers them), chr_len, chr_fwd / chr_rev, end_key / end_chr and idx.pac = the ceil(G / 4) .pac bytes; bwt / sa / ref stay empty.  Touches no
+// file but the FASTA.  idx.pac goes to gsa_create_from_pac (gsa_hip.h), gsah_unpack_ref gives the emitters their RefSequence as after gsah_load_index_files.
+bool gsah_reference_from_fasta(const std::string &fasta, HostIndex &idx, std::string &err);
 // LoadQueryFile / TrimChromosomeName / CheckQuerySeq (reference src/main.cpp:35-114)
 bool gsah_load_query(const std::string &path, std::vector<QueryContig> &out, std::string &err);
 

@@ -94,6 +94,19 @@ int gsah_c_build_index_with(const char *fasta, const char *prefix, gsah_bwt_fn f
 	return -1;
 }
 
+// gsah_reference_from_fasta through the C API: the reference stays in a static HostIndex until the next call; returns the number of sequences, -1 on error
+static HostIndex g_ref;
+int gsah_c_reference_from_fasta(const char *fasta, long long *G, long long *pac_bytes, char *err)
+{
+	std::string e;
+	if (!gsah_reference_from_fasta(fasta, g_ref, e)) { if (err) { strncpy(err, e.c_str(), 255); err[255] = 0; } return -1; }
+	*G = (long long)g_ref.G; *pac_bytes = (long long)g_ref.pac.size();
+	return (int)g_ref.chr_len.size();
+}
+const unsigned char *gsah_c_reference_pac(void) { return g_ref.pac.data(); }
+const char *gsah_c_reference_name(int i) { return g_ref.chr_name[(size_t)i].c_str(); }
+int gsah_c_reference_len(int i) { return g_ref.chr_len[(size_t)i]; }
+
 // Emit MAF + VCF for a whole query FASTA given, per contig, a finished gsa_result.
 // get_result(user, contig_index, seq, len, &result) is called once per contig, in order.
 typedef int (*gsah_result_cb)(void *user, int contig, const char *seq, int len, gsa_result *out);

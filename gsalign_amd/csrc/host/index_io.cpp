@@ -381,16 +381,20 @@ bool gsah_load_index(const std::string &prefix, HostIndex &idx, std::string &err
 
 bool gsah_build_index(const std::string &fasta, const std::string &prefix, std::string &err) { return gsah_build_index_with(fasta, prefix, err, nullptr, nullptr); }
 
-// fn = nullptr: the host's suffix sorters; else the caller supplies the BWT/SA half from the .pac bytes (gsah_bwt_fn, gsa_host.h): everything around it -- FASTA
-// parsing, N -> lrand48, .pac / .ann / .amb, the .bwt / .sa writers -- is the same code either way
-bool gsah_build_index_with(const std::string &fasta, const std::string &prefix, std::string &err, gsah_bwt_fn fn, void *user)
+// The FASTA half of the builder: kseq-style parsing, bns_fasta2bntseq / add1 (bntseq.c:110-211) -- an ambiguous base becomes lrand48() & 3 under srand48(11), runs of
+// one ambiguous letter are the holes of .amb -- and the .pac packing of the forward strand (bntseq.c:192-201).  Touches no file but the FASTA.
+namespace {
+struct Hole { int64_t off; int32_t len; char amb; };
+struct PackedFasta {
+	std::vector<FaRec> recs; std::vector<Hole> holes; std::vector<int64_t> offs; std::vector<int32_t> nambs;
+	std::vector<uint8_t> codes, pac; int64_t G = 0;
+};
+bool pack_fasta(const std::string &fasta, PackedFasta &P, std::string &err)
 {
-	std::vector<FaRec> recs;
+	std::vector<FaRec> &recs = P.recs;
 	if (!read_fasta_gz(fasta, recs) || recs.empty()) { err = "cannot read FASTA " + fasta; return false; }
-	// ---- pack: bns_fasta2bntseq / add1 (bntseq.c:110-211) ----
-	struct Hole { int64_t off; int32_t len; char amb; };
-	std::vector<Hole> holes; std::vector<int64_t> offs; std::vector<int32_t> nambs;
-	std::vector<uint8_t> codes;
+	std::vector<Hole> &holes = P.holes; std::vector<int64_t> &offs = P.offs; std::vector<int32_t> &nambs = P.nambs;
+	std::vector<uint8_t> &codes = P.codes;
 	srand48(11);
 	for (size_t s = 0; s < recs.size(); s++) {
 		offs.push_back((int64_t)codes.size()); nambs.push_back(0);
@@ -407,12 +411,56 @@ bool gsah_build_index_with(const std::string &fasta, const std::string &prefix, 
 			codes.push_back((uint8_t)c);
 		}
 	}
-	const int64_t G = (int64_t)codes.size();
+	const int64_t G = P.G = (int64_t)codes.size();
 	if (G <= 0) { err = "empty reference"; return false; }
+	P.pac.assign((size_t)((G >> 2) + ((G & 3) ? 1 : 0)), 0);
+	for (int64_t l = 0; l < G; l++) P.pac[l >> 2] |= codes[l] << ((~l & 3) << 1);
+	return true;
+}
+}
+
+// What gsah_load_index_files + the .ann file would deliver for the index of `fasta`, without an index: G, the sequence names and lengths, ChrLocMap and the .pac bytes
+// (idx.pac: ceil(G / 4) of them) -- what gsa_create_from_pac and gsah_unpack_ref need.  No file is written.
+bool gsah_reference_from_fasta(const std::string &fasta, HostIndex &idx, std::string &err)
+{
+	PackedFasta P;
+	if (!pack_fasta(fasta, P, err)) return false;
+	{ std::vector<uint8_t>().swap(P.codes); }
+	idx.G = P.G; idx.chr_name.clear(); idx.chr_len.clear();
+	for (const FaRec &r : P.recs) {
+		// (as the .ann round trip delivers a name: the first blank-separated word of "name comment" -- of "(null)" without either --, at most 10239 characters)
+		std::string line = r.name + " " + (r.comment.empty() ? "(null)" : r.comment);
+		size_t b = 0; while (b < line.size() && isspace((unsigned char)line[b])) b++;
+		size_t e = b; while (e < line.size() && !isspace((unsigned char)line[e]) && e - b < 10239) e++;
+		idx.chr_name.push_back(line.substr(b, e - b));
+		idx.chr_len.push_back((int32_t)r.seq.size());
+	}
+	idx.pac.resize(P.pac.size());
+	if (!idx.pac.data()) { err = "out of memory"; return false; }
+	memcpy(idx.pac.data(), P.pac.data(), P.pac.size());
+	const int64_t G2 = 2 * idx.G;
+	idx.chr_fwd.clear(); idx.chr_rev.clear(); idx.end_key.clear(); idx.end_chr.clear();
+	int64_t tot = 0; std::vector<std::pair<int64_t, int32_t> > ends;
+	for (size_t i = 0; i < idx.chr_len.size(); i++) {
+		idx.chr_fwd.push_back(tot); tot += idx.chr_len[i]; idx.chr_rev.push_back(G2 - tot);
+		ends.push_back(std::make_pair(idx.chr_fwd[i] + idx.chr_len[i] - 1, (int32_t)i)); ends.push_back(std::make_pair(idx.chr_rev[i] + idx.chr_len[i] - 1, (int32_t)i));
+	}
+	std::sort(ends.begin(), ends.end());
+	for (size_t i = 0; i < ends.size(); i++) { idx.end_key.push_back(ends[i].first); idx.end_chr.push_back(ends[i].second); }
+	return true;
+}
+
+// fn = nullptr: the host's suffix sorters; else the caller supplies the BWT/SA half from the .pac bytes (gsah_bwt_fn, gsa_host.h): everything around it -- FASTA
+// parsing, N -> lrand48, .pac / .ann / .amb, the .bwt / .sa writers -- is the same code either way
+bool gsah_build_index_with(const std::string &fasta, const std::string &prefix, std::string &err, gsah_bwt_fn fn, void *user)
+{
+	PackedFasta P;
+	if (!pack_fasta(fasta, P, err)) return false;
+	std::vector<FaRec> &recs = P.recs; std::vector<Hole> &holes = P.holes; std::vector<int64_t> &offs = P.offs; std::vector<int32_t> &nambs = P.nambs;
+	std::vector<uint8_t> &codes = P.codes, &pac = P.pac;
+	const int64_t G = P.G;
 	// .pac (forward only; bntseq.c:192-201)
-	std::vector<uint8_t> pac((size_t)((G >> 2) + ((G & 3) ? 1 : 0)), 0);
 	{
-		for (int64_t l = 0; l < G; l++) pac[l >> 2] |= codes[l] << ((~l & 3) << 1);
 		FILE *fp = fopen((prefix + ".pac").c_str(), "wb"); if (!fp) { err = "cannot write " + prefix + ".pac"; return false; }
 		fput(fp, pac.data(), pac.size());
 		uint8_t ct = 0; if (G % 4 == 0) fput(fp, &ct, 1);

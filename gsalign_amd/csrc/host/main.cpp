@@ -5,7 +5,8 @@
 // pthread stages.  Extra flags: -gpu LIST (device ordinals, comma separated: the query contigs shard over them with the
 // index replicated), -ctx N (contexts per GPU: gsa_clone, contigs overlap on one device) and -timing
 // (one JSON line on stderr: where the wall time of the run went).  -gpuindex: an index that has to be built (`index`, or -r) gets its BWT/SA half from the
-// GPU (gsa_build_index) instead of the host's suffix sorters; the files are the same bytes.
+// GPU (gsa_build_index) instead of the host's suffix sorters; the files are the same bytes.  -memindex (with -r): no index file at all -- the reference FASTA is
+// parsed (gsah_reference_from_fasta) and the first GPU's context is made from its .pac bytes in device memory (gsa_create_from_pac).
 // The contigs go through gsa_align_many (the per-contig loop of GSAlign.cpp:483-548).  Round 5: a GPU worker thread only COPIES a finished
 // contig out of the library's memory; ONE formatter thread takes the contigs in contig order (OutputMAF appends per contig, VarVec grows in
 // contig order: GSAlign.cpp:543-546) and formats each with the host pool's threads (par.h: the text lines of a block, the variants of a
@@ -50,7 +51,8 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -ctx   INT     contexts per GPU working on different query sequences [2]\n");
 	fprintf(stderr, "         -timing        print where the wall time went (one JSON line on stderr)\n");
 	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
-	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index), references up to 1.07 Gbp [false]\n\n", prog);
+	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index), references up to 1.07 Gbp [false]\n", prog);
+	fprintf(stderr, "         -memindex      with -r: build the index in GPU memory (gsa_create_from_pac) and align against it; no index file is written or read, references up to 1.07 Gbp [false]\n\n");
 }
 
 // the index of `fasta` under `prefix`; on_gpu: the BWT/SA half from gsa_build_index on `device` (a reference over its bound: one line, then the host builder).
@@ -102,7 +104,7 @@ int main(int argc, char *argv[])
 	//  kernel and faulting it in again for the next contig)
 	mallopt(M_MMAP_THRESHOLD, 1 << 30); mallopt(M_TRIM_THRESHOLD, 1 << 30); mallopt(M_TOP_PAD, 256 << 20);
 	gsa_params prm; gsa_default_params(&prm);
-	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, gpuindex = false, timing = getenv("GSA_TIMING") != NULL;
+	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
 	std::vector<int> gpus;
 	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL;
 	if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(argv[0], threads, prm, fmt); return 0; }
@@ -135,6 +137,7 @@ int main(int argc, char *argv[])
 		else if (a == "-timing") timing = true;
 		else if (a == "-gpuvar") gpuvar = true;
 		else if (a == "-gpuindex") gpuindex = true;
+		else if (a == "-memindex") memindex = true;
 		else if (a == "-dp") dotplot = true;
 		else if (a == "-gp" && i + 1 < argc) gnuplot_arg = argv[++i];      // main.cpp:285: the path of gnuplot, used as given
 		else if (a == "-d" || a == "-debug") { /* debug printers: not reproduced */ }
@@ -147,7 +150,7 @@ int main(int argc, char *argv[])
 
 	const time_t t0 = time(NULL);
 	const double T0 = now_s();
-	double t_query = 0, t_index = 0, t_create = 0, t_align = 0, t_drain = 0, t_vcf = 0, t_maf_fmt = 0, t_var = 0, t_copy = 0, t_build = 0;
+	double t_query = 0, t_index = 0, t_create = 0, t_align = 0, t_drain = 0, t_vcf = 0, t_maf_fmt = 0, t_var = 0, t_copy = 0, t_build = 0, t_ref_parse = 0, t_from_pac = 0;
 	fprintf(stderr, "Step1. Load the two genome sequences...\n");
 	std::string err, qerr; std::vector<QueryContig> qs; bool q_ok = false;
 	if (!first_char_is_header(query_fa)) { fprintf(stderr, "Please check the query file: %s\n", query_fa); return 0; }
@@ -155,8 +158,14 @@ int main(int argc, char *argv[])
 	std::thread q_loader([&] { const double t = now_s(); q_ok = gsah_load_query(query_fa, qs, qerr); t_query = now_s() - t; });
 	struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } q_join{ q_loader };
 	HostIndex idx; std::string prefix;
-	if (index_prefix != NULL && gsah_index_files_exist(index_prefix)) prefix = index_prefix;
-	else if (ref_fa != NULL && first_char_is_header(ref_fa)) {
+	if (index_prefix != NULL && gsah_index_files_exist(index_prefix)) {
+		prefix = index_prefix;
+		if (memindex) { fprintf(stderr, "-memindex: the index files of %s exist and are used\n", index_prefix); memindex = false; }
+	} else if (ref_fa != NULL && first_char_is_header(ref_fa) && memindex) {
+		// the FASTA half of the index builder only: names, lengths and the .pac bytes stay in memory, nothing is written beside the reference
+		const double t = now_s(); const bool ok = gsah_reference_from_fasta(ref_fa, idx, err); t_ref_parse = now_s() - t;
+		if (!ok) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+	} else if (ref_fa != NULL && first_char_is_header(ref_fa)) {
 		prefix = ref_fa; size_t p = prefix.find_last_of('.'); if (p != std::string::npos && p > 0) prefix.resize(p);
 		const double t = now_s();
 		if (const int rcb = build_index(ref_fa, prefix, gpuindex, gpus.empty() ? 0 : gpus[0])) return rcb;
@@ -167,6 +176,7 @@ int main(int argc, char *argv[])
 	if (gpus.empty()) gpus.push_back(0);
 	double t_reserve = 0, t_reserve_wait = 0, t_unpack_wait = 0, t_at_align = 0;
 	std::thread reserver([&] {
+		if (memindex) return;      // (no .bwt header to read the text length from, and gsa_create_from_pac adopts no reservation)
 		const double t = now_s();
 		uint64_t hdr[5] = { 0, 0, 0, 0, 0 };
 		FILE *fb = fopen((prefix + ".bwt").c_str(), "rb");
@@ -178,7 +188,7 @@ int main(int argc, char *argv[])
 	struct Joiner3 { std::thread &t; ~Joiner3() { if (t.joinable()) t.join(); } } reserve_join{ reserver };
 	// the index files as they lie on disk first (.bwt, .sa, .ann, the raw .pac bytes); RefSequence -- which only the emitters of THIS program read -- is unpacked further
 	// down, beside gsa_create: the device gets the .pac bytes and unpacks its own copy (GSA_CREATE_REF_PAC)
-	{ const double t = now_s(); const bool ok = gsah_load_index_files(prefix, idx, err); t_index = now_s() - t; if (!ok) { fprintf(stderr, "\n\nError! Please check your input! (%s)\n", err.c_str()); return 1; } }
+	if (!memindex) { const double t = now_s(); const bool ok = gsah_load_index_files(prefix, idx, err); t_index = now_s() - t; if (!ok) { fprintf(stderr, "\n\nError! Please check your input! (%s)\n", err.c_str()); return 1; } }
 
 	// FindGnuPlotPath (main.cpp:169-191): -dp needs a gnuplot binary -- the one -gp names, else the first one on PATH; without one the
 	// reference plots nothing either
@@ -213,7 +223,14 @@ int main(int argc, char *argv[])
 			const char *fw = getenv("GSA_FORCE_WIDE");
 			// (the first GPU gets the index from the host -- upload + table builds; every further GPU gets a device-to-device copy of the finished tables:
 			//  gsa_clone_to_device, no second pass over PCIe, nothing rebuilt)
-			const int rc_c = g == 0 ? gsa_create_opts(gpus[g], &view, &prm, ((fw && *fw && *fw != '0') ? GSA_CREATE_WIDE : 0u) | GSA_CREATE_REF_PAC, &owner) : gsa_clone_to_device(ctxs[0], gpus[g], &owner);
+			const uint32_t wide = (fw && *fw && *fw != '0') ? GSA_CREATE_WIDE : 0u;
+			const double tc = now_s();
+			const int rc_c = g > 0 ? gsa_clone_to_device(ctxs[0], gpus[g], &owner)
+			               : memindex ? gsa_create_from_pac(gpus[g], idx.pac.data(), idx.G, idx.chr_len.data(), (int32_t)idx.chr_len.size(), &prm, wide, &owner)
+			                          : gsa_create_opts(gpus[g], &view, &prm, wide | GSA_CREATE_REF_PAC, &owner);
+			if (g == 0 && memindex) t_from_pac = now_s() - tc;
+			// (a reference over the device builder's bound: the library's message, and no fall-back to a path that writes the files the user asked not to have)
+			if (rc_c == GSA_ERR_LIMIT && g == 0 && memindex) { fprintf(stderr, "-memindex: %s\n", gsa_last_error(NULL)); return 1; }
 			if (rc_c != GSA_OK) { fprintf(stderr, "GPU initialisation failed (device %d): %s\n", gpus[g], gsa_last_error(NULL)); return 2; }
 			for (const char *nm : { "split_min", "bundle_contig", "bundle_cap" }) {
 				std::string ev = std::string("GSA_") + nm; for (char &ch : ev) ch = (char)toupper((unsigned char)ch);
@@ -414,10 +431,10 @@ int main(int argc, char *argv[])
 		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, \"cigar_s\": %.3f, "
 		        "\"result_copy_s_sum\": %.3f, \"maf_format_s\": %.3f, \"variants_s\": %.3f, \"output_drain_after_align_s\": %.3f, \"maf_write_s\": %.3f, \"maf_bytes\": %llu, "
 		        "\"vcf_s\": %.3f, \"vcf_write_s\": %.3f, \"vcf_bytes\": %llu, \"destroy_s\": %.3f, \"host_threads\": %d, \"contexts\": %d, \"query_bp\": %lld, \"contigs\": %d, \"gbp_per_s_excl_index_build\": %.4f, "
-		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f}\n",
+		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f}\n",
 		        total, t_build, t_index, t_create, t_query, t_pin, t_align, cigar_ms / 1e3, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
-		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9);
+		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac);
 	}
 	if (timing && var_on_gpu) fprintf(stderr, "GSA_VARIANT_PASS {\"device_ms_sum\": %.3f, \"passes\": %lld, \"query_bp\": %lld}\n", var_dev_ms, var_dev_n, [&] { long long b = 0; for (const QueryContig &q : qs) b += (long long)q.seq.size(); return b; }());
 	// (everything is on disk and the GPU is released: the process ends here -- unwinding 20 GB of host buffers and the HIP runtime's own

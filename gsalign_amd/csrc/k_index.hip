@@ -12,6 +12,8 @@
 //                length of the next list -- and stops at 0.  Rounds ~ log2(longest repeat / 29): no depth limit, no fallback.
 // From the finished SA plain passes give what derive_bwt_sa and the interleave loop of host/index_io.cpp give: primary, the 2-bit BWT without the '$'
 // row, its running counts every 128 symbols (bwt_bwtupdate_core's layout) and the SA samples of every 32nd row.  L2 follows from the closing counts.
+// gsa_create_from_pac (build_tables_from_pac, at the end) runs the same sort and the same passes for a context: nothing is copied home, the SA array itself becomes the
+// context's dense SA (k_ix_widen for the 64-bit layout) and the file layout of the BWT words lives only until build_occ (k_tables.hip) has regrouped it.
 #include <chrono>
 #include "gsa_scan.h"
 
@@ -170,36 +172,51 @@ __global__ void __launch_bounds__(IX_T) k_ix_samples(i64 n_sa, const u32 *__rest
 	for (i64 j = (i64)blockIdx.x * IX_T + threadIdx.x; j < n_sa; j += (i64)gridDim.x * IX_T) sa[j] = j ? (u64)SA[32 * j] : ~0ull;
 }
 
+// the dense SA of the >= 2^32-row layout (GSA_CREATE_WIDE) from the finished 32-bit array; row 0 is the sa[0] = -1 sentinel there, SA[0] = S here
+__global__ void __launch_bounds__(IX_T) k_ix_widen(i64 n, const u32 *__restrict__ SA, u64 *__restrict__ d64)
+{
+	for (i64 i = (i64)blockIdx.x * IX_T + threadIdx.x; i < n; i += (i64)gridDim.x * IX_T) d64[i] = i ? (u64)SA[i] : ~0ull;
+}
+
 namespace {
-// the builder's device arrays: all freed when the call returns, whichever way
+// the builder's device arrays: all freed when the call returns, whichever way (gsa_create_from_pac takes SA out first: release)
 struct IxBufs {
 	hipStream_t st; std::vector<void *> p;
-	~IxBufs() { (void)hipStreamSynchronize(st); for (void *q : p) (void)hipFree(q); (void)hipGetLastError(); }
+	~IxBufs() { free_all(); }
+	void free_all() { if (p.empty()) return; (void)hipStreamSynchronize(st); for (void *q : p) (void)hipFree(q); p.clear(); (void)hipGetLastError(); }
+	void release(void *q) { for (size_t k = 0; k < p.size(); k++) if (p[k] == q) { p.erase(p.begin() + (long)k); return; } }
 	template <class T> bool get(T **out, size_t n) { void *q = nullptr; if (hipMalloc(&q, (n ? n : 1) * sizeof(T) + 256) != hipSuccess) { (void)hipGetLastError(); return false; } p.push_back(q); *out = (T *)q; return true; }
+};
+// what the sort leaves on the device: SA (n + 32 entries: the size of the 32-bit dense SA of a context, build_dense_sa), the packed text, the .pac bytes, the status
+// words {-, primary}; d_bwt is zeroed for the BWT / Occ passes (whole 64-byte blocks of the file layout and one more: what build_occ reads), d_sa is there when asked for
+struct IxSort {
+	IxBufs B;
+	i64 G = 0, S = 0, n = 0, n_tw = 0, n_words = 0, n_blk = 0, n_bwt = 0, n_sa = 0, k_end = 0; i32 rounds = 0;
+	uint8_t *d_pac = nullptr; u64 *tw = nullptr, *d_sa = nullptr; u32 *SA = nullptr, *d_st = nullptr, *d_bwt = nullptr;
 };
 }
 
-// pac: host, ceil(G / 4) bytes; primary, L2, bwt[bwt_words], sa[n_sa]: host.  Device bytes per suffix (S = 2G of them): keys 2 x 8, suffixes 2 x 4, slots 2 x 4, rank 4,
-// SA 4, the sort's scratch 12 (c->tmp) + its histograms -- 52 bytes, and under 1 byte for the packed text, the BWT words and the samples.
-int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds)
+// Device bytes per suffix (S = 2G of them): keys 2 x 8, suffixes 2 x 4, slots 2 x 4, rank 4, SA 4, the sort's scratch 12 (c->tmp) + its histograms -- 52 bytes, and
+// under 1 byte for the packed text, the BWT words and the samples.  pac: host, ceil(G / 4) bytes; ev0 (may be null) is recorded behind its upload.
+static int ix_sort(gsa_ctx *c, IxSort &X, const uint8_t *pac, i64 G, bool samples, hipEvent_t ev0, const char *who)
 {
 	const i64 S = 2 * G, n = S + 1;
-	const i64 n_tw = S / 32 + 3, n_words = (S + 15) / 16, n_blk = (S + 127) / 128, n_bwt = n_words + (n_blk + 1) * 8, n_sa = (S + 32) / 32, k_end = n_blk * 8 + n_words;
-	const size_t pac_bytes = (size_t)((G + 3) / 4);
+	X.G = G; X.S = S; X.n = n;
+	X.n_tw = S / 32 + 3; X.n_words = (S + 15) / 16; X.n_blk = (S + 127) / 128; X.n_bwt = X.n_words + (X.n_blk + 1) * 8; X.n_sa = (S + 32) / 32; X.k_end = X.n_blk * 8 + X.n_words;
+	const i64 n_tw = X.n_tw;
+	const size_t pac_bytes = (size_t)((G + 3) / 4), bwt_alloc = (size_t)((X.n_bwt + 15) / 16) * 16 + 16;
 	const int b = ceil_log2_u64((u64)S + 1);      // bits of a rank (0 .. S)
 	hipStream_t st = c->stream;
-	IxBufs B; B.st = st;
-	uint8_t *d_pac; u64 *tw, *keyA, *keyB, *d_sa; u32 *valA, *valB, *slotA, *slotB, *rank, *SA, *d_st, *d_bwt;
+	IxBufs &B = X.B; B.st = st;
+	uint8_t *d_pac; u64 *tw, *keyA, *keyB; u32 *valA, *valB, *slotA, *slotB, *rank, *SA, *d_st;
 	if (!B.get(&d_pac, pac_bytes) || !B.get(&tw, (size_t)n_tw) || !B.get(&keyA, (size_t)n) || !B.get(&keyB, (size_t)n) || !B.get(&valA, (size_t)n) || !B.get(&valB, (size_t)n) ||
 	    !B.get(&slotA, (size_t)n) || !B.get(&slotB, (size_t)n) || !B.get(&rank, (size_t)n + 1) || !B.get(&SA, (size_t)n + 32) || !B.get(&d_st, (size_t)8) ||
-	    !B.get(&d_bwt, (size_t)n_bwt + 16) || !B.get(&d_sa, (size_t)n_sa))
-		return gsa_fail(c, GSA_ERR_NOMEM, "gsa_build_index: hipMalloc (about 52 bytes per suffix, " + std::to_string((long long)S) + " suffixes)");
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 2; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } evg{ ev };
-	GSA_CHECK(c, hipEventCreate(&ev[0])); GSA_CHECK(c, hipEventCreate(&ev[1]));
+	    !B.get(&X.d_bwt, bwt_alloc) || (samples && !B.get(&X.d_sa, (size_t)X.n_sa)))
+		return gsa_fail(c, GSA_ERR_NOMEM, std::string(who) + ": hipMalloc (about 52 bytes per suffix, " + std::to_string((long long)S) + " suffixes)");
+	X.d_pac = d_pac; X.tw = tw; X.SA = SA; X.d_st = d_st;
 	GSA_CHECK(c, hipMemcpyAsync(d_pac, pac, pac_bytes, hipMemcpyHostToDevice, st));
-	GSA_CHECK(c, hipEventRecord(ev[0], st));
-	GSA_CHECK(c, hipMemsetAsync(d_bwt, 0, ((size_t)n_bwt + 16) * 4, st));
+	if (ev0) GSA_CHECK(c, hipEventRecord(ev0, st));
+	GSA_CHECK(c, hipMemsetAsync(X.d_bwt, 0, bwt_alloc * 4, st));
 	hipLaunchKernelGGL(k_ix_init, dim3(1), dim3(64), 0, st, rank, SA, d_st, S);
 	GSA_CHECK(c, hipGetLastError());
 	hipLaunchKernelGGL(k_ix_pack, dim3(ix_grid(n_tw)), dim3(IX_T), 0, st, (const uint8_t *)d_pac, G, S, tw, n_tw);
@@ -220,7 +237,7 @@ int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 
 		GSA_CHECK(c, hipMemcpyAsync(&left, d_st, 4, hipMemcpyDeviceToHost, st));
 		GSA_CHECK(c, hipStreamSynchronize(st));
 		if (left == 0) break;
-		if (++nr > 64) return gsa_fail(c, GSA_ERR_STATE, "internal: gsa_build_index: the suffix groups do not resolve");
+		if (++nr > 64) return gsa_fail(c, GSA_ERR_STATE, std::string("internal: ") + who + ": the suffix groups do not resolve");
 		m = (i64)left;
 		hipLaunchKernelGGL(k_ix_keys, dim3(ix_grid(m)), dim3(IX_T), 0, st, m, (const u32 *)valA, (const u32 *)rank, h, S, b, keyA);
 		GSA_CHECK(c, hipGetLastError());
@@ -228,17 +245,39 @@ int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 
 		slot = slot_out; slot_out = slot_out == slotA ? slotB : slotA;
 		h *= 2;
 	}
-	hipLaunchKernelGGL(k_ix_bwt, dim3(ix_grid(S)), dim3(IX_T), 0, st, S, (const u32 *)SA, (const u64 *)tw, (const u32 *)d_st, d_bwt);
+	X.rounds = nr;
+	return GSA_OK;
+}
+
+// the file layout of the .bwt words into X.d_bwt: the symbols, then the running counts in front of every block and the closing counts
+static int ix_bwt_occ(gsa_ctx *c, IxSort &X)
+{
+	hipStream_t st = c->stream;
+	hipLaunchKernelGGL(k_ix_bwt, dim3(ix_grid(X.S)), dim3(IX_T), 0, st, X.S, (const u32 *)X.SA, (const u64 *)X.tw, (const u32 *)X.d_st, X.d_bwt);
 	GSA_CHECK(c, hipGetLastError());
-	for (int sym0 = 0; sym0 < 4; sym0 += 2) { OpIxOcc op = { d_bwt, S, n_words, k_end, sym0 }; if (int rc = lb_launch<2>(c, n_blk, op, st)) return rc; }
-	hipLaunchKernelGGL(k_ix_samples, dim3(ix_grid(n_sa)), dim3(IX_T), 0, st, n_sa, (const u32 *)SA, d_sa);
+	for (int sym0 = 0; sym0 < 4; sym0 += 2) { OpIxOcc op = { X.d_bwt, X.S, X.n_words, X.k_end, sym0 }; if (int rc = lb_launch<2>(c, X.n_blk, op, st)) return rc; }
+	return GSA_OK;
+}
+
+// primary, L2[5], bwt[bwt_words], sa[n_sa]: host
+int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds)
+{
+	hipStream_t st = c->stream;
+	hipEvent_t ev[2] = { nullptr, nullptr };
+	struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 2; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } evg{ ev };
+	IxSort X;      // (behind the events: its arrays are freed, after a wait for the stream, before they are destroyed)
+	GSA_CHECK(c, hipEventCreate(&ev[0])); GSA_CHECK(c, hipEventCreate(&ev[1]));
+	if (int rc = ix_sort(c, X, pac, G, true, ev[0], "gsa_build_index")) return rc;
+	if (int rc = ix_bwt_occ(c, X)) return rc;
+	const i64 S = X.S, n_bwt = X.n_bwt, n_sa = X.n_sa, k_end = X.k_end;
+	hipLaunchKernelGGL(k_ix_samples, dim3(ix_grid(n_sa)), dim3(IX_T), 0, st, n_sa, (const u32 *)X.SA, X.d_sa);
 	GSA_CHECK(c, hipGetLastError());
 	GSA_CHECK(c, hipEventRecord(ev[1], st));
 	u32 h_st[2] = { 0, 0 }; i32 lberr = 0;
-	GSA_CHECK(c, hipMemcpyAsync(h_st, d_st, 8, hipMemcpyDeviceToHost, st));
+	GSA_CHECK(c, hipMemcpyAsync(h_st, X.d_st, 8, hipMemcpyDeviceToHost, st));
 	GSA_CHECK(c, hipMemcpyAsync(&lberr, c->d_mail.as<i32>() + M_LBERR, 4, hipMemcpyDeviceToHost, st));
-	GSA_CHECK(c, hipMemcpyAsync(bwt, d_bwt, (size_t)n_bwt * 4, hipMemcpyDeviceToHost, st));
-	GSA_CHECK(c, hipMemcpyAsync(sa, d_sa, (size_t)n_sa * 8, hipMemcpyDeviceToHost, st));
+	GSA_CHECK(c, hipMemcpyAsync(bwt, X.d_bwt, (size_t)n_bwt * 4, hipMemcpyDeviceToHost, st));
+	GSA_CHECK(c, hipMemcpyAsync(sa, X.d_sa, (size_t)n_sa * 8, hipMemcpyDeviceToHost, st));
 	GSA_CHECK(c, hipStreamSynchronize(st));
 	if (lberr) return gsa_fail(c, GSA_ERR_STATE, "internal: look-back scan timed out");
 	float fms = 0; if (hipEventElapsedTime(&fms, ev[0], ev[1]) != hipSuccess) { fms = 0; (void)hipGetLastError(); }
@@ -246,6 +285,57 @@ int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 
 	L2[0] = 0;
 	for (int k = 0; k < 4; k++) L2[k + 1] = L2[k] + ((u64)bwt[k_end + 2 * k] | ((u64)bwt[k_end + 2 * k + 1] << 32));
 	if (L2[4] != (u64)S) return gsa_fail(c, GSA_ERR_STATE, "internal: gsa_build_index: the symbol counts do not add up");
-	*ms = (double)fms; *rounds = nr;
+	*ms = (double)fms; *rounds = X.rounds;
+	return GSA_OK;
+}
+
+// gsa_create_from_pac's device half: the index tables of a context straight from the sort, with no copy home and no LF walk.  The caller has set up the
+// context's own state, the chromosome tables, d_ref (2G + 64 bytes) and force_wide; this fills di.primary / L2 / seq_len, the Occ blocks (build_occ from the
+// file layout in a short-lived device buffer), the sampled SA, RefSequence (unpack_pac from the .pac bytes the sort uploaded) and the dense SA -- the
+// builder's own SA array, adopted as d_sa_dense (narrow layout; row 0 patched to the -1 sentinel) or widened into it (GSA_CREATE_WIDE).  Everything else the
+// builder allocated is freed before it returns, the sort scratch that grew inside the context included: the caller chooses the k-mer table's size from
+// the free device memory next.
+int build_tables_from_pac(gsa_ctx *c, const uint8_t *pac, i64 G)
+{
+	hipStream_t st = c->stream;
+	IxSort X;
+	auto drop_scratch = [&]() { if (c->tmp.p) { ctx_quiesce(c); (void)hipFree(c->tmp.p); c->tmp.p = nullptr; c->tmp.cap = 0; c->tmp.len = 0; } };
+	struct ScratchGuard { decltype(drop_scratch) &f; ~ScratchGuard() { f(); } } sg{ drop_scratch };
+	if (int rc = ix_sort(c, X, pac, G, false, nullptr, "gsa_create_from_pac")) return rc;
+	if (int rc = ix_bwt_occ(c, X)) return rc;
+	const i64 S = X.S, n = X.n, n_sa = X.n_sa;
+	u32 h_st[2] = { 0, 0 }, h_end[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; i32 lberr = 0;
+	GSA_CHECK(c, hipMemcpyAsync(h_st, X.d_st, 8, hipMemcpyDeviceToHost, st));
+	GSA_CHECK(c, hipMemcpyAsync(h_end, X.d_bwt + X.k_end, 32, hipMemcpyDeviceToHost, st));
+	GSA_CHECK(c, hipMemcpyAsync(&lberr, c->d_mail.as<i32>() + M_LBERR, 4, hipMemcpyDeviceToHost, st));      // (no fused pass runs below this point)
+	GSA_CHECK(c, hipStreamSynchronize(st));
+	if (lberr) return gsa_fail(c, GSA_ERR_STATE, "internal: look-back scan timed out");
+	c->di.primary = (u64)h_st[1]; c->di.L2[0] = 0;
+	for (int k = 0; k < 4; k++) c->di.L2[k + 1] = c->di.L2[k] + ((u64)h_end[2 * k] | ((u64)h_end[2 * k + 1] << 32));
+	if (c->di.L2[4] != (u64)S) return gsa_fail(c, GSA_ERR_STATE, "internal: gsa_create_from_pac: the symbol counts do not add up");
+	c->di.seq_len = (u64)S;
+	if (int rc = build_occ(c, X.d_bwt, (u64)((X.n_bwt + 15) / 16))) return rc;
+	if (hipMalloc(&c->d_sa.p, (size_t)n_sa * 8) != hipSuccess) { (void)hipGetLastError(); return gsa_fail(c, GSA_ERR_NOMEM, "hipMalloc (sampled SA)"); }
+	c->d_sa.cap = (size_t)n_sa * 8;
+	hipLaunchKernelGGL(k_ix_samples, dim3(ix_grid(n_sa)), dim3(IX_T), 0, st, n_sa, (const u32 *)X.SA, c->d_sa.as<u64>());
+	GSA_CHECK(c, hipGetLastError());
+	c->di.sa = c->d_sa.as<u64>();
+	if (int rc = unpack_pac(c, X.d_pac, G, c->d_ref.as<uint8_t>())) return rc;
+	// all but SA go now (the wide array is allocated into the room they leave)
+	X.B.release(X.SA);
+	struct SaGuard { u32 *p; hipStream_t st; ~SaGuard() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); (void)hipGetLastError(); } } } sag{ X.SA, st };
+	X.B.free_all();
+	drop_scratch();
+	if (!c->force_wide) {
+		GSA_CHECK(c, hipMemsetAsync(X.SA, 0xFF, 4, st));      // row 0: SA[0] = S here, the sa[0] = -1 sentinel there
+		c->d_sa_dense.p = X.SA; c->d_sa_dense.len = ((size_t)n + 32) * 4; c->d_sa_dense.cap = c->d_sa_dense.len + 256; sag.p = nullptr;      // (IxBufs::get's size is dev_ensure's exact size)
+		c->di.sa32 = c->d_sa_dense.as<u32>(); c->di.sa64 = nullptr;
+	} else {
+		if (!dev_ensure<u64>(c, c->d_sa_dense, (size_t)n + 32, true)) return GSA_ERR_NOMEM;
+		hipLaunchKernelGGL(k_ix_widen, dim3(ix_grid(n)), dim3(IX_T), 0, st, n, (const u32 *)X.SA, c->d_sa_dense.as<u64>());
+		GSA_CHECK(c, hipGetLastError());
+		c->di.sa64 = c->d_sa_dense.as<u64>(); c->di.sa32 = nullptr;
+	}
+	GSA_CHECK(c, hipStreamSynchronize(st));
 	return GSA_OK;
 }

@@ -209,15 +209,19 @@ int build_occ(gsa_ctx *c, const void *ref_layout, u64 n_blocks128)
 	return GSA_OK;
 }
 
-int build_dense_sa(gsa_ctx *c, u64 n_sa)
+// the three steps behind the Occ blocks, in the order gsa_create_opts runs them; gsa_create_from_pac has its dense SA from the sort and calls the other two
+int build_ref2(gsa_ctx *c)
 {
-	{
-		const u64 words = c->di.seq_len / 16 + 8;      // (the 64-base text window reads five words from any base)
-		if (!dev_ensure<u32>(c, c->d_ref2, words, true)) return GSA_ERR_NOMEM;
-		hipLaunchKernelGGL(k_pack_ref, dim3(grid_for(words, 256)), dim3(256), 0, c->stream, c->di.ref, c->di.seq_len, c->d_ref2.as<u32>(), words);
-		GSA_CHECK(c, hipGetLastError());
-		c->di.ref2 = c->d_ref2.as<u32>();
-	}
+	const u64 words = c->di.seq_len / 16 + 8;      // (the 64-base text window reads five words from any base)
+	if (!dev_ensure<u32>(c, c->d_ref2, words, true)) return GSA_ERR_NOMEM;
+	hipLaunchKernelGGL(k_pack_ref, dim3(grid_for(words, 256)), dim3(256), 0, c->stream, c->di.ref, c->di.seq_len, c->d_ref2.as<u32>(), words);
+	GSA_CHECK(c, hipGetLastError());
+	c->di.ref2 = c->d_ref2.as<u32>();
+	return GSA_OK;
+}
+
+int densify_sa(gsa_ctx *c, u64 n_sa)
+{
 	const u64 rows = c->di.seq_len + 1;
 	const bool use32 = c->di.seq_len < 0xFFFFFFF0ull && !c->force_wide;
 	if (use32) { if (!dev_ensure<u32>(c, c->d_sa_dense, rows + 32, true)) return GSA_ERR_NOMEM; c->di.sa32 = c->d_sa_dense.as<u32>(); c->di.sa64 = nullptr; }
@@ -225,41 +229,51 @@ int build_dense_sa(gsa_ctx *c, u64 n_sa)
 	hipLaunchKernelGGL(k_densify_sa, dim3(grid_for(n_sa, 256)), dim3(256), 0, c->stream, c->di, n_sa, (u32 *)c->di.sa32, (u64 *)c->di.sa64);
 	GSA_CHECK(c, hipGetLastError());
 	GSA_CHECK(c, hipStreamSynchronize(c->stream));
+	return GSA_OK;
+}
+
+int build_kmer_table(gsa_ctx *c)
+{
+	// k = ceil(log4(2G)) + 2: nearly all k-mers that occur are unique then (a 10 Mb text: 96 % at k = 14, 86 % at k = 13), so a
+	// search is table -> text comparison with no stepwise Occ walk in between -- each Occ step is a round trip AND the
+	// heaviest block of the search loop.  Capped at 15 and at a quarter of the free device memory (4^15 x 16 B = 16 GiB
+	// of the 288: a human-chromosome-sized text of 5 x 10^8 rows has 34 % unique k-mers at k = 14, 78 % at 15).
+	int k = 0; while ((1ull << (2 * k)) < c->di.seq_len) k++;
+	k += 2; if (k > 15) k = 15;      // (not beyond the default MinSeedLength: a start whose first 15 bases occur -- presence bitmap -- must find its entry, else it walks base by base)
 	{
-		// k = ceil(log4(2G)) + 2: nearly all k-mers that occur are unique then (a 10 Mb text: 96 % at k = 14, 86 % at k = 13), so a
-		// search is table -> text comparison with no stepwise Occ walk in between -- each Occ step is a round trip AND the
-		// heaviest block of the search loop.  Capped at 15 and at a quarter of the free device memory (4^15 x 16 B = 16 GiB
-		// of the 288: a human-chromosome-sized text of 5 x 10^8 rows has 34 % unique k-mers at k = 14, 78 % at 15).
-		int k = 0; while ((1ull << (2 * k)) < c->di.seq_len) k++;
-		k += 2; if (k > 15) k = 15;      // (not beyond the default MinSeedLength: a start whose first 15 bases occur -- presence bitmap -- must find its entry, else it walks base by base)
-		{
-			size_t fr = 0, tot = 0;
-			if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = 8ull << 30; }
-			const size_t esz = (c->di.seq_len < 0xFFFFFFF0ull && !c->force_wide) ? 16 : 32;
-			while (k > 2 && ((size_t)esz << (2 * k)) > fr / 4) k--;
-			if (c->opt.kmer_k) { const int kk = c->opt.kmer_k; if (kk >= 2 && kk <= 15 && ((size_t)esz << (2 * kk)) <= fr / 2) k = kk; }      // (GSA_CREATE_KMER_K; tests: a long table on a short text)
-		}
-		if (k >= 2) {
-			const size_t n = (size_t)1 << (2 * k);
-			const int e16 = (c->di.seq_len < 0xFFFFFFF0ull && !c->force_wide) ? 1 : 0;
-			{	// (exactly this size: dev_ensure's growth margin would be 16 GiB on the longest table)
-				const size_t bytes = (e16 ? n * 2 : n * 4) * sizeof(u64);
-				if (c->d_kmer.cap < bytes) {
-					if (c->d_kmer.p) { hipFree(c->d_kmer.p); c->d_kmer.p = nullptr; c->d_kmer.cap = 0; }
-					size_t got = 0;
-					if (void *r = dev_take_reserved(c->device, bytes, &got)) { c->d_kmer.p = r; c->d_kmer.cap = got; }
-					else {
-					if (hipMalloc(&c->d_kmer.p, bytes) != hipSuccess) { (void)hipGetLastError(); return gsa_fail(c, GSA_ERR_NOMEM, "hipMalloc (k-mer table)"); }
-					c->d_kmer.cap = bytes;
-					}
+		size_t fr = 0, tot = 0;
+		if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = 8ull << 30; }
+		const size_t esz = (c->di.seq_len < 0xFFFFFFF0ull && !c->force_wide) ? 16 : 32;
+		while (k > 2 && ((size_t)esz << (2 * k)) > fr / 4) k--;
+		if (c->opt.kmer_k) { const int kk = c->opt.kmer_k; if (kk >= 2 && kk <= 15 && ((size_t)esz << (2 * kk)) <= fr / 2) k = kk; }      // (GSA_CREATE_KMER_K; tests: a long table on a short text)
+	}
+	if (k >= 2) {
+		const size_t n = (size_t)1 << (2 * k);
+		const int e16 = (c->di.seq_len < 0xFFFFFFF0ull && !c->force_wide) ? 1 : 0;
+		{	// (exactly this size: dev_ensure's growth margin would be 16 GiB on the longest table)
+			const size_t bytes = (e16 ? n * 2 : n * 4) * sizeof(u64);
+			if (c->d_kmer.cap < bytes) {
+				if (c->d_kmer.p) { hipFree(c->d_kmer.p); c->d_kmer.p = nullptr; c->d_kmer.cap = 0; }
+				size_t got = 0;
+				if (void *r = dev_take_reserved(c->device, bytes, &got)) { c->d_kmer.p = r; c->d_kmer.cap = got; }
+				else {
+				if (hipMalloc(&c->d_kmer.p, bytes) != hipSuccess) { (void)hipGetLastError(); return gsa_fail(c, GSA_ERR_NOMEM, "hipMalloc (k-mer table)"); }
+				c->d_kmer.cap = bytes;
 				}
 			}
-			hipLaunchKernelGGL(k_build_kmer, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, c->di, k, c->d_kmer.as<u64>(), e16);
-			c->di.kmer_e16 = e16;
-			GSA_CHECK(c, hipGetLastError());
-			GSA_CHECK(c, hipStreamSynchronize(c->stream));
-			c->di.kmer = c->d_kmer.as<u64>(); c->di.kmer_k = k;
 		}
+		hipLaunchKernelGGL(k_build_kmer, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, c->di, k, c->d_kmer.as<u64>(), e16);
+		c->di.kmer_e16 = e16;
+		GSA_CHECK(c, hipGetLastError());
+		GSA_CHECK(c, hipStreamSynchronize(c->stream));
+		c->di.kmer = c->d_kmer.as<u64>(); c->di.kmer_k = k;
 	}
 	return GSA_OK;
+}
+
+int build_dense_sa(gsa_ctx *c, u64 n_sa)
+{
+	if (int rc = build_ref2(c)) return rc;
+	if (int rc = densify_sa(c, n_sa)) return rc;
+	return build_kmer_table(c);
 }

@@ -77,6 +77,24 @@ def build_index_gpu(fasta: str, prefix: str, device: int = 0) -> None:
     build_index_with(fasta, prefix, lambda pac, G: capi.build_index_arrays(pac, G, device))
 
 
+def reference_from_fasta(fasta: str):
+    """gsah_reference_from_fasta: (pac uint8[ceil(G / 4)], G, names, lens int32[]) of a reference FASTA -- what the index builder would put into .pac and .ann, with
+    no file written: the arguments of capi.Aligner.from_reference."""
+    lib = load()
+    lib.gsah_c_reference_from_fasta.argtypes = [C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_char_p]
+    lib.gsah_c_reference_pac.restype = C.POINTER(C.c_uint8)
+    lib.gsah_c_reference_name.restype = C.c_char_p
+    G, nb = C.c_longlong(), C.c_longlong()
+    err = C.create_string_buffer(256)
+    n = lib.gsah_c_reference_from_fasta(fasta.encode(), C.byref(G), C.byref(nb), err)
+    if n < 0:
+        raise RuntimeError(err.value.decode())
+    pac = np.ctypeslib.as_array(lib.gsah_c_reference_pac(), shape=(int(nb.value),)).copy()
+    names = [lib.gsah_c_reference_name(i).decode() for i in range(n)]
+    lens = np.array([lib.gsah_c_reference_len(i) for i in range(n)], dtype=np.int32)
+    return pac, int(G.value), names, lens
+
+
 def result_from_dump(d: dict, keep: list):
     """dict in the oracle/capi 'blocks_as_dump' layout -> a populated capi.Result (arrays appended to `keep`)."""
     nb = d["b_score"].size; nf = d["f_qpos"].size

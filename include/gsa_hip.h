@@ -145,6 +145,21 @@ int  gsa_create(int device, const gsa_index_view *idx, const gsa_params *prm, gs
  * that loop itself -- G / 4 bytes cross PCIe instead of 2G, and a host program can unpack its own copy (for its emitters) WHILE gsa_create builds the device tables. */
 #define GSA_CREATE_REF_PAC 4u
 int  gsa_create_opts(int device, const gsa_index_view *idx, const gsa_params *prm, uint32_t flags, gsa_ctx **out);
+/* A context from the reference SEQUENCE instead of from its index files: what bwa_idx_build (BWT_Index/bwtindex.c:77-149) followed by bwa_idx_load +
+ * RestoreReferenceInfo (bwt_index.cpp:147-264) amount to, with no file and no host array in between.  pac = ceil(G / 4) host bytes as gsa_build_index takes them;
+ * chr_len / n_chr / prm as in gsa_index_view / gsa_create; flags as for gsa_create_opts (GSA_CREATE_REF_PAC is implied and accepted).  The device sorts the 2G + 1
+ * suffixes (gsa_build_index's sorter), and its suffix array becomes the context's dense SA; Occ blocks, SA samples, both text forms and the k-mer tables follow on
+ * the device.  The context is the one gsa_create_opts makes from the index files of the same sequence -- the same device tables bit for bit -- and is cloned
+ * (gsa_clone, gsa_clone_to_device) and destroyed like it.  A reservation of gsa_reserve_index on `device` is released, not adopted.
+ * Errors in this order: NULL pointers, G <= 0, n_chr <= 0, sum(chr_len) != G, an unknown flag GSA_ERR_ARG; G > 1 073 741 822 GSA_ERR_LIMIT (before anything is
+ * allocated and before pac is read); no device GSA_ERR_HIP; ~52 bytes of device memory per suffix that are not there GSA_ERR_NOMEM.  gsa_last_error(NULL) has the text. */
+int  gsa_create_from_pac(int device, const uint8_t *pac, int64_t G, const int32_t *chr_len, int32_t n_chr, const gsa_params *prm, uint32_t flags, gsa_ctx **out);
+/* Test support: device table `which` of a context (its own, or the one it borrows) copied to dst[cap]; *bytes = its size, dst == NULL only reports it; an absent
+ * table reports 0.  Only the DEFINED extent of a table is exported: the dense SA seq_len + 1 entries, the Occ blocks the 2 x n_blocks uint4 that were written,
+ * ref2 the packed words.  GSA_TABLE_HEADER: 48 bytes {primary, L2[5]}. */
+enum { GSA_TABLE_HEADER = 0, GSA_TABLE_OCC = 1, GSA_TABLE_OCC_BASE = 2, GSA_TABLE_SA_DENSE = 3, GSA_TABLE_SA = 4, GSA_TABLE_KMER = 5, GSA_TABLE_KMER_LO = 6,
+       GSA_TABLE_PRES = 7, GSA_TABLE_REF = 8, GSA_TABLE_REF2 = 9 };
+int  gsa_export_index_table(gsa_ctx *ctx, int which, void *dst, uint64_t cap, uint64_t *bytes);
 /* Optional, before gsa_create: sets device memory aside for the two largest device tables of an index whose text has `seq_len` BWT rows (bwt_t::seq_len, the fifth
  * word of the .bwt header: structure.h:28-38) -- the dense suffix array and the k-mer table, 84 GB for a human index, ~0.4 s of hipMalloc -- so that a host can do that
  * while it is still READING the index files (the reference's bwa_idx_load reads first and allocates as it goes, bwt_index.cpp:147-227).  `flags` as for gsa_create_opts.
