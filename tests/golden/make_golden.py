@@ -15,6 +15,8 @@ What is written (all data, no reference source):
   cx_sen_stages.npz             same with -sen, stages 1..8
   ksw2_pairs.npz                2000+ (ref_frag, qry_frag) -> (aln1, aln2) from the reference's ksw2_alignment
   gapsim.npz                    CalGapSimilarity known answers on the cx pair
+  gapsim_edges.npz              CalGapSimilarity known answers on the windows of tests/edge_pairs.py (leaf_query): rows only, the columns of
+                                gapsim.npz plus a case id (`--gapsim-edges` writes only this)
   small.*                       a 60 kb two-contig pair with its own index, MAF, VCF (quick CLI test)
   cx_<variant>.{maf,aln,vcf}.gz outputs of the unmodified reference CLI on cx under -unique / -fmt 2 / -one / -idy 95 /
                                 -one -ind 40 -clr 300 -alen 1000 (`--cli-variants` writes only these)
@@ -81,6 +83,7 @@ def main():
     shutil.rmtree(tmp)
     cli_variants()
     dotplot_golden()
+    subprocess.run([sys.executable, os.path.abspath(__file__), "--gapsim-edges"], check=True)
     print("golden fixtures written to", HERE)
 
 
@@ -240,8 +243,28 @@ def func_vectors(tmp):
     print("ksw2 pairs:", len(s1s), " gapsim rows:", len(rows), " true:", sum(r[5] for r in rows))
 
 
+def gapsim_edges():
+    """The real reference's CalGapSimilarity on the edge windows of tests/edge_pairs.py, against that module's reference (one process: one index)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import edge_pairs as ep
+    op.build(ref=True)
+    assert op.have_ref(), "oracle/_ref missing: needs /root/reference"
+    tmp = tempfile.mkdtemp(prefix="gsa_golden_edges_")
+    refs, _ = ep.build_cases()
+    synth.write_fasta(f"{tmp}/r.fa", refs); op.ref_build_index(f"{tmp}/r.fa", f"{tmp}/r")
+    ref = op.RefLib(f"{tmp}/r")
+    q, rows, notes = ep.leaf_query()
+    ref.set_query(q, "edge_leaf")
+    out = [(0, q1, q2, r1, r2, ref.gap_similarity(int(q1), int(q2), int(r1), int(r2)), cid) for cid, q1, q2, r1, r2 in rows.tolist()]
+    np.savez_compressed(f"{HERE}/gapsim_edges.npz", rows=np.asarray(out, dtype=np.int64))
+    print("gapsim edge rows:", len(out), " true:", sum(r[5] for r in out))
+    shutil.rmtree(tmp)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 2 and sys.argv[1] == "--func":
+    if len(sys.argv) > 1 and sys.argv[1] == "--gapsim-edges":
+        gapsim_edges()
+    elif len(sys.argv) > 2 and sys.argv[1] == "--func":
         func_vectors(sys.argv[2])
     elif len(sys.argv) > 1 and sys.argv[1] == "--cli-variants":
         cli_variants()
