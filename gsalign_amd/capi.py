@@ -23,6 +23,7 @@ EXPORTS = [
     "gsa_prefetch_contig", "gsa_prefetch_bundle", "gsa_cancel_prefetch", "gsa_get_wall_sums", "gsa_get_alloc_stats", "gsa_debug_buffers", "gsa_set_option", "gsa_host_register", "gsa_host_unregister",
     "gsa_call_variants", "gsa_align_many_variants", "gsa_get_variant_timing",
     "gsa_block_cigars", "gsa_get_cigar_timing", "gsa_align_many_ex",
+    "gsa_block_cs", "gsa_get_cs_timing", "gsa_extras_cs",
     "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
     "gsa_create_from_pac", "gsa_export_index_table",
 ]
@@ -116,9 +117,19 @@ class Extras(C.Structure):
     _fields_ = [("var", C.POINTER(Variants)), ("cig", C.POINTER(Cigars))]
 
 
+class CsBlock(C.Structure):
+    """gsa_cs_block, 16 bytes (include/gsa_hip.h): where a block's cs string lies and its length."""
+    _fields_ = [("cs_off", C.c_int64), ("n_cs", C.c_int32), ("_pad", C.c_int32)]
+
+
+class Cs(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("n_bytes", C.c_int64), ("blk", C.POINTER(CsBlock)), ("cs", C.POINTER(C.c_char))]
+
+
+BLOCK_CS_DT = np.dtype([("cs_off", "<i8"), ("n_cs", "<i4"), ("_pad", "<i4")])
 BLOCK_CIGAR_DT = np.dtype([("cig_off", "<i8"), ("n_cig", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"), ("_pad", "<i4")])
 CIGAR_LETTERS = "MIDNSHP=X"      # by BAM op code; the library writes I (1), D (2), = (7) and X (8)
-WANT_VARIANTS, WANT_CIGARS = 1, 2
+WANT_VARIANTS, WANT_CIGARS, WANT_CS = 1, 2, 4
 
 
 def cigars_arrays(cig: "Cigars"):
@@ -127,6 +138,20 @@ def cigars_arrays(cig: "Cigars"):
     blk = np.ctypeslib.as_array(C.cast(cig.blk, C.POINTER(C.c_uint8)), shape=(nb * BLOCK_CIGAR_DT.itemsize,)).view(BLOCK_CIGAR_DT).copy() if nb else np.zeros(0, BLOCK_CIGAR_DT)
     ops = np.ctypeslib.as_array(cig.ops, shape=(no,)).copy() if no else np.zeros(0, np.uint32)
     return blk, ops
+
+
+def cs_arrays(cs: "Cs"):
+    """gsa_cs -> (BLOCK_CS_DT array, uint8 bytes), both copies; block b's string is bytes[cs_off : cs_off + n_cs]."""
+    nb, n = int(cs.n_blocks), int(cs.n_bytes)
+    blk = np.ctypeslib.as_array(C.cast(cs.blk, C.POINTER(C.c_uint8)), shape=(nb * BLOCK_CS_DT.itemsize,)).view(BLOCK_CS_DT).copy() if nb else np.zeros(0, BLOCK_CS_DT)
+    by = np.ctypeslib.as_array(C.cast(cs.cs, C.POINTER(C.c_uint8)), shape=(n,)).copy() if n else np.zeros(0, np.uint8)
+    return blk, by
+
+
+def cs_of_ops_length(ops) -> int:
+    """bytes of the cs string the ops imply: ':' and the decimal length for '=', 3 per 'X' column, 1 + the columns for 'I' / 'D'"""
+    ops = np.asarray(ops, dtype=np.uint32)
+    return int(sum((1 + len(str(int(o) >> 4))) if int(o) & 15 == 7 else (3 * (int(o) >> 4) if int(o) & 15 == 8 else 1 + (int(o) >> 4)) for o in ops))
 
 
 def cigar_string(ops) -> str:
@@ -282,7 +307,7 @@ class DeviceContig:
             self.lib.gsa_device_free(self.device, C.c_void_p(self.ptr)); self.ptr = None
 
 
-def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False) -> None:
+def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False) -> None:
     """gsa_align_many: `contigs` (uint8 arrays, or DeviceContig objects -- all of one kind) on the given contexts, one host
     thread per context inside the library.  on_result(contig_index, Result) runs on the worker threads (the Result is valid
     during the call only).  in_order: hand the contigs out as listed (GSA_MANY_IN_ORDER) instead of longest first.
@@ -292,7 +317,8 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     variants=True: gsa_align_many_variants -- the worker runs the variant pass first and on_result(contig_index, Result, Variants) gets its records too
     (variants_array copies them out).
     cigars=True: gsa_align_many_ex with GSA_WANT_CIGARS (and GSA_WANT_VARIANTS when variants=True) -- on_result(contig_index, Result, Variants or None, Cigars)
-    (cigars_arrays copies them out)."""
+    (cigars_arrays copies them out).
+    cs=True: GSA_WANT_CS as well (it implies the CIGARs) -- on_result gets a fifth argument, the contig's Cs (gsa_extras_cs; cs_arrays copies it out)."""
     lib = aligners[0].lib
     n = len(contigs)
     ctxs = (C.c_void_p * len(aligners))(*[a.ctx for a in aligners])
@@ -300,13 +326,22 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     qs = (C.c_char_p * n)(*[C.cast(c.ptr if on_dev else c.ctypes.data, C.c_char_p) for c in contigs])
     ql = (C.c_int32 * n)(*[int(c.size) for c in contigs])
     flags = (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16)
-    if cigars:
+    if cigars or cs:
+        lib.gsa_extras_cs.argtypes = [C.POINTER(Extras), C.POINTER(Cs)]
+
         def ex_cb(user, ci, res, ex):
             e = ex.contents
-            return int((on_result(ci, res.contents, e.var.contents if e.var else None, e.cig.contents if e.cig else None) if on_result else 0) or 0)
+            args = (ci, res.contents, e.var.contents if e.var else None, e.cig.contents if e.cig else None)
+            if cs:
+                s = Cs()
+                rc_cs = lib.gsa_extras_cs(ex, C.byref(s))
+                if rc_cs != 0:
+                    return int(rc_cs)
+                args += (s,)
+            return int((on_result(*args) if on_result else 0) or 0)
         cbx = RESULT_EX_FN(ex_cb)
         lib.gsa_align_many_ex.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.c_uint32, RESULT_EX_FN, C.c_void_p]
-        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, WANT_CIGARS | (WANT_VARIANTS if variants else 0), cbx, None)
+        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, WANT_CIGARS | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0), cbx, None)
     elif variants:
         cbv = RESULT_VAR_FN(lambda user, ci, res, var: int((on_result(ci, res.contents, var.contents) if on_result else 0) or 0))
         lib.gsa_align_many_variants.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_VAR_FN, C.c_void_p]
@@ -317,7 +352,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
         rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, flags, cb, None)
     if rc != 0:
         msgs = [lib.gsa_last_error(a.ctx).decode() for a in aligners]
-        raise GsaError(f"gsa_align_many{'_ex' if cigars else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
+        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
 
 
 def _p(a, t):
@@ -596,6 +631,20 @@ class Aligner:
         self.lib.gsa_block_cigars.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Cigars)]
         self._ck(self.lib.gsa_block_cigars(self.ctx, C.c_int32(k), C.byref(cig)))
         return cigars_arrays(cig)
+
+    def block_cs(self, k: int = 0):
+        """gsa_block_cs on the stage-8 result this context holds (contig k of a bundle): (BLOCK_CS_DT array, one entry per block; uint8 bytes of all strings)."""
+        cs = Cs()
+        self.lib.gsa_block_cs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Cs)]
+        self._ck(self.lib.gsa_block_cs(self.ctx, C.c_int32(k), C.byref(cs)))
+        return cs_arrays(cs)
+
+    def cs_timing(self):
+        """(host wall ms inside gsa_block_cs on this context since it was created, its CIGAR pass included; number of calls)."""
+        ms, n = C.c_double(0), C.c_int64(0)
+        self.lib.gsa_get_cs_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        self._ck(self.lib.gsa_get_cs_timing(self.ctx, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     def cigar_timing(self):
         """(host wall ms inside gsa_block_cigars on this context since it was created, number of calls)."""

@@ -378,7 +378,7 @@ int gsa_export_index_table(gsa_ctx *c, int which, void *dst, uint64_t cap, uint6
 }
 
 // every device buffer a context can own (gsa_destroy frees them; gsa_debug_buffers lists them)
-#define GSA_DEVBUFS(X) X(d_bwt) X(d_bwt_ref) X(d_occ_base) X(d_sa) X(d_ref) X(d_chr_end) X(d_chr_of_end) X(qs[0].d_query) X(qs[1].d_query) X(qs[0].d_bndtab) X(qs[1].d_bndtab) X(tmp) X(d_cnt) X(d_zero) X(d_mail) X(d_lb_status[0]) X(d_lb_status[1]) X(d_sa_dense) X(d_kmer) X(d_kmer_lo) X(d_pres) X(d_ref2) X(d_cand_s) X(d_cand_len) X(d_cand_x0) X(d_cand_freq) X(d_onpath) X(d_cand_cnt) X(d_heavy) X(dn_lf) X(dn_x0) X(d_chunk_hits) X(d_chunk_base) X(d_key_a) X(d_key_b) X(d_val_a) X(d_val_b) X(s_q) X(s_len) X(s_r) X(s_gid) X(d_flag) X(d_scan) X(g_beg) X(w_j0) X(d_pdbm) X(d_pdby) X(d_pdcb) X(d_gpre) X(d_key_c) X(d_val_c) X(a_q) X(a_len) X(a_r) X(a_gb) X(a_ge) X(a_uniq) X(a_cu) X(a_alive) X(a_ws) X(a_wid) X(a_next) X(a_brk) X(a_aurank) X(a_aulist) X(a_runinfo) X(w_best) X(w_sum) X(w_n) X(d_btab) X(d_flag2) X(d_scan2) X(d_i64a) X(b_q) X(b_len) X(b_r) X(b_gb) X(b_ge) X(c_q) X(c_len) X(c_r) X(c_gb) X(c_ge) X(c_bid) X(blk_beg) X(blk_end) X(blk_score) X(r_q) X(r_len) X(r_r) X(r_bid) X(r_tmp_q) X(r_tmp_len) X(r_tmp_r) X(r_tmp_bid) X(r_cut4) X(r_cut5) X(r_simjob) X(r_simres) X(d_leaf) X(fb_seedbase) X(fb_sbeg) X(fb_fragbase) X(f_rec) X(f_rec16) X(f_type) X(f_mism) X(f_alnlen) X(f_job) X(f_score) X(d_dp_lane_order) X(d_dp_bnd) X(d_dp_ctr) X(d_dp_jobs) X(d_dp_large) X(d_tail) X(e_id) X(e_rec) X(e_list) X(e_off1) X(e_off2) X(e_opsoff) X(e_nops) X(e_ops) X(e_rev) X(r_head) X(f_early) X(r_orig) X(r_tmp_orig) X(j_frag) X(j_opsoff) X(j_nops) X(d_ops) X(j_cells) X(d_alnoff) X(bl_alnlen) X(bl_score) X(d_bblk) X(d_dp_arena) X(d_vblk) X(d_vcnt) X(d_vwg) X(d_var) X(d_cblk) X(d_cout) X(d_ccnt) X(d_cwg) X(d_cpre) X(d_crun) X(d_cops) X(leaf[0]) X(leaf[1]) X(leaf[2]) X(leaf[3]) X(leaf[4]) X(leaf[5]) X(leaf[6]) X(leaf[7]) X(leaf[8])
+#define GSA_DEVBUFS(X) X(d_bwt) X(d_bwt_ref) X(d_occ_base) X(d_sa) X(d_ref) X(d_chr_end) X(d_chr_of_end) X(qs[0].d_query) X(qs[1].d_query) X(qs[0].d_bndtab) X(qs[1].d_bndtab) X(tmp) X(d_cnt) X(d_zero) X(d_mail) X(d_lb_status[0]) X(d_lb_status[1]) X(d_sa_dense) X(d_kmer) X(d_kmer_lo) X(d_pres) X(d_ref2) X(d_cand_s) X(d_cand_len) X(d_cand_x0) X(d_cand_freq) X(d_onpath) X(d_cand_cnt) X(d_heavy) X(dn_lf) X(dn_x0) X(d_chunk_hits) X(d_chunk_base) X(d_key_a) X(d_key_b) X(d_val_a) X(d_val_b) X(s_q) X(s_len) X(s_r) X(s_gid) X(d_flag) X(d_scan) X(g_beg) X(w_j0) X(d_pdbm) X(d_pdby) X(d_pdcb) X(d_gpre) X(d_key_c) X(d_val_c) X(a_q) X(a_len) X(a_r) X(a_gb) X(a_ge) X(a_uniq) X(a_cu) X(a_alive) X(a_ws) X(a_wid) X(a_next) X(a_brk) X(a_aurank) X(a_aulist) X(a_runinfo) X(w_best) X(w_sum) X(w_n) X(d_btab) X(d_flag2) X(d_scan2) X(d_i64a) X(b_q) X(b_len) X(b_r) X(b_gb) X(b_ge) X(c_q) X(c_len) X(c_r) X(c_gb) X(c_ge) X(c_bid) X(blk_beg) X(blk_end) X(blk_score) X(r_q) X(r_len) X(r_r) X(r_bid) X(r_tmp_q) X(r_tmp_len) X(r_tmp_r) X(r_tmp_bid) X(r_cut4) X(r_cut5) X(r_simjob) X(r_simres) X(d_leaf) X(fb_seedbase) X(fb_sbeg) X(fb_fragbase) X(f_rec) X(f_rec16) X(f_type) X(f_mism) X(f_alnlen) X(f_job) X(f_score) X(d_dp_lane_order) X(d_dp_bnd) X(d_dp_ctr) X(d_dp_jobs) X(d_dp_large) X(d_tail) X(e_id) X(e_rec) X(e_list) X(e_off1) X(e_off2) X(e_opsoff) X(e_nops) X(e_ops) X(e_rev) X(r_head) X(f_early) X(r_orig) X(r_tmp_orig) X(j_frag) X(j_opsoff) X(j_nops) X(d_ops) X(j_cells) X(d_alnoff) X(bl_alnlen) X(bl_score) X(d_bblk) X(d_dp_arena) X(d_vblk) X(d_vcnt) X(d_vwg) X(d_var) X(d_cblk) X(d_cout) X(d_ccnt) X(d_cwg) X(d_cpre) X(d_crun) X(d_cops) X(d_crpos) X(d_cqpos) X(d_slen) X(d_swg) X(d_spre) X(d_sout) X(d_cs) X(leaf[0]) X(leaf[1]) X(leaf[2]) X(leaf[3]) X(leaf[4]) X(leaf[5]) X(leaf[6]) X(leaf[7]) X(leaf[8])
 void gsa_destroy(gsa_ctx *c)
 {
 	if (!c) return;
@@ -395,7 +395,7 @@ void gsa_destroy(gsa_ctx *c)
 	for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
 	if (c->h_cnt) hipHostFree(c->h_cnt);
 	if (c->h_mail) hipHostFree(c->h_mail);
-	for (DevBuf *b : { &c->p_frags, &c->p_tail, &c->p_leaf, &c->p_blk, &c->p_dp, &c->p_sj, &c->p_sj_early, &c->p_jpatch, &c->p_early, &c->qs[0].p_bndtab, &c->qs[1].p_bndtab, &c->p_bblk, &c->p_ba0, &c->p_vblk, &c->p_vhdr, &c->p_var, &c->p_cblk, &c->p_chdr, &c->p_cout, &c->p_cops }) if (b->p) hipHostFree(b->p);
+	for (DevBuf *b : { &c->p_frags, &c->p_tail, &c->p_leaf, &c->p_blk, &c->p_dp, &c->p_sj, &c->p_sj_early, &c->p_jpatch, &c->p_early, &c->qs[0].p_bndtab, &c->qs[1].p_bndtab, &c->p_bblk, &c->p_ba0, &c->p_vblk, &c->p_vhdr, &c->p_var, &c->p_cblk, &c->p_chdr, &c->p_cout, &c->p_cops, &c->p_shdr, &c->p_sout, &c->p_cs }) if (b->p) hipHostFree(b->p);
 	for (int i = 0; i < 2; i++) if (c->ev_var[i]) hipEventDestroy(c->ev_var[i]);
 	for (int i = 0; i < 28; i++) if (c->ev[i]) hipEventDestroy(c->ev[i]);
 	for (int i = 0; i < 4; i++) if (c->stream_aux[i]) hipStreamDestroy(c->stream_aux[i]);
@@ -1135,6 +1135,44 @@ int gsa_get_cigar_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls)
 	return GSA_OK;
 }
 
+// the cs string of every block of the stage-8 result the context holds: k_cs.hip
+// (cig: the CIGARs the pass computed on its way, for gsa_align_many_ex -- they lie in the CIGAR pass's own buffers)
+static int cs_call(gsa_ctx *c, int32_t k, gsa_cs *out, gsa_cigars *cig)
+{
+	if (!c || !out) return GSA_ERR_ARG;
+	out->n_blocks = 0; out->n_bytes = 0; out->blk = nullptr; out->cs = nullptr;
+	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, "gsa_block_cs: the context holds no finished (stage 8) result");
+	// (the pass reads the contig's bases on the device: a prefetch into the slot that held them leaves another contig there)
+	if (c->q_cur == -2) return gsa_fail(c, GSA_ERR_STATE, "gsa_block_cs: the contig's device copy was overwritten by a prefetch");
+	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, "gsa_block_cs: contig index out of range");
+	GSA_CHECK(c, hipSetDevice(c->device));
+	const auto t0 = std::chrono::steady_clock::now();
+	const int rc = block_cs(c, k, out, cig);
+	c->cs_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->cs_calls++;
+	return rc;
+}
+
+int gsa_block_cs(gsa_ctx *c, int32_t k, gsa_cs *out) { return cs_call(c, k, out, nullptr); }
+
+int gsa_get_cs_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls)
+{
+	if (!c || !ms_sum || !n_calls) return GSA_ERR_ARG;
+	*ms_sum = c->cs_ms_sum; *n_calls = (int64_t)c->cs_calls;
+	return GSA_OK;
+}
+
+// what the callback of gsa_align_many_ex is handed: the public gsa_extras at the head, the answers of later passes behind it
+struct ExtrasFull { gsa_extras ex; const gsa_cs *cs; };
+int gsa_extras_cs(const gsa_extras *ex, gsa_cs *out)
+{
+	if (!ex || !out) return GSA_ERR_ARG;
+	out->n_blocks = 0; out->n_bytes = 0; out->blk = nullptr; out->cs = nullptr;
+	const gsa_cs *cs = ((const ExtrasFull *)ex)->cs;
+	if (!cs) return GSA_ERR_STATE;
+	*out = *cs;
+	return GSA_OK;
+}
+
 // ---- the index builder (k_index.hip) ----
 int gsa_index_sizes(int64_t G, uint64_t *bwt_words, uint64_t *n_sa)
 {
@@ -1179,10 +1217,12 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 	auto deliver = [&](gsa_ctx *c, int32_t k, int32_t ci, const gsa_result *res) -> int {
 		if (sk.on_var) { gsa_variants var; const int rcv = gsa_call_variants(c, k, &var); return rcv != GSA_OK ? rcv : sk.on_var(user, ci, res, &var); }
 		if (sk.on_ex) {
-			gsa_variants var; gsa_cigars cig; gsa_extras ex = { nullptr, nullptr };
+			gsa_variants var; gsa_cigars cig; gsa_cs cs; ExtrasFull full = { { nullptr, nullptr }, nullptr }; gsa_extras &ex = full.ex;
 			// (the variants are copied by no one before the CIGAR pass runs, and both live in buffers of their own: the second pass leaves the first one's answer alone)
 			if (sk.want & GSA_WANT_VARIANTS) { const int rcv = gsa_call_variants(c, k, &var); if (rcv != GSA_OK) return rcv; ex.var = &var; }
-			if (sk.want & GSA_WANT_CIGARS) { const int rcc = gsa_block_cigars(c, k, &cig); if (rcc != GSA_OK) return rcc; ex.cig = &cig; }
+			// (the cs pass runs the CIGAR walk itself, into the CIGAR pass's buffers: its ops are the ones handed out, no second walk)
+			if (sk.want & GSA_WANT_CS) { const int rcs = cs_call(c, k, &cs, &cig); if (rcs != GSA_OK) return rcs; full.cs = &cs; ex.cig = &cig; }
+			else if (sk.want & GSA_WANT_CIGARS) { const int rcc = gsa_block_cigars(c, k, &cig); if (rcc != GSA_OK) return rcc; ex.cig = &cig; }
 			return sk.on_ex(user, ci, res, &ex);
 		}
 		return sk.on_result ? sk.on_result(user, ci, res) : GSA_OK;
@@ -1334,7 +1374,7 @@ int gsa_align_many_variants(gsa_ctx *const *ctx, int32_t n_ctx, const char *cons
 }
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n, uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user)
 {
-	if (!on_result || (want & ~(uint32_t)(GSA_WANT_VARIANTS | GSA_WANT_CIGARS))) return GSA_ERR_ARG;
+	if (!on_result || (want & ~(uint32_t)(GSA_WANT_VARIANTS | GSA_WANT_CIGARS | GSA_WANT_CS))) return GSA_ERR_ARG;
 	ManySink sk; sk.on_ex = on_result; sk.want = want;
 	return align_many_impl(ctx, n_ctx, query, qlen, n, flags, sk, user);
 }

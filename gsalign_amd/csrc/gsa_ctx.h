@@ -238,6 +238,10 @@ struct gsa_ctx {
 	// pinned: block table in, header {ops, columns, records without a job}, block table out, ops ----
 	DevBuf d_cblk, d_cout, d_ccnt, d_cwg, d_cpre, d_crun, d_cops, p_cblk, p_chdr, p_cout, p_cops;
 	double cig_ms_sum = 0; long long cig_calls = 0;      // host wall time inside gsa_block_cigars (always on: two clock reads per call)
+	// ---- per-block cs strings (k_cs.hip): the runs' first positions (written by the CIGAR walk, block_cigars(.., pos)), per-op byte counts, per-workgroup sums, the ops' offsets,
+	// block table out, the bytes; pinned: header {bytes, blocks too long, bases out of range}, block table out, the bytes ----
+	DevBuf d_crpos, d_cqpos, d_slen, d_swg, d_spre, d_sout, d_cs, p_shdr, p_sout, p_cs;
+	double cs_ms_sum = 0; long long cs_calls = 0;        // host wall time inside gsa_block_cs, its CIGAR pass included
 	// what growing buffers cost this context (dev_ensure / pin_ensure: hipMalloc, hipHostMalloc, the frees and the quiesce in front of them) -- gsa_get_alloc_stats
 	double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 };
@@ -310,7 +314,9 @@ int stage78_extend(gsa_ctx *c);       // k_extend.hip  (S7: classification, DP, 
 int run_gapsim_jobs(gsa_ctx *c, i32 n, const i32 *d_n, const i32 *d_q1, const i32 *d_q2, const i64 *d_r1, const i64 *d_r2, i32 *d_res, const i32 *d_jseed, i32 *d_cut4);   // k_gapsim.hip
 void dp_count_cells(gsa_ctx *c, i32 n_ub, const i32 *len1, const i32 *len2, hipStream_t stream);   // k_dp.hip (profiling)
 int call_variants(gsa_ctx *c, i32 k, gsa_variants *out);   // k_variants.hip  (VariantIdentification over the stage-8 result of contig k)
-int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out);      // k_cigar.hip  (the CIGAR of every block of the stage-8 result of contig k)
+struct CigBlk { i64 frag_off; i32 n_frag, bdir, wbase, _pad; };      // one block of the result, ALL of them, in result order: first record (absolute), records, strand, first work item; entry [nb]: wbase = W  (k_cigar.hip's block table d_cblk, read by k_cs.hip too)
+int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out, bool pos = false);      // k_cigar.hip  (the CIGAR of every block of the stage-8 result of contig k; pos: the runs' first positions too, into d_crpos / d_cqpos)
+int block_cs(gsa_ctx *c, i32 k, gsa_cs *out, gsa_cigars *cig_out = nullptr);   // k_cs.hip  (the cs string of every block: the CIGAR pass with positions, then its own three passes; cig_out: that CIGAR pass's answer)
 int ctx_create_bare(int device, gsa_ctx **out);            // gsa_api.hip  (a context with NO index: device, stream, mailbox and scratch -- what the sort and the fused passes need; gsa_destroy frees it)
 int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds);   // k_index.hip  (suffix sort + BWT / Occ / SA samples of forward + reverse complement)
 struct LgJob { i32 job, m, n; };

@@ -92,6 +92,7 @@ template struct RawArr<gsa_rec>;
 template struct RawArr<char>;
 template struct RawArr<gsa_variant>;
 template struct RawArr<gsa_block_cigar>;
+template struct RawArr<gsa_cs_block>;
 template struct RawArr<uint32_t>;
 void ContigResult::assign(const gsa_result &r, bool summary_mode)
 {
@@ -381,9 +382,79 @@ void gsah_cigar_trim(const uint32_t *ops, int bdir, int64_t ext, std::vector<uin
 	bc.n_cig = (int32_t)out.size();
 }
 
-void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink) const
+namespace {
+inline char cs_letter(char b, bool fwd) { return (fwd ? "acgtn" : "tgcan")[nt4((unsigned char)b)]; }
+inline void cs_number(std::string &out, uint64_t v) { char tmp[24]; int n = 0; do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v); while (n) out.push_back(tmp[--n]); }
+inline int64_t cs_op_bytes(uint32_t op)
 {
-	std::vector<gsa_block_cigar> own_blk; std::vector<uint32_t> own_ops, cut;
+	const uint32_t len = op >> 4, cls = op & 15u;
+	if (cls != GSA_CIGAR_EQ) return cls == GSA_CIGAR_X ? 3 * (int64_t)len : 1 + (int64_t)len;
+	int64_t n = 2; for (uint32_t v = len; v >= 10; v /= 10) n++;
+	return n;
+}
+}
+
+void gsah_block_cs(const ContigResult &r, std::vector<gsa_cs_block> &blk, std::string &cs)
+{
+	blk.assign(r.blocks.size(), gsa_cs_block());
+	cs.clear();
+	std::vector<uint8_t> cls; std::string t1, t2;      // the block's columns in walk order: class, reference row, query row (a seed's rows are not looked at)
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		cls.clear(); t1.clear(); t2.clear();
+		for (int64_t k = 0; k < b.n_frag; k++) {
+			const gsa_frag f = r.frag(b.frag_off + k);
+			if (f.bseed) { if (f.qlen > 0) { cls.insert(cls.end(), (size_t)f.qlen, (uint8_t)GSA_CIGAR_EQ); t1.append((size_t)f.qlen, 'A'); t2.append((size_t)f.qlen, 'A'); } }
+			else {
+				const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+				for (int i = 0; i < f.aln_len; i++) cls.push_back((uint8_t)column_class(x1[i], x2[i]));
+				if (f.aln_len > 0) { t1.append(x1, (size_t)f.aln_len); t2.append(x2, (size_t)f.aln_len); }
+			}
+		}
+		const bool fwd = b.bdir != 0;
+		if (!fwd) { std::reverse(cls.begin(), cls.end()); std::reverse(t1.begin(), t1.end()); std::reverse(t2.begin(), t2.end()); }      // SelfComplementarySeq
+		const size_t at = cs.size();
+		for (size_t i = 0; i < cls.size();) {
+			size_t j = i; while (j < cls.size() && cls[j] == cls[i]) j++;
+			if (cls[i] == GSA_CIGAR_EQ) { cs.push_back(':'); cs_number(cs, j - i); }
+			else if (cls[i] == GSA_CIGAR_X) { for (size_t k = i; k < j; k++) { cs.push_back('*'); cs.push_back(cs_letter(t1[k], fwd)); cs.push_back(cs_letter(t2[k], fwd)); } }
+			else if (cls[i] == GSA_CIGAR_INS) { cs.push_back('+'); for (size_t k = i; k < j; k++) cs.push_back(cs_letter(t2[k], fwd)); }
+			else { cs.push_back('-'); for (size_t k = i; k < j; k++) cs.push_back(cs_letter(t1[k], fwd)); }
+			i = j;
+		}
+		blk[bi].cs_off = (int64_t)at; blk[bi].n_cs = (int32_t)(cs.size() - at); blk[bi]._pad = 0;
+	}
+}
+
+void gsah_cs_trim(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, int bdir, int64_t ext, std::string &out)
+{
+	out.clear();
+	int64_t lo = 0, hi = n_ops, b0 = 0, b1 = n;      // the ops that stay whole: [lo, hi), their bytes: [b0, b1)
+	std::string edge;                                // what is left of the op at the cut
+	while (ext > 0 && lo < hi) {
+		const int64_t at = bdir ? hi - 1 : lo;
+		const uint32_t cls = ops[at] & 15u; const int64_t len = ops[at] >> 4, bytes = cs_op_bytes(ops[at]);
+		const int64_t take = len <= ext ? len : ext;
+		ext -= take;
+		const int64_t p = bdir ? b1 - bytes : b0;    // the op's first byte
+		if (bdir) { hi--; b1 -= bytes; } else { lo++; b0 += bytes; }
+		if (take == len) continue;
+		const int64_t keep = len - take;
+		if (p < 0 || p + bytes > n) break;           // (a string that is not the ops': nothing is read outside it)
+		if (cls == GSA_CIGAR_EQ) { edge.push_back(':'); cs_number(edge, (uint64_t)keep); }
+		else if (cls == GSA_CIGAR_X) edge.assign(cs + p + (bdir ? 0 : 3 * take), (size_t)(3 * keep));
+		else { edge.push_back(cs[p]); edge.append(cs + p + 1 + (bdir ? 0 : take), (size_t)keep); }
+	}
+	if (b1 > n) b1 = n;
+	if (!bdir) out += edge;
+	if (b1 > b0) out.append(cs + b0, (size_t)(b1 - b0));
+	if (bdir) out += edge;
+}
+
+void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink,
+                       const gsa_cs_block *csb, const char *cs) const
+{
+	std::vector<gsa_block_cigar> own_blk; std::vector<uint32_t> own_ops, cut; std::string cs_cut;
 	if (!blk && r.summary) return;      // (the comparator walks records and strings a summary result does not hold)
 	if (!blk) { gsah_block_cigars(q.seq.data(), r, own_blk, own_ops); blk = own_blk.data(); ops = own_ops.data(); }
 	OutBuf o;
@@ -397,6 +468,8 @@ void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_ci
 		const int ext = extension(*idx, b, last);
 		gsa_block_cigar bc = blk[bi];
 		const uint32_t *bo = ops + bc.cig_off;
+		const char *bcs = csb ? cs + csb[bi].cs_off : nullptr; size_t n_bcs = csb ? (size_t)csb[bi].n_cs : 0;
+		if (csb && ext > 0) { gsah_cs_trim(bcs, (int64_t)n_bcs, bo, bc.n_cig, b.bdir, ext, cs_cut); bcs = cs_cut.data(); n_bcs = cs_cut.size(); }      // (from the untrimmed ops)
 		if (ext > 0) {      // (as maf_block: the block and its last record are shortened for whoever looks at them next -- the variant walk, the dot plot)
 			b.aln_len -= ext; b.score -= ext; last.rlen -= ext; last.qlen -= ext; r.trim(fl, ext);
 			gsah_cigar_trim(bo, b.bdir, ext, cut, bc); bo = cut.data();
@@ -412,7 +485,7 @@ void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_ci
 			int d, c, g; idx->coordinate(last.rpos + last.rlen - 1, &d, &c, &g); ts = g - 1;
 		}
 		const std::string &rname = idx->chr_name[b.chr];
-		o.reserve(o.n + q.name.size() + rname.size() + 256 + (size_t)bc.n_cig * 11);
+		o.reserve(o.n + q.name.size() + rname.size() + 256 + (size_t)bc.n_cig * 11 + n_bcs);
 		char *w = o.p + o.n;
 		memcpy(w, q.name.data(), q.name.size()); w += q.name.size(); *w++ = '\t';
 		w = put_int(w, qsize); *w++ = '\t'; w = put_int(w, qs); *w++ = '\t'; w = put_int(w, qe); *w++ = '\t';
@@ -423,6 +496,7 @@ void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_ci
 		w = put_int(w, (long long)bc.n_x + bc.n_ins + bc.n_del); memcpy(w, "\tAS:i:", 6); w += 6;
 		w = put_int(w, b.bdup ? 1 : b.score); memcpy(w, b.bdup ? "\ttp:A:S\tcg:Z:" : "\ttp:A:P\tcg:Z:", 13); w += 13;
 		w += gsa_cigar_string(bo, bc.n_cig, w, (size_t)bc.n_cig * 11 + 1);
+		if (csb) { memcpy(w, "\tcs:Z:", 6); w += 6; if (n_bcs) memcpy(w, bcs, n_bcs); w += n_bcs; }
 		*w++ = '\n';
 		o.n = (size_t)(w - o.p);
 		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
@@ -430,9 +504,9 @@ void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_ci
 	if (o.n) sink(std::move(o));
 }
 
-void Emitter::paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops) const
+void Emitter::paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const gsa_cs_block *csb, const char *cs) const
 {
-	paf_text(q, r, blk, ops, [&](OutBuf &&o) { if (o.n) fwrite(o.p, 1, o.n, fp); });
+	paf_text(q, r, blk, ops, [&](OutBuf &&o) { if (o.n) fwrite(o.p, 1, o.n, fp); }, csb, cs);
 }
 
 void Emitter::aln(FILE *fp, const QueryContig &q, ContigResult &r) const

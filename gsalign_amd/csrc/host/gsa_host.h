@@ -108,6 +108,12 @@ void gsah_block_cigars(const char *seq, const ContigResult &r, std::vector<gsa_b
 // iExtension's trim (tools.cpp:192-202) on a block's ops: the last `ext` columns IN WALK ORDER go -- the last ops of a forward block, the FIRST ones of a
 // reverse-strand block (its ops are in output order).  out = the ops that stay; bc's op count and columns per class are reduced by what was removed.
 void gsah_cigar_trim(const uint32_t *ops, int bdir, int64_t ext, std::vector<uint32_t> &out, gsa_block_cigar &bc);
+// The cs string of every block of a finished contig (gsa_cs_block / bytes as in gsa_hip.h), UNTRIMMED: the walk of gsah_block_cigars over the records and the two
+// gapped strings that also writes the tokens -- the comparator of gsa_block_cs.  It needs only the strings: a seed is ":len".
+void gsah_block_cs(const ContigResult &r, std::vector<gsa_cs_block> &blk, std::string &cs);
+// iExtension's trim on ONE block's cs string (cs[n], the string of the block's untrimmed ops[n_ops], output order): the columns gsah_cigar_trim drops go -- the
+// tail of a forward block's string, the head of a reverse-strand block's -- and a cut ":n" is printed again.  out = the cs of the trimmed ops.
+void gsah_cs_trim(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, int bdir, int64_t ext, std::string &out);
 
 struct OutBuf;                             // par.h
 
@@ -126,8 +132,10 @@ struct Emitter {
 	// PAF: one line per block with its cg:Z: CIGAR, blocks selected and trimmed (iExtension) like OutputMAF's; blk / ops = the contig's CIGARs from gsa_block_cigars,
 	// or NULL: computed here (gsah_block_cigars).  Shortens the last record of a block exactly as maf_block does.  A summary result (ContigResult::summary) must
 	// bring its CIGARs: the first and last record of block bi are recs[2 bi] and recs[2 bi + 1], and no string is touched.
-	void paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink) const;
-	void paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops) const;
+	// csb / cs (optional; they need blk / ops) = the contig's cs strings from gsa_block_cs: every line gets "\tcs:Z:<string>" behind its cg:Z: field, trimmed like the ops.
+	void paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink,
+	              const gsa_cs_block *csb = nullptr, const char *cs = nullptr) const;
+	void paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const gsa_cs_block *csb = nullptr, const char *cs = nullptr) const;
 	// OutputAlignment (tools.cpp:222-286)
 	void aln(FILE *fp, const QueryContig &q, ContigResult &r) const;
 	// OutputDotplot (DotPloting.cpp:10-71): gnuplot script `gp_path` + one data file per plotted reference sequence

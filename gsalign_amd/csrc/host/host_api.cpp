@@ -120,9 +120,25 @@ int gsah_c_emit(const char *index_prefix, const char *query_fa, const char *maf_
 	return gsah_c_emit_fmt(index_prefix, query_fa, maf_path, vcf_path, reference_label, allow_dup, 1, cb, user, err);
 }
 
+static int emit_impl(const char *index_prefix, const char *query_fa, const char *maf_path, const char *vcf_path, const char *reference_label,
+                     int allow_dup, int fmt, bool with_cs, gsah_result_cb cb, void *user, char *err);
+
 // fmt 1: MAF (OutputMAF), fmt 2: ALN (OutputAlignment) -- the -fmt flag of the CLI (main.cpp:284); fmt 3: PAF, the CIGARs from the host comparator (gsah_block_cigars)
 int gsah_c_emit_fmt(const char *index_prefix, const char *query_fa, const char *maf_path, const char *vcf_path, const char *reference_label,
                     int allow_dup, int fmt, gsah_result_cb cb, void *user, char *err)
+{
+	return emit_impl(index_prefix, query_fa, maf_path, vcf_path, reference_label, allow_dup, fmt, false, cb, user, err);
+}
+
+// fmt 3 with a cs:Z: field behind every cg:Z: (the -cs flag of the CLI): CIGARs and cs strings from the host comparators (gsah_block_cigars, gsah_block_cs)
+int gsah_c_emit_paf_cs(const char *index_prefix, const char *query_fa, const char *paf_path, const char *vcf_path, const char *reference_label,
+                       int allow_dup, gsah_result_cb cb, void *user, char *err)
+{
+	return emit_impl(index_prefix, query_fa, paf_path, vcf_path, reference_label, allow_dup, 3, true, cb, user, err);
+}
+
+static int emit_impl(const char *index_prefix, const char *query_fa, const char *maf_path, const char *vcf_path, const char *reference_label,
+                     int allow_dup, int fmt, bool with_cs, gsah_result_cb cb, void *user, char *err)
 {
 	std::string e; HostIndex idx; std::vector<QueryContig> qs;
 	if (!gsah_load_index(index_prefix, idx, e) || !gsah_load_query(query_fa, qs, e)) { if (err) { strncpy(err, e.c_str(), 255); err[255] = 0; } return -1; }
@@ -134,7 +150,11 @@ int gsah_c_emit_fmt(const char *index_prefix, const char *query_fa, const char *
 		ContigResult cr; cr.assign(res);
 		FILE *fp = fopen(maf_path, ci == 0 ? "w" : "a");         // tools.cpp:158-163
 		if (!fp) { if (err) strcpy(err, "cannot open MAF output"); return -3; }
-		if (fmt == 3) em.paf(fp, qs[ci], cr, nullptr, nullptr); else if (fmt == 2) em.aln(fp, qs[ci], cr); else em.maf(fp, ci == 0, qs[ci], cr);
+		if (fmt == 3 && with_cs) {
+			std::vector<gsa_block_cigar> cb_blk; std::vector<uint32_t> cb_ops; std::vector<gsa_cs_block> cs_blk; std::string cs;
+			gsah_block_cigars(qs[ci].seq.data(), cr, cb_blk, cb_ops); gsah_block_cs(cr, cs_blk, cs);
+			em.paf(fp, qs[ci], cr, cb_blk.data(), cb_ops.data(), cs_blk.data(), cs.data());
+		} else if (fmt == 3) em.paf(fp, qs[ci], cr, nullptr, nullptr); else if (fmt == 2) em.aln(fp, qs[ci], cr); else em.maf(fp, ci == 0, qs[ci], cr);
 		fclose(fp);
 		em.variants((int)ci, qs[ci], cr);
 	}
@@ -223,6 +243,31 @@ int gsah_c_cigar_trim(const uint32_t *ops, int bdir, long long ext, uint32_t *ou
 	gsah_cigar_trim(ops, bdir, ext, o, *bc);
 	if (!o.empty()) memcpy(out, o.data(), o.size() * sizeof(uint32_t));
 	return (int)o.size();
+}
+
+// The cs string of every block of one finished contig (gsa_cs_block / bytes, gsa_hip.h), on the host, from the gapped strings and seed records, untrimmed: what
+// gsa_block_cs gives.  blk[res->n_blocks] is always filled; cs[cap]; returns the number of bytes (call with cap = 0 to size `cs`), < 0 on error.  Needs no index.
+long long gsah_c_cs(const gsa_result *res, gsa_cs_block *blk, char *cs, long long cap)
+{
+	if (!res || (res->n_blocks > 0 && !blk) || (cap > 0 && !cs)) return -1;
+	ContigResult cr; cr.assign(*res);
+	std::vector<gsa_cs_block> b; std::string o;
+	gsah_block_cs(cr, b, o);
+	if (!b.empty()) memcpy(blk, b.data(), b.size() * sizeof(gsa_cs_block));
+	const size_t m = std::min<size_t>(o.size(), cap > 0 ? (size_t)cap : 0);
+	if (m) memcpy(cs, o.data(), m);
+	return (long long)o.size();
+}
+
+// gsah_cs_trim on one block's string cs[n] (of its untrimmed ops[n_ops]): out[n] receives the string that stays; returns its length
+long long gsah_c_cs_trim(const char *cs, long long n, const uint32_t *ops, long long n_ops, int bdir, long long ext, char *out)
+{
+	if (n < 0 || n_ops < 0 || (n > 0 && (!cs || !out)) || (n_ops > 0 && !ops)) return -1;
+	std::string o;
+	gsah_cs_trim(cs, n, ops, n_ops, bdir, ext, o);
+	if (o.size() > (size_t)n) return -2;
+	if (!o.empty()) memcpy(out, o.data(), o.size());
+	return (long long)o.size();
 }
 
 // OutputDotplot for one contig: script + data files (no gnuplot run).  Returns 1 if something was written.

@@ -50,6 +50,7 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -gpu   LIST    GPU ordinals, comma separated [0]\n");
 	fprintf(stderr, "         -ctx   INT     contexts per GPU working on different query sequences [2]\n");
 	fprintf(stderr, "         -timing        print where the wall time went (one JSON line on stderr)\n");
+	fprintf(stderr, "         -cs            with -fmt 3: add the cs:Z: difference string (short form) of every alignment, computed on the GPU (gsa_block_cs) [false]\n");
 	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
 	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index), references up to 1.07 Gbp [false]\n", prog);
 	fprintf(stderr, "         -memindex      with -r: build the index in GPU memory (gsa_create_from_pac) and align against it; no index file is written or read, references up to 1.07 Gbp [false]\n\n");
@@ -104,7 +105,7 @@ int main(int argc, char *argv[])
 	//  kernel and faulting it in again for the next contig)
 	mallopt(M_MMAP_THRESHOLD, 1 << 30); mallopt(M_TRIM_THRESHOLD, 1 << 30); mallopt(M_TOP_PAD, 256 << 20);
 	gsa_params prm; gsa_default_params(&prm);
-	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
+	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, want_cs = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
 	std::vector<int> gpus;
 	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL;
 	if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(argv[0], threads, prm, fmt); return 0; }
@@ -136,6 +137,7 @@ int main(int argc, char *argv[])
 		else if (a == "-ctx" && i + 1 < argc) { n_ctx_per_gpu = atoi(argv[++i]); if (n_ctx_per_gpu < 1) n_ctx_per_gpu = 1; }
 		else if (a == "-timing") timing = true;
 		else if (a == "-gpuvar") gpuvar = true;
+		else if (a == "-cs") want_cs = true;
 		else if (a == "-gpuindex") gpuindex = true;
 		else if (a == "-memindex") memindex = true;
 		else if (a == "-dp") dotplot = true;
@@ -146,6 +148,7 @@ int main(int argc, char *argv[])
 	}
 	if ((index_prefix == NULL && ref_fa == NULL) || query_fa == NULL) { usage(argv[0], threads, prm, fmt); return 0; }
 	if (out_prefix == NULL) out_prefix = "output"; else if (!check_prefix(out_prefix)) return 0;
+	if (want_cs && fmt != 3) { fprintf(stderr, "Warning! -cs adds the cs:Z: field to PAF lines (-fmt 3) only: ignored\n"); want_cs = false; }
 	HostPool::global().resize(threads < 1 ? 1 : (threads > 256 ? 256 : threads));
 
 	const time_t t0 = time(NULL);
@@ -274,8 +277,9 @@ int main(int argc, char *argv[])
 		std::mutex mu; std::condition_variable cv; std::vector<ContigResult> res; std::vector<char> ready; bool abort = false; double copy_s = 0;
 		std::vector<RawArr<gsa_variant> > var;      // -gpuvar: the contig's variants as gsa_call_variants left them
 		std::vector<RawArr<gsa_block_cigar> > cblk; std::vector<RawArr<uint32_t> > cops;      // -fmt 3: the contig's CIGARs as gsa_block_cigars left them
+		std::vector<RawArr<gsa_cs_block> > sblk; std::vector<RawArr<char> > sbytes; bool want_cs = false;      // -cs: the contig's cs strings as gsa_block_cs left them
 	} sink;
-	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size());
+	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size()); sink.sblk.resize(qs.size()); sink.sbytes.resize(qs.size()); sink.want_cs = want_cs;
 	const bool var_on_gpu = gpuvar && vcf;          // (-no_vcf: nobody reads the variants)
 	// the MAF file: created by the first contig that has alignments ("w" for contig 0, "a" afterwards: tools.cpp:158-163 -- a run whose
 	// first contig aligns nowhere appends to whatever the file held, as the reference does)
@@ -300,9 +304,12 @@ int main(int argc, char *argv[])
 			}
 			if (maf_w && fmt == 3 && sink.cblk[ci].size() != cr.blocks.size()) {      // (never the host comparator in place of a missing device answer)
 				out_failed = true; fprintf(stderr, "Error! %d blocks, CIGARs of %d\n", (int)cr.blocks.size(), (int)sink.cblk[ci].size());
-			} else if (maf_w && fmt == 3) em.paf_text(qs[ci], cr, sink.cblk[ci].data(), sink.cops[ci].data(), [&](OutBuf &&o) { maf_w->push(std::move(o)); });
+			} else if (maf_w && fmt == 3 && want_cs && sink.sblk[ci].size() != cr.blocks.size()) {
+				out_failed = true; fprintf(stderr, "Error! %d blocks, cs strings of %d\n", (int)cr.blocks.size(), (int)sink.sblk[ci].size());
+			} else if (maf_w && fmt == 3) em.paf_text(qs[ci], cr, sink.cblk[ci].data(), sink.cops[ci].data(), [&](OutBuf &&o) { maf_w->push(std::move(o)); },
+			                                          want_cs ? sink.sblk[ci].data() : nullptr, want_cs ? sink.sbytes[ci].data() : nullptr);
 			else if (maf_w) em.maf_text(ci == 0, qs[ci], cr, [&](OutBuf &&o) { maf_w->push(std::move(o)); }, [&](size_t c) { return maf_w->take(c); });
-			sink.cblk[ci].reset(); sink.cops[ci].reset();
+			sink.cblk[ci].reset(); sink.cops[ci].reset(); sink.sblk[ci].reset(); sink.sbytes[ci].reset();
 			t_maf_fmt += now_s() - t;
 		}
 		if (fmt == 2) {
@@ -364,6 +371,11 @@ int main(int argc, char *argv[])
 		sk.res[(size_t)ci].assign(*res);
 		if (ex->var) sk.var[(size_t)ci].assign(ex->var->v, (size_t)ex->var->n);
 		if (ex->cig) { sk.cblk[(size_t)ci].assign(ex->cig->blk, (size_t)ex->cig->n_blocks); sk.cops[(size_t)ci].assign(ex->cig->ops, (size_t)ex->cig->n_ops); }
+		if (sk.want_cs) {
+			gsa_cs cs;
+			if (gsa_extras_cs(ex, &cs) != GSA_OK) return 1;
+			sk.sblk[(size_t)ci].assign(cs.blk, (size_t)cs.n_blocks); sk.sbytes[(size_t)ci].assign(cs.cs, (size_t)cs.n_bytes);
+		}
 		const double dt = now_s() - t;
 		{ std::lock_guard<std::mutex> lk(sk.mu); sk.ready[(size_t)ci] = 1; sk.copy_s += dt; }
 		sk.cv.notify_all();
@@ -371,18 +383,20 @@ int main(int argc, char *argv[])
 	};
 	if (timing && var_on_gpu) for (gsa_ctx *c : ctxs) (void)gsa_set_profiling(c, 8);      // (the variant passes' device time, for the GSA_VARIANT_PASS line)
 	const double ta = now_s(); t_at_align = ta - T0;
-	const int rc_many = fmt == 3 ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, GSA_WANT_CIGARS | (var_on_gpu ? GSA_WANT_VARIANTS : 0u), on_result_ex, &sink)
+	const int rc_many = fmt == 3 ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, GSA_WANT_CIGARS | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u), on_result_ex, &sink)
 	                  : var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
 	                               : gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
 	t_align = now_s() - ta;
 	// where the contexts' host threads spent that time (gsa_get_wall_sums: [0] query set-up / wait for the upload, [s] stage s) and what growing buffers cost them
 	if (timing && getenv("GSA_DUMP_BUFFERS")) for (gsa_ctx *c : ctxs) (void)gsa_debug_buffers(c, 24);
 	double cigar_ms = 0;      // -fmt 3: wall time the workers spent inside gsa_block_cigars, all contexts
+	double cs_ms = 0;         // -cs: the same of gsa_block_cs (which runs the CIGAR walk itself: cigar_s is 0 then)
 	double var_dev_ms = 0; long long var_dev_n = 0;      // -gpuvar: device time of the variant passes (hipEvents), all contexts
 	double wall_sum[10] = { 0 }; double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 	for (gsa_ctx *c : ctxs) {
 		double w[10]; int64_t wn = 0; if (gsa_get_wall_sums(c, w, &wn) == GSA_OK) for (int k = 0; k < 9; k++) wall_sum[k] += w[k];
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_cigar_timing(c, &cm, &cn) == GSA_OK) cigar_ms += cm; }
+		{ double cm = 0; int64_t cn = 0; if (gsa_get_cs_timing(c, &cm, &cn) == GSA_OK) cs_ms += cm; }
 		double vm = 0; int64_t vn = 0; if (gsa_get_variant_timing(c, &vm, &vn) == GSA_OK) { var_dev_ms += vm; var_dev_n += vn; }
 		double am = 0; int64_t an = 0, ab = 0; if (gsa_get_alloc_stats(c, &am, &an, &ab) == GSA_OK) { alloc_ms += am; alloc_n += an; alloc_bytes += ab; }
 	}
@@ -431,10 +445,10 @@ int main(int argc, char *argv[])
 		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, \"cigar_s\": %.3f, "
 		        "\"result_copy_s_sum\": %.3f, \"maf_format_s\": %.3f, \"variants_s\": %.3f, \"output_drain_after_align_s\": %.3f, \"maf_write_s\": %.3f, \"maf_bytes\": %llu, "
 		        "\"vcf_s\": %.3f, \"vcf_write_s\": %.3f, \"vcf_bytes\": %llu, \"destroy_s\": %.3f, \"host_threads\": %d, \"contexts\": %d, \"query_bp\": %lld, \"contigs\": %d, \"gbp_per_s_excl_index_build\": %.4f, "
-		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f}\n",
+		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"cs_s\": %.3f}\n",
 		        total, t_build, t_index, t_create, t_query, t_pin, t_align, cigar_ms / 1e3, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
-		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac);
+		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, cs_ms / 1e3);
 	}
 	if (timing && var_on_gpu) fprintf(stderr, "GSA_VARIANT_PASS {\"device_ms_sum\": %.3f, \"passes\": %lld, \"query_bp\": %lld}\n", var_dev_ms, var_dev_n, [&] { long long b = 0; for (const QueryContig &q : qs) b += (long long)q.seq.size(); return b; }());
 	// (everything is on disk and the GPU is released: the process ends here -- unwinding 20 GB of host buffers and the HIP runtime's own

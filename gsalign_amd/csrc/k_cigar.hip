@@ -14,6 +14,8 @@
 //           slot k of the block -- at n_cig - 1 - k for a reverse-strand block: SelfComplementarySeq reverses the two lines, classes do
 //           not change under complement, and merging is symmetric
 // No workgroup waits for another, nothing spins.
+// POS (block_cigars(.., pos = true), the front half of gsa_block_cs, k_cs.hip): the EMIT walk also stores, beside run[slot], the reference and query position of the
+// run's first column in walk order, and counts the runs other than '=' that go on into the next record at a position that does not continue them.
 //
 // As in k_variants.hip the columns of a gap are DERIVED from the forward M/D/I op string of its DP job (d_ops, or e_ops for the jobs launched
 // early) and the two sequences, never read from the string pools: the strings of the large DP jobs never exist in d_tail.  'D' puts '-' into
@@ -27,7 +29,6 @@
 #define ENS(T, buf, n) do { if (!dev_ensure<T>(c, c->buf, (size_t)(n))) return GSA_ERR_NOMEM; } while (0)
 #define CIG_SERIAL 64      // gap records of at most this many columns are walked by one lane, longer ones by a wavefront in 64-column steps
 
-struct CigBlk { i64 frag_off; i32 n_frag, bdir, wbase, _pad; };      // one block of the result, ALL of them, in result order: first record (absolute), records, strand, first work item; entry [nb]: wbase = W
 struct CigIn {
 	i32 nb; i64 W; const CigBlk *blk;
 	const gsa_frag *frag; const i32 *ftype, *fjob;
@@ -35,6 +36,7 @@ struct CigIn {
 	const i32 *e_nops; const i64 *e_opsoff; const uint8_t *e_ops;      // DP jobs launched early from the leaf table (fjob <= -2)
 	const uint8_t *query, *ref;
 	i64 n_out;
+	i64 *run_r; i32 *run_q;                                           // POS only: position of every run's first column (walk order)
 };
 
 enum { CG_NONE = 0, CG_RUN = 1, CG_WALK = 2, CG_BAD = 3 };      // no column; L columns of one class; walked column by column; a DP record without a DP job (reported, never skipped)
@@ -85,19 +87,34 @@ __device__ i32 cig_prev(const CigIn &a, const CigBlk &b, i64 i)
 	return 0;
 }
 
-__device__ __forceinline__ void cig_put(const CigIn &a, i64 *run, i64 slot, i64 col, i32 cls)
+template <bool POS>
+__device__ __forceinline__ void cig_put(const CigIn &a, i64 *run, i64 slot, i64 col, i32 cls, i64 rp, i32 qp)
 {
-	if (slot >= 0 && slot < a.n_out) run[slot] = (col << 4) | (i64)cls;
+	if (slot >= 0 && slot < a.n_out) { run[slot] = (col << 4) | (i64)cls; if (POS) { a.run_r[slot] = rp; a.run_q[slot] = qp; } }
+}
+
+// POS: record i goes on with the run (class cls, not '=') the record in front of it ended with: 1 when the bases that run prints do not go on at (rpos, qpos)
+__device__ i32 cig_gap_in_run(const CigIn &a, const CigBlk &b, i64 i, i32 cls, i64 rpos, i32 qpos)
+{
+	for (i64 j = i - 1; j >= b.frag_off; j--) {
+		const CigRec g = cig_load(a, j);
+		if (g.kind == CG_NONE) continue;
+		if (g.kind == CG_BAD) return 0;
+		const bool r_ok = cls == (i32)GSA_CIGAR_INS || g.rpos + (g.rlen > 0 ? g.rlen : 0) == rpos;      // (an insertion prints no reference base)
+		const bool q_ok = cls == (i32)GSA_CIGAR_DEL || g.qpos + (g.qlen > 0 ? g.qlen : 0) == qpos;
+		return (r_ok && q_ok) ? 0 : 1;
+	}
+	return 0;
 }
 
 // a run record or a short walk, by one lane; returns the number of run starts; columns per class into cnt[]
-template <bool EMIT>
+template <bool EMIT, bool POS>
 __device__ i32 cig_lane(const CigIn &a, const CigRec &g, i32 prev, i64 *run, i64 slot, i64 col, i32 cnt[4])
 {
 	if (g.kind == CG_RUN) {
 		cnt[cig_slot(g.cls)] += g.L;
 		if (g.cls == prev) return 0;
-		if (EMIT) cig_put(a, run, slot, col, g.cls);
+		if (EMIT) cig_put<POS>(a, run, slot, col, g.cls, g.rpos, g.qpos);
 		return 1;
 	}
 	i64 rp = g.rpos; i32 qp = g.qpos, n = 0;
@@ -105,7 +122,7 @@ __device__ i32 cig_lane(const CigIn &a, const CigRec &g, i32 prev, i64 *run, i64
 		const int ch = g.op ? (int)g.op[i] : (int)'M';
 		const i32 cls = cig_class(a, ch, rp, qp);
 		cnt[cig_slot(cls)]++;
-		if (cls != prev) { if (EMIT) cig_put(a, run, slot + n, col + i, cls); n++; prev = cls; }
+		if (cls != prev) { if (EMIT) cig_put<POS>(a, run, slot + n, col + i, cls, rp, qp); n++; prev = cls; }
 		if (ch != 'D') rp++;
 		if (ch != 'I') qp++;
 	}
@@ -114,7 +131,7 @@ __device__ i32 cig_lane(const CigIn &a, const CigRec &g, i32 prev, i64 *run, i64
 
 // a long walk by a whole wavefront, 64 columns per step: a lane's reference / query position is the step's base plus the number of lower lanes whose
 // column consumes a base of that side, its slot the base plus the number of lower lanes that start a run
-template <bool EMIT>
+template <bool EMIT, bool POS>
 __device__ i32 cig_wave(const CigIn &a, const CigRec &g, i32 prev, i64 *run, i64 slot, i64 col, i32 cnt[4])
 {
 	const int lane = threadIdx.x & 63;
@@ -132,7 +149,7 @@ __device__ i32 cig_wave(const CigIn &a, const CigRec &g, i32 prev, i64 *run, i64
 		const bool st = valid && cls != pcls;
 		const unsigned long long ms = __ballot(st);
 		if (valid) cnt[cig_slot(cls)]++;
-		if (EMIT && st) cig_put(a, run, slot + n + __popcll(ms & below), col + p, cls);
+		if (EMIT && st) cig_put<POS>(a, run, slot + n + __popcll(ms & below), col + p, cls, rp, qp);
 		rp0 += __popcll(m1); qp0 += __popcll(m2); n += __popcll(ms); carry = __shfl(cls, 63);
 	}
 	return n;
@@ -162,7 +179,7 @@ __device__ __forceinline__ i32 cig_block_of(const CigIn &a, i64 w)
 
 // One work item per record of the listed blocks, a workgroup per 256 of them.  EMIT = false: run starts / columns per record -> ns[] / nc[], per workgroup -> wg[] / wg[nwg + ..],
 // columns per class -> out[block]; EMIT = true: ps[] / pc[] hold every record's first slot and first column (global), the starts are stored into run[].
-template <bool EMIT>
+template <bool EMIT, bool POS>
 __global__ void __launch_bounds__(256) k_cig_pass(CigIn a, i32 *ns, i32 *nc, i64 *wg, i64 nwg, unsigned long long *bad, gsa_block_cigar *out, const i64 *ps, const i64 *pc, i64 *run)
 {
 	__shared__ i32 s_list[256], s_val[256], s_prev[256];
@@ -180,6 +197,10 @@ __global__ void __launch_bounds__(256) k_cig_pass(CigIn a, i32 *ns, i32 *nc, i64
 		g = cig_load(a, i);
 		if (g.kind == CG_RUN || g.kind == CG_WALK) prev = cig_prev(a, a.blk[b], i);
 		if (EMIT) { slot = ps[w]; col = pc[w] - pc[a.blk[b].wbase]; }
+		if (POS && prev != 0 && prev != (i32)GSA_CIGAR_EQ && (g.kind == CG_RUN || g.kind == CG_WALK)) {
+			const i32 first = g.kind == CG_RUN ? g.cls : cig_class(a, g.op ? (int)g.op[0] : (int)'M', g.rpos, g.qpos);
+			if (first == prev && cig_gap_in_run(a, a.blk[b], i, first, g.rpos, g.qpos)) atomicAdd(bad + 2, 1ull);
+		}
 	}
 	__syncthreads();
 	const bool wide = g.kind == CG_WALK && g.L > CIG_SERIAL;
@@ -187,7 +208,7 @@ __global__ void __launch_bounds__(256) k_cig_pass(CigIn a, i32 *ns, i32 *nc, i64
 	i32 n = 0;
 	if (wide) { const int at = atomicAdd(&s_n, 1); s_list[at] = tid; s_prev[tid] = prev; s_slot[tid] = slot; s_col[tid] = col; }
 	else if (g.kind == CG_BAD) { if (!EMIT) atomicAdd(bad, 1ull); }
-	else if (g.kind != CG_NONE) n = cig_lane<EMIT>(a, g, prev, run, slot, col, cnt);
+	else if (g.kind != CG_NONE) n = cig_lane<EMIT, POS>(a, g, prev, run, slot, col, cnt);
 	if (!EMIT) cig_totals(out, active, b, cnt);
 	__syncthreads();
 	const int nlist = s_n;
@@ -198,7 +219,7 @@ __global__ void __launch_bounds__(256) k_cig_pass(CigIn a, i32 *ns, i32 *nc, i64
 		const i32 bt = cig_block_of(a, wt);
 		const CigRec gt = cig_load(a, a.blk[bt].frag_off + (wt - a.blk[bt].wbase));
 		i32 cw[4] = { 0, 0, 0, 0 };
-		const i32 nt = cig_wave<EMIT>(a, gt, s_prev[t], run, s_slot[t], s_col[t], cw);
+		const i32 nt = cig_wave<EMIT, POS>(a, gt, s_prev[t], run, s_slot[t], s_col[t], cw);
 		if (!EMIT) { cig_totals(out, true, bt, cw); if (lane == 0) s_val[t] = nt; }
 	}
 	if (EMIT) return;      // (safe: nothing below this line is reached on the EMIT path, so no __syncthreads is left waiting for these threads)
@@ -281,7 +302,7 @@ __global__ void __launch_bounds__(256) k_cig_pack(i32 nb, const CigBlk *blk, con
 	ops[off + (blk[lo].bdir ? k : (i64)n - 1 - k)] = (u32)((u64)len << 4) | (u32)(me & 15);
 }
 
-int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out)
+int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out, bool pos)
 {
 	out->n_blocks = 0; out->n_ops = 0; out->blk = nullptr; out->ops = nullptr;
 	// the blocks of contig k in the final list, and where its records start
@@ -292,7 +313,7 @@ int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out)
 	}
 	if (nb == 0 || c->n_frags <= 0) return GSA_OK;
 	hipStream_t st = c->stream;
-	if (!pin_ensure<CigBlk>(c, c->p_cblk, nb + 1) || !pin_ensure<i64>(c, c->p_chdr, 4) || !pin_ensure<gsa_block_cigar>(c, c->p_cout, nb)) return GSA_ERR_NOMEM;
+	if (!pin_ensure<CigBlk>(c, c->p_cblk, nb + 1) || !pin_ensure<i64>(c, c->p_chdr, 8) || !pin_ensure<gsa_block_cigar>(c, c->p_cout, nb)) return GSA_ERR_NOMEM;
 	CigBlk *hb = c->p_cblk.as<CigBlk>(); i64 W = 0;
 	for (size_t j = 0; j < nb; j++) {
 		const gsa_block &bl = c->h_blocks[b0 + j];
@@ -305,22 +326,22 @@ int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out)
 	gsa_block_cigar *hout = c->p_cout.as<gsa_block_cigar>();
 	if (W == 0) { memset(hout, 0, nb * sizeof(gsa_block_cigar)); out->n_blocks = (int32_t)nb; out->blk = hout; return GSA_OK; }
 	const i64 nwg = (W + 255) / 256;
-	ENS(CigBlk, d_cblk, nb + 1); ENS(gsa_block_cigar, d_cout, nb); ENS(i32, d_ccnt, 2 * ((size_t)W + 1)); ENS(i64, d_cwg, 2 * (size_t)nwg + 2); ENS(i64, d_cpre, 2 * ((size_t)W + 1));
+	ENS(CigBlk, d_cblk, nb + 1); ENS(gsa_block_cigar, d_cout, nb); ENS(i32, d_ccnt, 2 * ((size_t)W + 1)); ENS(i64, d_cwg, 2 * (size_t)nwg + 3); ENS(i64, d_cpre, 2 * ((size_t)W + 1));
 	i32 *ns = c->d_ccnt.as<i32>(), *nc = ns + (W + 1);
-	i64 *wg = c->d_cwg.as<i64>(); unsigned long long *bad = (unsigned long long *)(wg + 2 * nwg);      // {records without a job, runs too long for an op}
+	i64 *wg = c->d_cwg.as<i64>(); unsigned long long *bad = (unsigned long long *)(wg + 2 * nwg);      // {records without a job, runs too long for an op, pos: runs that go on in the next record somewhere else}
 	i64 *ps = c->d_cpre.as<i64>(), *pc = ps + (W + 1);
 	i64 *hdr = c->p_chdr.as<i64>();
 	const CigBlk *dblk = c->d_cblk.as<CigBlk>(); gsa_block_cigar *dout = c->d_cout.as<gsa_block_cigar>();
 	GSA_CHECK(c, hipMemcpyAsync(c->d_cblk.p, hb, (nb + 1) * sizeof(CigBlk), hipMemcpyHostToDevice, st));
 	GSA_CHECK(c, hipMemsetAsync(dout, 0, nb * sizeof(gsa_block_cigar), st));
-	GSA_CHECK(c, hipMemsetAsync(bad, 0, 2 * sizeof(unsigned long long), st));
+	GSA_CHECK(c, hipMemsetAsync(bad, 0, 3 * sizeof(unsigned long long), st));
 	CigIn a;
 	a.nb = (i32)nb; a.W = W; a.blk = dblk;
 	a.frag = c->f_rec.as<gsa_frag>(); a.ftype = c->f_type.as<i32>(); a.fjob = c->f_job.as<i32>();
 	a.j_nops = c->j_nops.as<i32>(); a.j_opsoff = c->j_opsoff.as<i64>(); a.j_ops = c->d_ops.as<uint8_t>();
 	a.e_nops = c->e_nops.as<i32>(); a.e_opsoff = c->e_opsoff.as<i64>(); a.e_ops = c->e_ops.as<uint8_t>();
-	a.query = c->q_dev; a.ref = c->di.ref; a.n_out = 0;
-	hipLaunchKernelGGL(k_cig_pass<false>, dim3((unsigned)nwg), dim3(256), 0, st, a, ns, nc, wg, nwg, bad, dout, (const i64 *)nullptr, (const i64 *)nullptr, (i64 *)nullptr);
+	a.query = c->q_dev; a.ref = c->di.ref; a.n_out = 0; a.run_r = nullptr; a.run_q = nullptr;
+	hipLaunchKernelGGL((k_cig_pass<false, false>), dim3((unsigned)nwg), dim3(256), 0, st, a, ns, nc, wg, nwg, bad, dout, (const i64 *)nullptr, (const i64 *)nullptr, (i64 *)nullptr);
 	GSA_CHECK(c, hipGetLastError());
 	hipLaunchKernelGGL(k_cig_scan, dim3(1), dim3(256), 0, st, nwg, wg, (const unsigned long long *)bad, W, ps, pc, hdr);
 	GSA_CHECK(c, hipGetLastError());
@@ -337,13 +358,19 @@ int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out)
 		// the output is sized from the scan's total; it goes home in one copy
 		ENS(i64, d_crun, (size_t)n); ENS(u32, d_cops, (size_t)n); if (!pin_ensure<u32>(c, c->p_cops, (size_t)n)) return GSA_ERR_NOMEM;
 		a.n_out = n;
-		hipLaunchKernelGGL(k_cig_pass<true>, dim3((unsigned)nwg), dim3(256), 0, st, a, ns, nc, wg, nwg, bad, dout, (const i64 *)ps, (const i64 *)pc, c->d_crun.as<i64>());
+		if (pos) {
+			ENS(i64, d_crpos, (size_t)n); ENS(i32, d_cqpos, (size_t)n);
+			a.run_r = c->d_crpos.as<i64>(); a.run_q = c->d_cqpos.as<i32>();
+			hipLaunchKernelGGL((k_cig_pass<true, true>), dim3((unsigned)nwg), dim3(256), 0, st, a, ns, nc, wg, nwg, bad, dout, (const i64 *)ps, (const i64 *)pc, c->d_crun.as<i64>());
+		} else
+			hipLaunchKernelGGL((k_cig_pass<true, false>), dim3((unsigned)nwg), dim3(256), 0, st, a, ns, nc, wg, nwg, bad, dout, (const i64 *)ps, (const i64 *)pc, c->d_crun.as<i64>());
 		GSA_CHECK(c, hipGetLastError());
 		hipLaunchKernelGGL(k_cig_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (i32)nb, dblk, (const gsa_block_cigar *)dout, (const i64 *)pc, (const i64 *)c->d_crun.as<i64>(), n, c->d_cops.as<u32>(), bad + 1);
 		GSA_CHECK(c, hipGetLastError());
 		GSA_CHECK(c, hipMemcpyAsync(c->p_cops.p, c->d_cops.p, (size_t)n * sizeof(u32), hipMemcpyDeviceToHost, st));
-		GSA_CHECK(c, hipMemcpyAsync(hdr + 3, bad + 1, sizeof(i64), hipMemcpyDeviceToHost, st));
+		GSA_CHECK(c, hipMemcpyAsync(hdr + 3, bad + 1, (pos ? 2 : 1) * sizeof(i64), hipMemcpyDeviceToHost, st));
 		GSA_CHECK(c, hipStreamSynchronize(st));
+		if (pos && hdr[4]) return gsa_fail(c, GSA_ERR_STATE, "internal: gsa_block_cs met " + std::to_string((long long)hdr[4]) + " run(s) that go on in the next record at another position");
 		if (hdr[3]) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_block_cigars: " + std::to_string((long long)hdr[3]) + " run(s) of 2^28 columns or more do not fit an op");
 	}
 	out->n_blocks = (int32_t)nb; out->n_ops = n; out->blk = hout; out->ops = n ? c->p_cops.as<u32>() : nullptr;

@@ -115,11 +115,14 @@ def result_from_dump(d: dict, keep: list):
     return r
 
 
-def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, reference_label: str, per_contig, allow_dup: bool = True, fmt: int = 1, summary: bool = False) -> None:
+def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, reference_label: str, per_contig, allow_dup: bool = True, fmt: int = 1, summary: bool = False, cs: bool = False) -> None:
     """per_contig(ci, seq_uint8) -> dump dict of the finished contig (stage 8 layout).  fmt 1 = MAF, 2 = ALN, 3 = PAF with the host comparator's CIGARs (written to maf_path).
     summary=True (fmt 3 only; gsah_c_emit_summary): the PAF is formatted from a summary result -- blocks and block ends, taken out of the full dump, with the
-    comparator's CIGARs -- and no VCF is written (vcf_path is not opened)."""
+    comparator's CIGARs -- and no VCF is written (vcf_path is not opened).
+    cs=True (fmt 3 only; gsah_c_emit_paf_cs): every line also gets the cs:Z: field, from the host comparator gsah_block_cs."""
     keep: list = []
+    if cs and (fmt != 3 or summary):
+        raise ValueError("cs=True goes with fmt=3 (and not with summary=True)")
     if summary and fmt != 3:
         raise ValueError("summary=True formats PAF only (fmt=3)")
 
@@ -134,6 +137,11 @@ def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, referen
         rc = load().gsah_c_emit_summary(index_prefix.encode(), query_fa.encode(), maf_path.encode(), 1 if allow_dup else 0, RESULT_CB(cb), None, err)
         if rc != 0:
             raise RuntimeError(f"gsah_c_emit_summary -> {rc}: {err.value.decode()}")
+        return
+    if cs:
+        rc = load().gsah_c_emit_paf_cs(index_prefix.encode(), query_fa.encode(), maf_path.encode(), vcf_path.encode(), reference_label.encode(), 1 if allow_dup else 0, RESULT_CB(cb), None, err)
+        if rc != 0:
+            raise RuntimeError(f"gsah_c_emit_paf_cs -> {rc}: {err.value.decode()}")
         return
     rc = load().gsah_c_emit_fmt(index_prefix.encode(), query_fa.encode(), maf_path.encode(), vcf_path.encode(), reference_label.encode(),
                                 1 if allow_dup else 0, fmt, RESULT_CB(cb), None, err)
@@ -231,3 +239,39 @@ def cigar_trim(ops, bdir: bool, ext: int, counts):
         raise RuntimeError(f"gsah_c_cigar_trim -> {n}")
     assert n == int(bc["n_cig"][0])
     return out[:n].copy(), (int(bc["n_eq"][0]), int(bc["n_x"][0]), int(bc["n_ins"][0]), int(bc["n_del"][0]))
+
+
+def cs(index_prefix, seq, result):
+    """gsah_c_cs: the cs string (PAF's cs:Z:, short form) of every block of one finished contig on the host, from the gapped strings and seed records, untrimmed -- what
+    Aligner.block_cs computes on the GPU.  result: a capi.Result, a dump dict (oracle layout) or a result dict of capi.Aligner.  index_prefix and seq are not needed by the
+    walk and may be None (kept for symmetry with cigars()).  Returns (BLOCK_CS_DT array, uint8 bytes); block b's string is bytes[cs_off : cs_off + n_cs]."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    lib = load()
+    lib.gsah_c_cs.restype = C.c_longlong
+    lib.gsah_c_cs.argtypes = [C.POINTER(capi.Result), C.c_void_p, C.c_void_p, C.c_longlong]
+    blk = np.zeros(int(result.n_blocks), capi.BLOCK_CS_DT)
+    n = lib.gsah_c_cs(C.byref(result), C.c_void_p(blk.ctypes.data), None, 0)
+    if n < 0:
+        raise RuntimeError(f"gsah_c_cs -> {n}")
+    by = np.zeros(int(n), np.uint8)
+    if n:
+        n2 = lib.gsah_c_cs(C.byref(result), C.c_void_p(blk.ctypes.data), C.c_void_p(by.ctypes.data), n)
+        assert n2 == n
+    return blk, by
+
+
+def cs_trim(cs_bytes, ops, bdir: bool, ext: int) -> bytes:
+    """gsah_c_cs_trim: iExtension's trim on ONE block's cs string (of its untrimmed ops, output order) -- the last `ext` columns in walk order go, a cut ':n' is
+    printed again.  Returns the string that stays: the cs of the trimmed ops."""
+    b = np.frombuffer(cs_bytes.encode() if isinstance(cs_bytes, str) else bytes(cs_bytes), np.uint8)
+    ops = np.ascontiguousarray(ops, dtype=np.uint32)
+    out = np.zeros(max(b.size, 1), np.uint8)
+    lib = load()
+    lib.gsah_c_cs_trim.restype = C.c_longlong
+    lib.gsah_c_cs_trim.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p]
+    n = lib.gsah_c_cs_trim(C.c_void_p(b.ctypes.data), int(b.size), C.c_void_p(ops.ctypes.data), int(ops.size), 1 if bdir else 0, int(ext), C.c_void_p(out.ctypes.data))
+    if n < 0:
+        raise RuntimeError(f"gsah_c_cs_trim -> {n}")
+    return out[:n].tobytes()

@@ -375,12 +375,44 @@ int gsa_block_cigars(gsa_ctx *ctx, int32_t k, gsa_cigars *out);
 /* measurement: host wall time the calling threads spent inside gsa_block_cigars on this context since it was created (launches, the two waits,
  * the copies home), and the number of calls.  Always on (two clock reads per call). */
 int gsa_get_cigar_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+/* ---- per-block cs strings (PAF's cs:Z:, short form) ---------------------------
+ * The cs of a block is a function of the block's CIGAR ops, in the order gsa_block_cigars delivers them (output order, i.e. reference-forward:
+ * a reverse-strand block's ops are stored reversed), and of the bases under them.  Each op gives one token group:
+ *   = run of n columns   ':' and decimal n
+ *   X run of n columns   n groups "*rq": r the reference letter, q the query letter of that column
+ *   I run of n columns   '+' and the n query letters
+ *   D run of n columns   '-' and the n reference letters
+ * The letter of a byte b is "acgtn"[nt4(b)] in a forward-strand block (bdir != 0) and "tgcan"[nt4(b)] in a reverse-strand block, whose columns are
+ * taken back to front; nt4 maps A/C/G/T in either case to 0..3 and everything else to 4.  For a reverse-strand block the byte comes from the
+ * reverse-complement half of the 2G text and from the query as stored, so the letters printed are the forward-strand reference base and the
+ * complemented query base: what the two `s` lines of OutputMAF show after SelfComplementarySeq, lower-cased, with every byte outside acgt
+ * printed as 'n' (the reference's ReverseMap turns IUPAC codes into NUL there; 'n' is the defined answer here).  The classes are the CIGAR's:
+ * N against N is an X column and prints "*nn", a difference in case only is '='.  Only the short form exists (the long form, "=ACGT...", is as
+ * large as the genome).  Like the CIGAR the answer is UNTRIMMED: the iExtension trim is the emitter's business.
+ * blk[b] = where block b's string lies in `cs` and its length; the strings are not NUL-terminated. */
+typedef struct { int64_t cs_off; int32_t n_cs; int32_t _pad; } gsa_cs_block;                           /* 16 bytes; one per block of gsa_result::blocks, same order */
+typedef struct { int32_t n_blocks; int64_t n_bytes; const gsa_cs_block *blk; const char *cs; } gsa_cs; /* 32 bytes */
+/* The cs strings of ALL blocks of the stage-8 result the context holds, duplicates included.  Validity, call order, k and the error codes are
+ * those of gsa_block_cigars (GSA_ERR_STATE before stage 8 and after a prefetch has overwritten the contig, GSA_ERR_ARG for k out of range; no
+ * blocks: n_blocks = 0, n_bytes = 0).  The call runs the CIGAR pass itself; a later gsa_block_cigars or gsa_call_variants on the same result
+ * returns what it returned before -- the three answers live in buffers of their own.  A block whose string reaches 2^31 bytes: GSA_ERR_LIMIT.
+ * Memory is owned by the context and valid until the next call on it; the bytes come home in one copy into pinned memory. */
+int gsa_block_cs(gsa_ctx *ctx, int32_t k, gsa_cs *out);
+/* measurement: host wall time the calling threads spent inside gsa_block_cs on this context since it was created (its CIGAR pass included), and
+ * the number of calls.  Always on. */
+int gsa_get_cs_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+
 /* gsa_align_many with optional passes run by the worker in front of the callback -- before the prefetch after next can touch the contig's
- * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars).  *ex and what it points to are valid during
+ * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs).  *ex and what it points to are valid during
  * the callback only, like *res. */
 #define GSA_WANT_VARIANTS 1u
 #define GSA_WANT_CIGARS   2u
+#define GSA_WANT_CS       4u   /* gsa_block_cs; implies GSA_WANT_CIGARS */
 typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;   /* NULL where not asked for */
+/* The contig's cs strings inside the callback of gsa_align_many_ex: the library hands the callback a LARGER object whose head is the gsa_extras
+ * (which keeps its two members and its 16 bytes), and this call reaches what lies behind it -- so it is valid for the `ex` the library passed
+ * only, never for a gsa_extras the caller made.  GSA_ERR_STATE when GSA_WANT_CS was not asked for.  *out is valid during the callback only. */
+int gsa_extras_cs(const gsa_extras *ex, gsa_cs *out);
 typedef int (*gsa_result_ex_fn)(void *user, int32_t contig, const gsa_result *res, const gsa_extras *ex);
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
                       uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user);
