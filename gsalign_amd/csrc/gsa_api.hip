@@ -1092,48 +1092,50 @@ static int align_split(gsa_ctx *const *grp, int n_grp, const char *query, int32_
 	return gsa_finish_contig(grp[0], out);
 }
 
+// What the three passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip) ask of the context before they run; `who`: the export, for the messages
+static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who)
+{
+	const std::string w(who);
+	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, w + ": the context holds no finished (stage 8) result");
+	// (the pass reads the contig's bases on the device: a prefetch into the slot that held them leaves another contig there)
+	if (c->q_cur == -2) return gsa_fail(c, GSA_ERR_STATE, w + ": the contig's device copy was overwritten by a prefetch");
+	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, w + ": contig index out of range");
+	GSA_CHECK(c, hipSetDevice(c->device));
+	return GSA_OK;
+}
+
+static int pass_timing(const gsa_ctx *c, double gsa_ctx::*sum, long long gsa_ctx::*calls, double *ms_sum, int64_t *n_calls)
+{
+	if (!c || !ms_sum || !n_calls) return GSA_ERR_ARG;
+	*ms_sum = c->*sum; *n_calls = (int64_t)(c->*calls);
+	return GSA_OK;
+}
+
 // VariantIdentification (SeqVariant.cpp:12-119) over the stage-8 result the context holds: k_variants.hip
 int gsa_call_variants(gsa_ctx *c, int32_t k, gsa_variants *out)
 {
 	if (!c || !out) return GSA_ERR_ARG;
 	out->n = 0; out->v = nullptr; out->n_snv = out->n_ins = out->n_del = 0;
-	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, "gsa_call_variants: the context holds no finished (stage 8) result");
-	// (the pass reads the contig's bases on the device: a prefetch into the slot that held them leaves another contig there)
-	if (c->q_cur == -2) return gsa_fail(c, GSA_ERR_STATE, "gsa_call_variants: the contig's device copy was overwritten by a prefetch");
-	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, "gsa_call_variants: contig index out of range");
-	GSA_CHECK(c, hipSetDevice(c->device));
-	return call_variants(c, k, out);
+	const int rc = result_pass_ready(c, k, "gsa_call_variants");
+	return rc ? rc : call_variants(c, k, out);
 }
 
-int gsa_get_variant_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls)
-{
-	if (!c || !ms_sum || !n_calls) return GSA_ERR_ARG;
-	*ms_sum = c->var_ms_sum; *n_calls = (int64_t)c->var_calls;
-	return GSA_OK;
-}
+int gsa_get_variant_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::var_ms_sum, &gsa_ctx::var_calls, ms_sum, n_calls); }
 
 // the CIGAR of every block of the stage-8 result the context holds: k_cigar.hip
 int gsa_block_cigars(gsa_ctx *c, int32_t k, gsa_cigars *out)
 {
 	if (!c || !out) return GSA_ERR_ARG;
 	out->n_blocks = 0; out->n_ops = 0; out->blk = nullptr; out->ops = nullptr;
-	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, "gsa_block_cigars: the context holds no finished (stage 8) result");
-	// (the pass reads the contig's bases on the device: a prefetch into the slot that held them leaves another contig there)
-	if (c->q_cur == -2) return gsa_fail(c, GSA_ERR_STATE, "gsa_block_cigars: the contig's device copy was overwritten by a prefetch");
-	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, "gsa_block_cigars: contig index out of range");
-	GSA_CHECK(c, hipSetDevice(c->device));
+	int rc = result_pass_ready(c, k, "gsa_block_cigars");
+	if (rc) return rc;
 	const auto t0 = std::chrono::steady_clock::now();
-	const int rc = block_cigars(c, k, out);
+	rc = block_cigars(c, k, out);
 	c->cig_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->cig_calls++;
 	return rc;
 }
 
-int gsa_get_cigar_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls)
-{
-	if (!c || !ms_sum || !n_calls) return GSA_ERR_ARG;
-	*ms_sum = c->cig_ms_sum; *n_calls = (int64_t)c->cig_calls;
-	return GSA_OK;
-}
+int gsa_get_cigar_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::cig_ms_sum, &gsa_ctx::cig_calls, ms_sum, n_calls); }
 
 // the cs string of every block of the stage-8 result the context holds: k_cs.hip
 // (cig: the CIGARs the pass computed on its way, for gsa_align_many_ex -- they lie in the CIGAR pass's own buffers)
@@ -1141,25 +1143,17 @@ static int cs_call(gsa_ctx *c, int32_t k, gsa_cs *out, gsa_cigars *cig)
 {
 	if (!c || !out) return GSA_ERR_ARG;
 	out->n_blocks = 0; out->n_bytes = 0; out->blk = nullptr; out->cs = nullptr;
-	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, "gsa_block_cs: the context holds no finished (stage 8) result");
-	// (the pass reads the contig's bases on the device: a prefetch into the slot that held them leaves another contig there)
-	if (c->q_cur == -2) return gsa_fail(c, GSA_ERR_STATE, "gsa_block_cs: the contig's device copy was overwritten by a prefetch");
-	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, "gsa_block_cs: contig index out of range");
-	GSA_CHECK(c, hipSetDevice(c->device));
+	int rc = result_pass_ready(c, k, "gsa_block_cs");
+	if (rc) return rc;
 	const auto t0 = std::chrono::steady_clock::now();
-	const int rc = block_cs(c, k, out, cig);
+	rc = block_cs(c, k, out, cig);
 	c->cs_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->cs_calls++;
 	return rc;
 }
 
 int gsa_block_cs(gsa_ctx *c, int32_t k, gsa_cs *out) { return cs_call(c, k, out, nullptr); }
 
-int gsa_get_cs_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls)
-{
-	if (!c || !ms_sum || !n_calls) return GSA_ERR_ARG;
-	*ms_sum = c->cs_ms_sum; *n_calls = (int64_t)c->cs_calls;
-	return GSA_OK;
-}
+int gsa_get_cs_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::cs_ms_sum, &gsa_ctx::cs_calls, ms_sum, n_calls); }
 
 // what the callback of gsa_align_many_ex is handed: the public gsa_extras at the head, the answers of later passes behind it
 struct ExtrasFull { gsa_extras ex; const gsa_cs *cs; };

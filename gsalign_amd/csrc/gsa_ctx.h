@@ -272,6 +272,8 @@ template <class T> static inline T *dev_ensure(gsa_ctx *c, DevBuf &b, size_t n, 
 	c->alloc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count(); c->alloc_n++; c->alloc_bytes += (long long)want;
 	return (T *)b.p;
 }
+// inside a stage driver (`c` is the context, the function returns an error code): c->buf holds n elements of T, or the driver fails
+#define ENS(T, buf, n) do { if (!dev_ensure<T>(c, c->buf, (size_t)(n))) return GSA_ERR_NOMEM; } while (0)
 
 template <class T> static inline T *pin_ensure(gsa_ctx *c, DevBuf &b, size_t n)
 {
@@ -313,8 +315,8 @@ i64 frags_count(gsa_ctx *c);          // k_extend.hip  (record count, fetched fr
 int stage78_extend(gsa_ctx *c);       // k_extend.hip  (S7: classification, DP, gapped strings, block sums)
 int run_gapsim_jobs(gsa_ctx *c, i32 n, const i32 *d_n, const i32 *d_q1, const i32 *d_q2, const i64 *d_r1, const i64 *d_r2, i32 *d_res, const i32 *d_jseed, i32 *d_cut4);   // k_gapsim.hip
 void dp_count_cells(gsa_ctx *c, i32 n_ub, const i32 *len1, const i32 *len2, hipStream_t stream);   // k_dp.hip (profiling)
+// the passes over a stage-8 result (shared parts: gsa_walk.h).  `out` comes in zeroed (gsa_api.hip's exports do that, once) and is written only on success
 int call_variants(gsa_ctx *c, i32 k, gsa_variants *out);   // k_variants.hip  (VariantIdentification over the stage-8 result of contig k)
-struct CigBlk { i64 frag_off; i32 n_frag, bdir, wbase, _pad; };      // one block of the result, ALL of them, in result order: first record (absolute), records, strand, first work item; entry [nb]: wbase = W  (k_cigar.hip's block table d_cblk, read by k_cs.hip too)
 int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out, bool pos = false);      // k_cigar.hip  (the CIGAR of every block of the stage-8 result of contig k; pos: the runs' first positions too, into d_crpos / d_cqpos)
 int block_cs(gsa_ctx *c, i32 k, gsa_cs *out, gsa_cigars *cig_out = nullptr);   // k_cs.hip  (the cs string of every block: the CIGAR pass with positions, then its own three passes; cig_out: that CIGAR pass's answer)
 int ctx_create_bare(int device, gsa_ctx **out);            // gsa_api.hip  (a context with NO index: device, stream, mailbox and scratch -- what the sort and the fused passes need; gsa_destroy frees it)

@@ -887,7 +887,6 @@ int launch_early_dp(gsa_ctx *c)
 }
 
 #define LAUNCH(k, n, ...) hipLaunchKernelGGL(k, dim3(grid_for((size_t)(n), TPB)), dim3(TPB), 0, st, __VA_ARGS__)
-#define ENS(T, buf, n) do { if (!dev_ensure<T>(c, c->buf, (size_t)(n))) return GSA_ERR_NOMEM; } while (0)
 #define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 // The same segmentation for contigs whose chain does not fit one workgroup's LDS (round 5: ONE launch; until then leave() per tile, 13-14

@@ -22,29 +22,23 @@
 // the reference row (CIGAR I), 'I' into the query row (CIGAR D) (ksw2_alignment.cpp:264-272); an equal-length gap that needed no DP is all
 // 'M'; a pure insertion / deletion record is one run whatever its length.
 #include <cstring>
-#include "gsa_ctx.h"
 #include "gsa_fm.h"
-#include "gsa_gap.h"
+#include "gsa_walk.h"
 
-#define ENS(T, buf, n) do { if (!dev_ensure<T>(c, c->buf, (size_t)(n))) return GSA_ERR_NOMEM; } while (0)
 #define CIG_SERIAL 64      // gap records of at most this many columns are walked by one lane, longer ones by a wavefront in 64-column steps
 
-struct CigIn {
+struct CigIn : GapIn {
 	i32 nb; i64 W; const CigBlk *blk;
-	const gsa_frag *frag; const i32 *ftype, *fjob;
-	const i32 *j_nops; const i64 *j_opsoff; const uint8_t *j_ops;      // DP jobs of the job list
-	const i32 *e_nops; const i64 *e_opsoff; const uint8_t *e_ops;      // DP jobs launched early from the leaf table (fjob <= -2)
-	const uint8_t *query, *ref;
 	i64 n_out;
 	i64 *run_r; i32 *run_q;                                           // POS only: position of every run's first column (walk order)
 };
 
 enum { CG_NONE = 0, CG_RUN = 1, CG_WALK = 2, CG_BAD = 3 };      // no column; L columns of one class; walked column by column; a DP record without a DP job (reported, never skipped)
-struct CigRec { i32 kind, L, cls; const uint8_t *op; i32 qpos, qlen, rlen; i64 rpos; };
+struct CigRec { i32 kind = CG_NONE, L = 0, cls = 0; const uint8_t *op = nullptr; i32 qpos = 0, qlen = 0, rlen = 0; i64 rpos = 0; };
 
 __device__ __forceinline__ CigRec cig_load(const CigIn &a, i64 i)
 {
-	CigRec g; g.kind = CG_NONE; g.L = 0; g.cls = 0; g.op = nullptr;
+	CigRec g;
 	const i32 t = a.ftype[i];
 	const gsa_frag f = a.frag[i];
 	g.qpos = f.qpos; g.qlen = f.qlen; g.rlen = f.rlen; g.rpos = f.rpos;
@@ -52,14 +46,8 @@ __device__ __forceinline__ CigRec cig_load(const CigIn &a, i64 i)
 	if (f.qlen <= 0 && f.rlen <= 0) return g;
 	if (f.qlen <= 0) { g.kind = CG_RUN; g.L = f.rlen; g.cls = (i32)GSA_CIGAR_DEL; return g; }
 	if (f.rlen <= 0) { g.kind = CG_RUN; g.L = f.qlen; g.cls = (i32)GSA_CIGAR_INS; return g; }
-	g.kind = CG_WALK;
-	if (t == FT_DP) {
-		const i32 fj = a.fjob[i];
-		if (fj >= 0) { g.op = a.j_ops + a.j_opsoff[fj]; g.L = a.j_nops[fj]; }
-		else if (fj <= -2) { const i32 e = -2 - fj; g.op = a.e_ops + a.e_opsoff[e]; g.L = a.e_nops[e]; }
-		else g.kind = CG_BAD;
-	} else g.L = f.qlen;                                            // FT_EQ: every column is a pair of bases
-	if (g.kind == CG_WALK && g.L <= 0) g.kind = CG_NONE;
+	if (!gap_ops(a, i, t, f, g.op, g.L)) g.kind = CG_BAD;
+	else if (g.L > 0) g.kind = CG_WALK;
 	return g;
 }
 
@@ -170,13 +158,6 @@ __device__ __forceinline__ void cig_totals(gsa_block_cigar *out, bool active, i3
 	}
 }
 
-__device__ __forceinline__ i32 cig_block_of(const CigIn &a, i64 w)
-{
-	i32 lo = 0, hi = a.nb;                          // last block with wbase <= w (blocks without records share their wbase with the next one: the last of them is the one that has w)
-	while (hi - lo > 1) { const i32 m = (lo + hi) >> 1; if (a.blk[m].wbase <= w) lo = m; else hi = m; }
-	return lo;
-}
-
 // One work item per record of the listed blocks, a workgroup per 256 of them.  EMIT = false: run starts / columns per record -> ns[] / nc[], per workgroup -> wg[] / wg[nwg + ..],
 // columns per class -> out[block]; EMIT = true: ps[] / pc[] hold every record's first slot and first column (global), the starts are stored into run[].
 template <bool EMIT, bool POS>
@@ -188,11 +169,11 @@ __global__ void __launch_bounds__(256) k_cig_pass(CigIn a, i32 *ns, i32 *nc, i64
 	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 	const i64 w = (i64)blockIdx.x * 256 + tid;
 	if (tid == 0) s_n = 0;
-	CigRec g; g.kind = CG_NONE; g.L = 0; g.cls = 0; g.op = nullptr; g.qpos = 0; g.qlen = 0; g.rlen = 0; g.rpos = 0;
+	CigRec g;
 	i32 b = 0, prev = 0; i64 slot = 0, col = 0;
 	const bool active = w < a.W;
 	if (active) {
-		b = cig_block_of(a, w);
+		b = blk_last_le(a.blk, a.nb, &CigBlk::wbase, w);      // (blocks without records share their wbase with the next one: the last of them is the one that has w)
 		const i64 i = a.blk[b].frag_off + (w - a.blk[b].wbase);
 		g = cig_load(a, i);
 		if (g.kind == CG_RUN || g.kind == CG_WALK) prev = cig_prev(a, a.blk[b], i);
@@ -216,7 +197,7 @@ __global__ void __launch_bounds__(256) k_cig_pass(CigIn a, i32 *ns, i32 *nc, i64
 		// (the record's look-up is repeated by every lane of the wavefront: the addresses are uniform, so the loads are one request each)
 		const int t = s_list[q];
 		const i64 wt = (i64)blockIdx.x * 256 + t;
-		const i32 bt = cig_block_of(a, wt);
+		const i32 bt = blk_last_le(a.blk, a.nb, &CigBlk::wbase, wt);
 		const CigRec gt = cig_load(a, a.blk[bt].frag_off + (wt - a.blk[bt].wbase));
 		i32 cw[4] = { 0, 0, 0, 0 };
 		const i32 nt = cig_wave<EMIT, POS>(a, gt, s_prev[t], run, s_slot[t], s_col[t], cw);
@@ -234,46 +215,23 @@ __global__ void __launch_bounds__(256) k_cig_pass(CigIn a, i32 *ns, i32 *nc, i64
 	if (tid == 0) { wg[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3]; wg[nwg + blockIdx.x] = s_w[4] + s_w[5] + s_w[6] + s_w[7]; }
 }
 
-// second level of the scan (the pattern of k_var_scan, two arrays): one workgroup turns the workgroups' sums into their first slots / first columns; the totals
+// second level of the scan, two arrays: one workgroup turns the workgroups' sums into their first slots / first columns; the totals
 // go behind the last record's prefix values and, with the count of records without a job, to the host's header
 __global__ void __launch_bounds__(256) k_cig_scan(i64 nwg, i64 *wg, const unsigned long long *bad, i64 W, i64 *ps, i64 *pc, i64 *hdr)
 {
 	__shared__ i64 s_w[4];
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	i64 total[2] = { 0, 0 };
-	for (int arr = 0; arr < 2; arr++) {
-		i64 *x = wg + (i64)arr * nwg;
-		i64 carry = 0;
-		for (i64 base = 0; base < nwg; base += 256) {
-			const i64 i = base + tid;
-			const i64 v = i < nwg ? x[i] : 0;
-			i64 s = v;
-			for (int d = 1; d < 64; d <<= 1) { const i64 y = __shfl_up(s, d); if (lane >= d) s += y; }
-			if (lane == 63) s_w[wv] = s;
-			__syncthreads();
-			i64 pre = 0; for (int k = 0; k < wv; k++) pre += s_w[k];
-			if (i < nwg) x[i] = carry + pre + s - v;
-			carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-			__syncthreads();
-		}
-		total[arr] = carry;
-	}
-	if (tid == 0) { ps[W] = total[0]; pc[W] = total[1]; hdr[0] = total[0]; hdr[1] = total[1]; hdr[2] = (i64)bad[0]; }
+	const i64 slots = wg_scan_sums(wg, nwg, s_w), cols = wg_scan_sums(wg + nwg, nwg, s_w);
+	if (threadIdx.x == 0) { ps[W] = slots; pc[W] = cols; hdr[0] = slots; hdr[1] = cols; hdr[2] = (i64)bad[0]; }
 }
 
 // every record's first slot and first column: the workgroup's (k_cig_scan) plus the exclusive sums in front of it inside the workgroup
 __global__ void __launch_bounds__(256) k_cig_prefix(i64 W, i64 nwg, const i32 *ns, const i32 *nc, const i64 *wg, i64 *ps, i64 *pc)
 {
 	__shared__ i64 s_w[8];
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	const i64 w = (i64)blockIdx.x * 256 + tid;
-	const i64 v0 = w < W ? ns[w] : 0, v1 = w < W ? nc[w] : 0;
-	i64 s0 = v0, s1 = v1;
-	for (int d = 1; d < 64; d <<= 1) { const i64 x = __shfl_up(s0, d), y = __shfl_up(s1, d); if (lane >= d) { s0 += x; s1 += y; } }
-	if (lane == 63) { s_w[wv] = s0; s_w[4 + wv] = s1; }
-	__syncthreads();
-	i64 p0 = 0, p1 = 0; for (int k = 0; k < wv; k++) { p0 += s_w[k]; p1 += s_w[4 + k]; }
-	if (w < W) { ps[w] = wg[blockIdx.x] + p0 + s0 - v0; pc[w] = wg[nwg + blockIdx.x] + p1 + s1 - v1; }
+	const i64 w = (i64)blockIdx.x * 256 + threadIdx.x;
+	i64 v[2] = { w < W ? ns[w] : 0, w < W ? nc[w] : 0 };
+	wg_excl_scan(v, s_w);                           // (both arrays behind one barrier)
+	if (w < W) { ps[w] = wg[blockIdx.x] + v[0]; pc[w] = wg[nwg + blockIdx.x] + v[1]; }
 }
 
 // a block's ops: from its first record's slot to the next block's
@@ -290,8 +248,7 @@ __global__ void __launch_bounds__(256) k_cig_pack(i32 nb, const CigBlk *blk, con
 {
 	const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
 	if (s >= n_ops) return;
-	i32 lo = 0, hi = nb;                            // last block with cig_off <= s (blocks without ops share their offset with the next one)
-	while (hi - lo > 1) { const i32 m = (lo + hi) >> 1; if (out[m].cig_off <= s) lo = m; else hi = m; }
+	const i32 lo = blk_last_le(out, nb, &gsa_block_cigar::cig_off, s);      // (blocks without ops share their offset with the next one)
 	const i64 off = out[lo].cig_off; const i32 n = out[lo].n_cig;
 	const i64 k = s - off;
 	if (k < 0 || k >= n) return;                    // (cannot happen: the blocks' ranges tile [0, n_ops))
@@ -304,22 +261,17 @@ __global__ void __launch_bounds__(256) k_cig_pack(i32 nb, const CigBlk *blk, con
 
 int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out, bool pos)
 {
-	out->n_blocks = 0; out->n_ops = 0; out->blk = nullptr; out->ops = nullptr;
-	// the blocks of contig k in the final list, and where its records start
-	size_t b0 = 0, nb = c->h_blocks.size(); i64 f0 = 0;
-	if (c->bnd.n) {
-		if (c->h_blocks.empty() || c->b_nblk.size() != (size_t)c->bnd.n) nb = 0;
-		else { for (i32 j = 0; j < k; j++) b0 += (size_t)c->b_nblk[(size_t)j]; nb = (size_t)c->b_nblk[(size_t)k]; f0 = c->b_frag0[(size_t)k]; }
-	}
+	const ResultRange rr = result_range(c, k);
+	const size_t nb = rr.nb;
 	if (nb == 0 || c->n_frags <= 0) return GSA_OK;
 	hipStream_t st = c->stream;
 	if (!pin_ensure<CigBlk>(c, c->p_cblk, nb + 1) || !pin_ensure<i64>(c, c->p_chdr, 8) || !pin_ensure<gsa_block_cigar>(c, c->p_cout, nb)) return GSA_ERR_NOMEM;
 	CigBlk *hb = c->p_cblk.as<CigBlk>(); i64 W = 0;
 	for (size_t j = 0; j < nb; j++) {
-		const gsa_block &bl = c->h_blocks[b0 + j];
+		const gsa_block &bl = c->h_blocks[rr.b0 + j];
 		const i32 nf = bl.n_frag > 0 ? bl.n_frag : 0;
 		if (W + nf >= (1ll << 31) - 256) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_block_cigars: too many records");
-		CigBlk &v = hb[j]; v.frag_off = bl.frag_off + f0; v.n_frag = nf; v.bdir = bl.bdir; v.wbase = (i32)W; v._pad = 0;
+		CigBlk &v = hb[j]; v.frag_off = bl.frag_off + rr.f0; v.n_frag = nf; v.bdir = bl.bdir; v.wbase = (i32)W; v._pad = 0;
 		W += nf;
 	}
 	{ CigBlk &v = hb[nb]; v.frag_off = 0; v.n_frag = 0; v.bdir = 1; v.wbase = (i32)W; v._pad = 0; }
@@ -337,10 +289,7 @@ int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out, bool pos)
 	GSA_CHECK(c, hipMemsetAsync(bad, 0, 3 * sizeof(unsigned long long), st));
 	CigIn a;
 	a.nb = (i32)nb; a.W = W; a.blk = dblk;
-	a.frag = c->f_rec.as<gsa_frag>(); a.ftype = c->f_type.as<i32>(); a.fjob = c->f_job.as<i32>();
-	a.j_nops = c->j_nops.as<i32>(); a.j_opsoff = c->j_opsoff.as<i64>(); a.j_ops = c->d_ops.as<uint8_t>();
-	a.e_nops = c->e_nops.as<i32>(); a.e_opsoff = c->e_opsoff.as<i64>(); a.e_ops = c->e_ops.as<uint8_t>();
-	a.query = c->q_dev; a.ref = c->di.ref; a.n_out = 0; a.run_r = nullptr; a.run_q = nullptr;
+	gap_in_fill(c, a); a.n_out = 0; a.run_r = nullptr; a.run_q = nullptr;
 	hipLaunchKernelGGL((k_cig_pass<false, false>), dim3((unsigned)nwg), dim3(256), 0, st, a, ns, nc, wg, nwg, bad, dout, (const i64 *)nullptr, (const i64 *)nullptr, (i64 *)nullptr);
 	GSA_CHECK(c, hipGetLastError());
 	hipLaunchKernelGGL(k_cig_scan, dim3(1), dim3(256), 0, st, nwg, wg, (const unsigned long long *)bad, W, ps, pc, hdr);

@@ -13,10 +13,9 @@
 //           scan's total, every base's position against the text it is read from.
 // No workgroup waits for another, nothing spins.
 #include <cstring>
-#include "gsa_ctx.h"
 #include "gsa_fm.h"
+#include "gsa_walk.h"
 
-#define ENS(T, buf, n) do { if (!dev_ensure<T>(c, c->buf, (size_t)(n))) return GSA_ERR_NOMEM; } while (0)
 #define CS_SERIAL 64
 
 struct CsIn {
@@ -49,39 +48,20 @@ __global__ void __launch_bounds__(256) k_cs_len(i64 n, const u32 *ops, i64 *len,
 	if (tid == 0) wg[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
 
-// second level (the pattern of k_cig_scan, one array): the workgroups' sums -> their first bytes; the total goes behind the last op's offset and to the host's header
+// second level: the workgroups' sums -> their first bytes; the total goes behind the last op's offset and to the host's header
 __global__ void __launch_bounds__(256) k_cs_scan(i64 nwg, i64 *wg, i64 n, i64 *po, i64 *hdr)
 {
 	__shared__ i64 s_w[4];
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	i64 carry = 0;
-	for (i64 base = 0; base < nwg; base += 256) {
-		const i64 i = base + tid;
-		const i64 v = i < nwg ? wg[i] : 0;
-		i64 s = v;
-		for (int d = 1; d < 64; d <<= 1) { const i64 y = __shfl_up(s, d); if (lane >= d) s += y; }
-		if (lane == 63) s_w[wv] = s;
-		__syncthreads();
-		i64 pre = 0; for (int k = 0; k < wv; k++) pre += s_w[k];
-		if (i < nwg) wg[i] = carry + pre + s - v;
-		carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-		__syncthreads();
-	}
-	if (tid == 0) { po[n] = carry; hdr[0] = carry; }
+	const i64 total = wg_scan_sums(wg, nwg, s_w);
+	if (threadIdx.x == 0) { po[n] = total; hdr[0] = total; }
 }
 
 __global__ void __launch_bounds__(256) k_cs_prefix(i64 n, const i64 *len, const i64 *wg, i64 *po)
 {
 	__shared__ i64 s_w[4];
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	const i64 s = (i64)blockIdx.x * 256 + tid;
-	const i64 v = s < n ? len[s] : 0;
-	i64 x = v;
-	for (int d = 1; d < 64; d <<= 1) { const i64 y = __shfl_up(x, d); if (lane >= d) x += y; }
-	if (lane == 63) s_w[wv] = x;
-	__syncthreads();
-	i64 pre = 0; for (int k = 0; k < wv; k++) pre += s_w[k];
-	if (s < n) po[s] = wg[blockIdx.x] + pre + x - v;
+	const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
+	const i64 e = wg_excl_scan<i64>(s < n ? len[s] : 0, s_w);
+	if (s < n) po[s] = wg[blockIdx.x] + e;
 }
 
 // a block's string: from its first op's byte to the byte behind its last op (the blocks' op ranges tile [0, n_ops), so that is the next block's first byte)
@@ -101,8 +81,7 @@ struct CsOp { i64 at, rp; i32 qp; u32 L, cls; bool fwd; };           // first by
 __device__ CsOp cs_load(const CsIn &a, i64 s)
 {
 	CsOp o;
-	i32 lo = 0, hi = a.nb;                          // last block with cig_off <= s (blocks without ops share their offset with the next one)
-	while (hi - lo > 1) { const i32 m = (lo + hi) >> 1; if (a.cig[m].cig_off <= s) lo = m; else hi = m; }
+	const i32 lo = blk_last_le(a.cig, a.nb, &gsa_block_cigar::cig_off, s);      // (blocks without ops share their offset with the next one)
 	const i64 off = a.cig[lo].cig_off; const i64 n = a.cig[lo].n_cig;
 	const u32 op = a.ops[s];
 	o.fwd = a.blk[lo].bdir != 0; o.L = op >> 4; o.cls = op & 15u; o.at = a.po[s];
@@ -162,8 +141,7 @@ __global__ void __launch_bounds__(256) k_cs_emit(CsIn a)
 
 int block_cs(gsa_ctx *c, i32 k, gsa_cs *out, gsa_cigars *cig_out)
 {
-	out->n_blocks = 0; out->n_bytes = 0; out->blk = nullptr; out->cs = nullptr;
-	gsa_cigars cig;
+	gsa_cigars cig = { 0, 0, nullptr, nullptr };
 	const int rc_cig = block_cigars(c, k, &cig, true);
 	if (cig_out) *cig_out = cig;
 	if (rc_cig) return rc_cig;

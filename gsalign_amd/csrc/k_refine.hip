@@ -19,7 +19,6 @@
 #define EARLY_CHUNK 4096     // large gaps copied together with the leaf table (more -> a second copy)
 #define GID(n) i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= (n)) return
 #define LAUNCH(k, n, ...) hipLaunchKernelGGL(k, dim3(grid_for((size_t)(n), TPB)), dim3(TPB), 0, st, __VA_ARGS__)
-#define ENS(T, buf, n) do { if (!dev_ensure<T>(c, c->buf, (size_t)(n))) return GSA_ERR_NOMEM; } while (0)
 #define RC(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
 // (each struct below is one fused pass: value -> exclusive scan -> emit, see gsa_scan.h; `ub`, the

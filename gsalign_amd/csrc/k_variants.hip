@@ -14,31 +14,26 @@
 // jobs launched early) and the two sequences -- an aligned column is the sequence byte or '-' (ksw2_alignment.cpp:264-272:
 // 'D' puts '-' into aln1, 'I' into aln2); an equal-length gap that needed no DP is all 'M'.  One byte per column instead
 // of two, and one code path.
-#include "gsa_ctx.h"
 #include "gsa_fm.h"
-#include "gsa_gap.h"
+#include "gsa_walk.h"
 
-#define ENS(T, buf, n) do { if (!dev_ensure<T>(c, c->buf, (size_t)(n))) return GSA_ERR_NOMEM; } while (0)
 #define VAR_SERIAL 64      // records of at most this many columns are walked by one lane, longer ones by a wavefront in 64-column steps
 
 struct VarBlk { i64 frag_off; i32 n_frag, chr, block, wbase; };      // one surviving, non-duplicate block: first record (absolute), records, its reference sequence, index in gsa_result::blocks, first work item
-struct VarIn {
+struct VarIn : GapIn {
 	i32 nvb; i64 W; const VarBlk *blk;
-	const gsa_frag *frag; const i32 *ftype, *fjob;
-	const i32 *j_nops; const i64 *j_opsoff; const uint8_t *j_ops;      // DP jobs of the job list
-	const i32 *e_nops; const i64 *e_opsoff; const uint8_t *e_ops;      // DP jobs launched early from the leaf table (fjob <= -2)
-	const uint8_t *query, *ref; i32 qoff;                              // qoff: start of the contig in a bundle's concatenation
+	i32 qoff;                                                          // start of the contig in a bundle's concatenation
 	const i64 *chr_end; i32 n_ends; i64 G;
 	i64 n_out;
 };
 
 enum { VC_NONE = 0, VC_DEL = 1, VC_INS = 2, VC_ONE = 3, VC_WALK = 4 };
-struct VarGap { i32 cls, L; const uint8_t *op; i32 qpos, qlen, rlen; i64 rpos; };
-enum { VC_BAD = 5 };      // a DP record without a DP job: cannot happen (OpDpJobs gives every FT_DP record a job >= 0 or an early job <= -2); counted and reported, never skipped silently
+struct VarGap { i32 cls = VC_NONE, L = 0; const uint8_t *op = nullptr; i32 qpos = 0, qlen = 0, rlen = 0; i64 rpos = 0; };
+enum { VC_BAD = 5 };      // a DP record without a DP job (gap_ops): counted and reported
 
 __device__ __forceinline__ VarGap var_load(const VarIn &a, i64 i)
 {
-	VarGap g; g.cls = VC_NONE; g.L = 0; g.op = nullptr; g.qpos = 0; g.qlen = 0; g.rlen = 0; g.rpos = 0;
+	VarGap g;
 	const i32 t = a.ftype[i];
 	if (t == FT_SEED) return g;
 	const gsa_frag f = a.frag[i];
@@ -47,15 +42,7 @@ __device__ __forceinline__ VarGap var_load(const VarIn &a, i64 i)
 	if (f.qlen == 0) g.cls = VC_DEL;
 	else if (f.rlen == 0) g.cls = VC_INS;
 	else if (f.qlen == 1 && f.rlen == 1) g.cls = VC_ONE;
-	else {
-		g.cls = VC_WALK;
-		if (t == FT_DP) {
-			const i32 fj = a.fjob[i];
-			if (fj >= 0) { g.op = a.j_ops + a.j_opsoff[fj]; g.L = a.j_nops[fj]; }
-			else if (fj <= -2) { const i32 e = -2 - fj; g.op = a.e_ops + a.e_opsoff[e]; g.L = a.e_nops[e]; }
-			else g.cls = VC_BAD;
-		} else g.L = f.qlen;                                        // FT_EQ: every column is a pair of bases
-	}
+	else g.cls = gap_ops(a, i, t, f, g.op, g.L) ? VC_WALK : VC_BAD;
 	return g;
 }
 
@@ -147,27 +134,16 @@ __global__ void __launch_bounds__(256) k_var_pass(VarIn a, i32 *nv, i64 *wg, uns
 	const i64 w = (i64)blockIdx.x * 256 + tid;
 	if (tid == 0) s_n = 0;
 	if (tid < 3) s_k[tid] = 0;
-	VarGap g; g.cls = VC_NONE; g.L = 0; g.op = nullptr; g.qpos = 0; g.qlen = 0; g.rlen = 0; g.rpos = 0;
+	VarGap g;
 	i32 b = 0;
 	if (w < a.W) {
-		i32 lo = 0, hi = a.nvb;                      // last block with wbase <= w
-		while (hi - lo > 1) { const i32 m = (lo + hi) >> 1; if (a.blk[m].wbase <= w) lo = m; else hi = m; }
-		b = lo;
+		b = blk_last_le(a.blk, a.nvb, &VarBlk::wbase, w);
 		g = var_load(a, a.blk[b].frag_off + (w - a.blk[b].wbase));
 	}
 	i32 cnt[3] = { 0, 0, 0 };
 	i64 slot = 0;
 	const i64 wgb = EMIT ? wg[blockIdx.x] : 0;      // the workgroup's first slot
-	if (EMIT) {
-		// exclusive scan of the workgroup's counts
-		const i32 v = w < a.W ? nv[w] : 0;
-		i32 s = v;
-		for (int d = 1; d < 64; d <<= 1) { const i32 x = __shfl_up(s, d); if (lane >= d) s += x; }
-		if (lane == 63) s_w[wv] = s;
-		__syncthreads();
-		i32 pre = 0; for (int k = 0; k < wv; k++) pre += s_w[k];
-		slot = wgb + pre + s - v;
-	}
+	if (EMIT) slot = wgb + wg_excl_scan<i32>(w < a.W ? nv[w] : 0, s_w);      // the workgroup's first slot plus the counts in front of the record inside it
 	__syncthreads();
 	const bool wide = g.cls == VC_WALK && g.L > VAR_SERIAL;
 	i32 n = 0;
@@ -181,8 +157,7 @@ __global__ void __launch_bounds__(256) k_var_pass(VarIn a, i32 *nv, i64 *wg, uns
 		// (the record's look-up is repeated by every lane of the wavefront: the addresses are uniform, so the loads are one request each)
 		const int t = s_list[q];
 		const i64 wt = (i64)blockIdx.x * 256 + t;
-		i32 lo = 0, hi = a.nvb;
-		while (hi - lo > 1) { const i32 m = (lo + hi) >> 1; if (a.blk[m].wbase <= wt) lo = m; else hi = m; }
+		const i32 lo = blk_last_le(a.blk, a.nvb, &VarBlk::wbase, wt);
 		const VarGap gt = var_load(a, a.blk[lo].frag_off + (wt - a.blk[lo].wbase));
 		const i32 nt = var_wave<EMIT>(a, gt, a.blk[lo], out, EMIT ? wgb + s_val[t] : 0, cnt);
 		if (!EMIT && lane == 0) s_val[t] = nt;
@@ -203,40 +178,22 @@ __global__ void __launch_bounds__(256) k_var_pass(VarIn a, i32 *nv, i64 *wg, uns
 __global__ void __launch_bounds__(256) k_var_scan(i64 nwg, i64 *wg, const unsigned long long *kinds, i64 *hdr)
 {
 	__shared__ i64 s_w[4];
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	i64 carry = 0;
-	for (i64 base = 0; base < nwg; base += 256) {
-		const i64 i = base + tid;
-		const i64 v = i < nwg ? wg[i] : 0;
-		i64 s = v;
-		for (int d = 1; d < 64; d <<= 1) { const i64 x = __shfl_up(s, d); if (lane >= d) s += x; }
-		if (lane == 63) s_w[wv] = s;
-		__syncthreads();
-		i64 pre = 0; for (int k = 0; k < wv; k++) pre += s_w[k];
-		if (i < nwg) wg[i] = carry + pre + s - v;
-		carry += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-		__syncthreads();
-	}
-	if (tid == 0) { hdr[0] = carry; hdr[1] = (i64)kinds[0]; hdr[2] = (i64)kinds[1]; hdr[3] = (i64)kinds[2]; hdr[4] = (i64)kinds[3]; }
+	const i64 total = wg_scan_sums(wg, nwg, s_w);
+	if (threadIdx.x == 0) { hdr[0] = total; hdr[1] = (i64)kinds[0]; hdr[2] = (i64)kinds[1]; hdr[3] = (i64)kinds[2]; hdr[4] = (i64)kinds[3]; }
 }
 
 int call_variants(gsa_ctx *c, i32 k, gsa_variants *out)
 {
-	out->n = 0; out->v = nullptr; out->n_snv = out->n_ins = out->n_del = 0;
-	// the blocks of contig k in the final list, and where its records start
-	size_t b0 = 0, nb = c->h_blocks.size(); i64 f0 = 0; i32 qoff = 0;
-	if (c->bnd.n) {
-		if (c->h_blocks.empty() || c->b_nblk.size() != (size_t)c->bnd.n) nb = 0;
-		else { for (i32 j = 0; j < k; j++) b0 += (size_t)c->b_nblk[(size_t)j]; nb = (size_t)c->b_nblk[(size_t)k]; f0 = c->b_frag0[(size_t)k]; qoff = c->b_off[(size_t)k]; }
-	}
+	const ResultRange rr = result_range(c, k);
+	const size_t nb = rr.nb;
 	if (nb == 0 || c->n_frags <= 0) return GSA_OK;
 	hipStream_t st = c->stream;
 	if (!pin_ensure<VarBlk>(c, c->p_vblk, nb + 1) || !pin_ensure<i64>(c, c->p_vhdr, 5)) return GSA_ERR_NOMEM;
 	VarBlk *hb = c->p_vblk.as<VarBlk>(); i32 nvb = 0; i64 W = 0;
 	for (size_t j = 0; j < nb; j++) {
-		const gsa_block &bl = c->h_blocks[b0 + j];
+		const gsa_block &bl = c->h_blocks[rr.b0 + j];
 		if (bl.bdup || bl.n_frag <= 0) continue;                    // (:22)
-		VarBlk &v = hb[nvb++]; v.frag_off = bl.frag_off + f0; v.n_frag = bl.n_frag; v.chr = bl.chr; v.block = (i32)j; v.wbase = (i32)W;
+		VarBlk &v = hb[nvb++]; v.frag_off = bl.frag_off + rr.f0; v.n_frag = bl.n_frag; v.chr = bl.chr; v.block = (i32)j; v.wbase = (i32)W;
 		W += bl.n_frag;
 	}
 	if (W == 0) return GSA_OK;
@@ -252,10 +209,7 @@ int call_variants(gsa_ctx *c, i32 k, gsa_variants *out)
 	GSA_CHECK(c, hipMemsetAsync(kinds, 0, 4 * sizeof(unsigned long long), st));
 	VarIn a;
 	a.nvb = nvb; a.W = W; a.blk = c->d_vblk.as<VarBlk>();
-	a.frag = c->f_rec.as<gsa_frag>(); a.ftype = c->f_type.as<i32>(); a.fjob = c->f_job.as<i32>();
-	a.j_nops = c->j_nops.as<i32>(); a.j_opsoff = c->j_opsoff.as<i64>(); a.j_ops = c->d_ops.as<uint8_t>();
-	a.e_nops = c->e_nops.as<i32>(); a.e_opsoff = c->e_opsoff.as<i64>(); a.e_ops = c->e_ops.as<uint8_t>();
-	a.query = c->q_dev; a.ref = c->di.ref; a.qoff = qoff;
+	gap_in_fill(c, a); a.qoff = rr.qoff;
 	a.chr_end = c->di.chr_end; a.n_ends = c->di.n_ends; a.G = c->di.G; a.n_out = 0;
 	hipLaunchKernelGGL(k_var_pass<false>, dim3((unsigned)nwg), dim3(256), 0, st, a, c->d_vcnt.as<i32>(), c->d_vwg.as<i64>(), kinds, (gsa_variant *)nullptr);
 	hipLaunchKernelGGL(k_var_scan, dim3(1), dim3(256), 0, st, nwg, c->d_vwg.as<i64>(), (const unsigned long long *)kinds, hdr);
