@@ -36,7 +36,7 @@ struct HostBlock {       // one entry of the reference's AlnBlockVec, as leaf ra
 };
 
 // A query slot: the device copy of a contig, or of a bundle's concatenation with its tables.  A context has two: while the contig
-// of one slot goes through the stages, the next one is uploaded into the other on `stream_up` (gsa_prefetch_contig /
+// of one slot goes through the stages, the next one is uploaded into the other by the Uploader's thread and copy stream (gsa_prefetch_contig /
 // gsa_prefetch_bundle; gsa_align_many does it by itself), so the H2D copy of a contig -- 4.8 ms for 250 Mb at 52 GB/s, the reference
 // reads QueryChrVec[i].seq from host memory every iteration (GSAlign.cpp:483-490) -- hides behind its predecessor's stages.
 struct QuerySlot {
@@ -50,6 +50,7 @@ struct QuerySlot {
 	std::atomic<int> busy{0};                      // uploads of this slot the Uploader has not finished yet
 	std::atomic<int> up_err{0};                    // first hipError_t of an upload into this slot (the Uploader thread sets it, slot_finish turns it into GSA_ERR_HIP)
 };
+static inline void slot_wait(QuerySlot &s) { while (s.busy.load(std::memory_order_acquire) > 0) std::this_thread::yield(); }      // (the slot functions of gsa_query.hip, gsa_destroy)
 
 // Uploads of query sequences, ONE AT A TIME per device index, in the order they were asked for (a thread + a copy stream; the contexts
 // that share an index -- gsa_clone -- share it).  Why not a copy stream per context: copies that run side by side share the link, so
@@ -94,7 +95,7 @@ struct gsa_ctx {
 	Options opt;
 	Uploader *up = nullptr; bool own_up = false;
 	hipStream_t stream = nullptr;
-	hipStream_t stream_seed = nullptr;      // (experiment, GSA_SEED_CUS: the seed-search kernels on a stream restricted to part of the CUs)
+	hipStream_t stream_seed = nullptr;      // GSA_CREATE_PRIO: the seed-search kernels on a stream of their own, so that they do not inherit the main stream's priority (ctx_private_init); else null
 	hipEvent_t ev_seed_fork = nullptr;
 	u64 seed_ticket = 0;                    // value of the seed kernel's ticket counter (d_cnt[16]) before the next launch
 	int n_cus = 0;
@@ -102,7 +103,7 @@ struct gsa_ctx {
 	hipStream_t stream_aux[4] = {nullptr, nullptr, nullptr, nullptr};   // [3]: the striped DP's lower size class beside its upper one (option dp_side); [0] early striped DP, [1] tiny DP + strings + sums, [2] records to the host (four streams in all: one per hardware queue)
 	std::string err;
 	Params prm;
-	DevIndex di;
+	DevIndex di = {};
 	gsa_ctx *index_owner = nullptr;                // gsa_clone: the context whose device index this one borrows (nullptr = own)
 	gsa_ctx *lender = nullptr;                     // gsa_clone: the context `di` was copied from -- its presence bitmap / short k-mer table are read through that copy
 	std::atomic<int> n_borrowers{0};               // live clones made FROM this context (gsa_set_params must not rebuild the tables they read)
@@ -112,11 +113,11 @@ struct gsa_ctx {
 	bool prof_seed = false;                        // time the seed kernel only (two events instead of ten per contig)
 	bool count_blocks = false;                     // run the accounting build of the seed kernel (exact algorithmic Occ-block count)
 	u64 dbg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-	hipEvent_t ev[28];
-	float kernel_ms[8];
+	hipEvent_t ev[28] = {};
+	float kernel_ms[8] = {};
 	double wall_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int64_t wall_n = 0;      // host wall clock spent in [0] the query set-up (upload / wait for the prefetch) and [s] stage s of gsa_run_to, summed over contigs since gsa_set_profiling (gsa_get_wall_sums)
 	double acc_seed_ms = 0.0;                      // seed-search kernel time summed over the contigs since gsa_set_profiling (flag bit 2), see gsa_get_timings
-	u64 counters[8];
+	u64 counters[8] = {};
 
 	// index (device)
 	DevBuf d_bwt, d_bwt_ref, d_occ_base, d_sa, d_ref, d_chr_end, d_chr_of_end;
@@ -131,7 +132,7 @@ struct gsa_ctx {
 	int qbits = 1, pdbits = 1;
 	i64 pd_span = 0;                               // number of PosDiff key values: 2G + qlen + 2, a bundle: contigs x stride
 
-	// ---- a bundle of contigs in one pass (Bundle, gsa_internal.h; gsa_align_bundle in gsa_api.hip) ----
+	// ---- a bundle of contigs in one pass (Bundle, gsa_internal.h; gsa_align_bundle in gsa_api.hip, set_query_bundle in gsa_query.hip) ----
 	Bundle bnd = { 0, 0, 0, nullptr, nullptr }; bool bundle_call = false;
 	std::vector<i32> b_off, b_qlen;               // start of contig k in the concatenation [n + 1], its length (copied from the slot that holds the bundle)
 	std::vector<std::vector<HostBlock> > b_lists;  // the AlnBlockVec of every contig while the list logic runs (stages 3-6)
@@ -246,6 +247,26 @@ struct gsa_ctx {
 	double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 };
 
+// Every DevBuf member above and in QuerySlot, once: GSA_DEVBUFS the device buffers (gsa_destroy frees them with hipFree, gsa_debug_buffers lists them), GSA_PINBUFS the pinned
+// host buffers (hipHostFree).  A member missing here leaks with every context: tests/test_build_checks.py holds the two lists against the declarations.
+#define GSA_DEVBUFS(X) \
+	X(d_bwt) X(d_bwt_ref) X(d_occ_base) X(d_sa) X(d_ref) X(d_chr_end) X(d_chr_of_end) X(qs[0].d_query) X(qs[1].d_query) X(qs[0].d_bndtab) X(qs[1].d_bndtab) \
+	X(tmp) X(d_cnt) X(d_zero) X(d_mail) X(d_lb_status[0]) X(d_lb_status[1]) X(d_sa_dense) X(d_kmer) X(d_kmer_lo) X(d_pres) X(d_ref2) \
+	X(d_cand_s) X(d_cand_len) X(d_cand_x0) X(d_cand_freq) X(d_onpath) X(d_cand_cnt) X(d_heavy) X(dn_lf) X(dn_x0) X(d_chunk_hits) X(d_chunk_base) \
+	X(d_key_a) X(d_key_b) X(d_val_a) X(d_val_b) X(s_q) X(s_len) X(s_r) X(s_gid) X(d_flag) X(d_scan) X(g_beg) X(w_j0) X(d_pdbm) X(d_pdby) X(d_pdcb) X(d_gpre) X(d_key_c) X(d_val_c) \
+	X(a_q) X(a_len) X(a_r) X(a_gb) X(a_ge) X(a_uniq) X(a_cu) X(a_alive) X(a_ws) X(a_wid) X(a_next) X(a_brk) X(a_aurank) X(a_aulist) X(a_runinfo) X(w_best) X(w_sum) X(w_n) \
+	X(d_btab) X(d_flag2) X(d_scan2) X(d_i64a) X(b_q) X(b_len) X(b_r) X(b_gb) X(b_ge) X(c_q) X(c_len) X(c_r) X(c_gb) X(c_ge) X(c_bid) X(blk_beg) X(blk_end) X(blk_score) \
+	X(r_q) X(r_len) X(r_r) X(r_bid) X(r_tmp_q) X(r_tmp_len) X(r_tmp_r) X(r_tmp_bid) X(r_cut4) X(r_cut5) X(r_simjob) X(r_simres) X(d_leaf) \
+	X(fb_seedbase) X(fb_sbeg) X(fb_fragbase) X(f_rec) X(f_rec16) X(f_type) X(f_mism) X(f_alnlen) X(f_job) X(f_score) \
+	X(d_dp_lane_order) X(d_dp_bnd) X(d_dp_ctr) X(d_dp_jobs) X(d_dp_large) X(d_tail) \
+	X(e_id) X(e_rec) X(e_list) X(e_off1) X(e_off2) X(e_opsoff) X(e_nops) X(e_ops) X(e_rev) X(r_head) X(f_early) X(r_orig) X(r_tmp_orig) \
+	X(j_frag) X(j_opsoff) X(j_nops) X(d_ops) X(j_cells) X(d_alnoff) X(bl_alnlen) X(bl_score) X(d_bblk) X(d_dp_arena) \
+	X(d_vblk) X(d_vcnt) X(d_vwg) X(d_var) X(d_cblk) X(d_cout) X(d_ccnt) X(d_cwg) X(d_cpre) X(d_crun) X(d_cops) X(d_crpos) X(d_cqpos) X(d_slen) X(d_swg) X(d_spre) X(d_sout) X(d_cs) \
+	X(leaf[0]) X(leaf[1]) X(leaf[2]) X(leaf[3]) X(leaf[4]) X(leaf[5]) X(leaf[6]) X(leaf[7]) X(leaf[8])
+#define GSA_PINBUFS(X) \
+	X(p_frags) X(p_tail) X(p_leaf) X(p_blk) X(p_dp) X(p_sj) X(p_sj_early) X(p_jpatch) X(p_early) X(qs[0].p_bndtab) X(qs[1].p_bndtab) X(p_bblk) X(p_ba0) \
+	X(p_vblk) X(p_vhdr) X(p_var) X(p_cblk) X(p_chdr) X(p_cout) X(p_cops) X(p_shdr) X(p_sout) X(p_cs)
+
 // A buffer is about to be freed: nothing of this context may still use it -- not only the main stream: the early striped DP launch runs on
 // stream_aux[0] beside stages 3-7 and shares direction / boundary / ticket buffers with the late launch, strings and record copies run on
 // stream_aux[1] / [2].  (Until round 4 only the main stream was waited for: a late launch that outgrew a shared buffer while the early one
@@ -256,7 +277,7 @@ static inline void ctx_quiesce(gsa_ctx *c)
 	for (int i = 0; i < 4; i++) if (c->stream_aux[i]) hipStreamSynchronize(c->stream_aux[i]);
 }
 
-void *dev_take_reserved(int device, size_t bytes, size_t *got);   // gsa_api.hip  (gsa_reserve_index: memory set aside for the dense SA / the k-mer table)
+void *dev_take_reserved(int device, size_t bytes, size_t *got);   // gsa_create.hip  (gsa_reserve_index: memory set aside for the dense SA / the k-mer table)
 // exact = true: the index tables -- asked for once, never grown: no slack (the dense SA of a human index is 49 GB: half again was 25 GB of HBM and 0.1 s of gsa_create)
 template <class T> static inline T *dev_ensure(gsa_ctx *c, DevBuf &b, size_t n, bool exact = false)
 {
@@ -319,8 +340,17 @@ void dp_count_cells(gsa_ctx *c, i32 n_ub, const i32 *len1, const i32 *len2, hipS
 int call_variants(gsa_ctx *c, i32 k, gsa_variants *out);   // k_variants.hip  (VariantIdentification over the stage-8 result of contig k)
 int block_cigars(gsa_ctx *c, i32 k, gsa_cigars *out, bool pos = false);      // k_cigar.hip  (the CIGAR of every block of the stage-8 result of contig k; pos: the runs' first positions too, into d_crpos / d_cqpos)
 int block_cs(gsa_ctx *c, i32 k, gsa_cs *out, gsa_cigars *cig_out = nullptr);   // k_cs.hip  (the cs string of every block: the CIGAR pass with positions, then its own three passes; cig_out: that CIGAR pass's answer)
-int ctx_create_bare(int device, gsa_ctx **out);            // gsa_api.hip  (a context with NO index: device, stream, mailbox and scratch -- what the sort and the fused passes need; gsa_destroy frees it)
 int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds);   // k_index.hip  (suffix sort + BWT / Occ / SA samples of forward + reverse complement)
+int host_stage4_5_6(gsa_ctx *c, int stage);    // gsa_blocks.cpp
+int host_stage8_finish(gsa_ctx *c);            // gsa_blocks.cpp
+int build_block_view(gsa_ctx *c);              // gsa_blocks.cpp
+void bundle_split_lists(gsa_ctx *c);           // gsa_blocks.cpp  (a bundle of contigs: one AlnBlockVec per contig for stages 4-6 ...
+void bundle_join_lists(gsa_ctx *c);            // gsa_blocks.cpp   ... joined again, contig after contig, for stages 7-8)
+// the host side of the C ABI, file to file
+#define GSA_BUNDLE_MAX_CONTIGS 4096
+int reset_run_state(gsa_ctx *c);      // gsa_query.hip  (back to stage 0: nothing of the previous run in flight or half-consumed; the query, its geometry and `bnd` stay)
+int set_query_bundle(gsa_ctx *c, const char *const *query, const int32_t *qlen, int32_t n, bool dev_q);   // gsa_query.hip  (gsa_align_bundle's gsa_set_query)
+int cs_call(gsa_ctx *c, int32_t k, gsa_cs *out, gsa_cigars *cig);   // gsa_api.hip  (gsa_block_cs; cig: the CIGARs the pass computed on its way, for gsa_align_many_ex)
 struct LgJob { i32 job, m, n; };
 int launch_stripes(gsa_ctx *c, hipStream_t ss, std::vector<LgJob> &large, const uint8_t *pool1, const i64 *off1, const uint8_t *pool2, const i64 *off2,
                    uint8_t *ops, const i64 *ops_off, i32 *ops_len, uint8_t *rev, int err_slot);   // k_dp_stripe.hip

@@ -88,10 +88,10 @@ struct Params {
 
 #define GSA_CHECK(ctx, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return gsa_fail((ctx), GSA_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)
 
-int gsa_fail(gsa_ctx *ctx, int code, const std::string &msg);
+int gsa_fail(gsa_ctx *ctx, int code, const std::string &msg);      // gsa_create.hip  (ctx == nullptr: the text goes to gsa_last_error(NULL) of this thread)
 
-// ---- rocPRIM-backed primitives (gsa_prim.hip) --------------------------------
-// All asynchronous on `stream`; `tmp` is a reusable scratch buffer that grows.
+// ---- the pipeline's own radix sort (gsa_sort.hip) -----------------------------
+// Asynchronous on the context's stream; `tmp` is a reusable scratch buffer that grows.
 int gsa_sort_pairs_u64_u32(gsa_ctx *, const u64 *kin, u64 *kout, const u32 *vin, u32 *vout, size_t n, int begin_bit, int end_bit);      // gsa_sort.hip: stable LSD radix sort, kin / vin untouched
 
 static inline int ceil_log2_u64(u64 v) { int b = 0; while ((1ull << b) < v && b < 63) b++; return b; }

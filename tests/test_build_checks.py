@@ -38,6 +38,31 @@ def test_scanner_sees_a_spill_in_front_of_the_exec_restore(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().endswith("clean"), r.stdout
 
 
+def test_buffer_lists_name_every_devbuf_member_once():
+    """gsa_destroy frees what GSA_DEVBUFS (hipFree) and GSA_PINBUFS (hipHostFree) name: every DevBuf member of gsa_ctx and of its two QuerySlots must stand in
+    exactly one of the two lists, once, array members element by element, and the lists name nothing else (a member left out leaks with every context)."""
+    import re
+    src = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "gsalign_amd", "csrc", "gsa_ctx.h")).read())
+
+    def members(struct):
+        body = re.search(r"\bstruct %s \{(.*?)\n\};" % struct, src, re.S).group(1)
+        out = []
+        for stmt in body.split(";"):
+            m = re.match(r"\s*DevBuf\s+(.+)$", stmt, re.S)
+            for decl in (m.group(1).split(",") if m else []):
+                name, dim = re.fullmatch(r"\s*(\w+)\s*(?:\[(\d+)\])?\s*", decl).groups()
+                out += [f"{name}[{k}]" for k in range(int(dim))] if dim else [name]
+        return out
+
+    declared = members("gsa_ctx") + [f"qs[{i}].{m}" for i in range(2) for m in members("QuerySlot")]
+    listed = []
+    for macro in ("GSA_DEVBUFS", "GSA_PINBUFS"):
+        text = re.search(r"#define %s\(X\)((?:[^\n]*\\\n)*[^\n]*)" % macro, src).group(1)
+        listed += re.findall(r"X\(([^)]+)\)", text)
+    assert len(declared) > 150 and len(set(declared)) == len(declared)
+    assert sorted(listed) == sorted(declared), (sorted(set(declared) - set(listed)), sorted(set(listed) - set(declared)), [n for n in set(listed) if listed.count(n) > 1])
+
+
 def test_product_kernels_have_no_spill_in_front_of_an_exec_restore():
     r = subprocess.run(["make", "-j8", "check-spills"], cwd=os.path.join(ROOT, "gsalign_amd", "csrc"), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and r.stdout.strip().endswith("clean"), (r.stdout[-3000:], r.stderr[-2000:])

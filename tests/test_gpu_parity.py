@@ -396,6 +396,38 @@ def test_striped_dp_fallback_path(oracle_built, tmp_path, monkeypatch):
     o.close(); g.close()
 
 
+def _runs_to_the_end(g):
+    """how often gsa_run_to(8) ran on this context since the last gsa_set_profiling"""
+    ms = (capi.C.c_double * 10)(); n = capi.C.c_int64()
+    assert g.lib.gsa_get_wall_sums(g.ctx, ms, capi.C.byref(n)) == 0
+    return n.value
+
+
+def test_contig_retry_after_handoff_timeout(oracle_built, tmp_path):
+    """gsa_align_contig / gsa_align_contig_device repeat the contig with one DP job per launch after a stripe hand-off time-out
+    (forced once by the test hook dp_fake_timeout): the retry's answer is the plain one byte for byte, and gsa_run_to(8) ran twice.
+    The device-resident contig has no query slot (q_cur = -1): gsa_rewind accepts it all the same."""
+    from result_compare import same_result as _same_result
+    refs, qrys = synth.make_pair_fast(600000, 1, 0.002, seed=57)
+    q = qrys[0][1]
+    idx = _build(tmp_path, refs)
+    o = oracle_built.Oracle(idx); o.set_query(q); o.run_to(8); want = o.blocks(with_aln=True); o.close()
+    g = capi.Aligner(idx)
+    plain = g.align_contig(q)
+    d = g.device_copy(q)
+    for what, align in (("host", lambda: g.align_contig(q)), ("device", lambda: g.align_contig_device(d))):
+        g.set_option("dp_fake_timeout", 1); g.set_profiling(False)
+        got = align()                                                    # first pass reports the (fake) time-out, the retry answers
+        _same_result(got, plain, f"{what}: retry")
+        dump = capi.result_as_dump(got, with_aln=True)
+        for key, val in want.items():
+            assert np.array_equal(dump[key], val), (what, key)
+        assert _runs_to_the_end(g) == 2, what
+        _same_result(align(), plain, f"{what}: hook used up")            # the plain path: one more run
+        assert _runs_to_the_end(g) == 3, what
+    g.close()
+
+
 def test_align_many_contexts(oracle_built, tmp_path):
     """gsa_align_many: contigs handed to three contexts by the library's own worker threads; every result vs the oracle."""
     refs, qrys = synth.make_pair_fast(3000000, 6, 0.02, seed=58)
