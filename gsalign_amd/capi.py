@@ -24,6 +24,7 @@ EXPORTS = [
     "gsa_call_variants", "gsa_align_many_variants", "gsa_get_variant_timing",
     "gsa_block_cigars", "gsa_get_cigar_timing", "gsa_align_many_ex",
     "gsa_block_cs", "gsa_get_cs_timing", "gsa_extras_cs",
+    "gsa_lift_set", "gsa_lift", "gsa_get_lift_timing", "gsa_extras_lift",
     "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
     "gsa_create_from_pac", "gsa_export_index_table",
 ]
@@ -126,10 +127,26 @@ class Cs(C.Structure):
     _fields_ = [("n_blocks", C.c_int32), ("n_bytes", C.c_int64), ("blk", C.POINTER(CsBlock)), ("cs", C.POINTER(C.c_char))]
 
 
+class LiftHit(C.Structure):
+    """gsa_lift_hit, 16 bytes (include/gsa_hip.h): where input position idx lies on the query contig."""
+    _fields_ = [("idx", C.c_int32), ("qpos", C.c_int32), ("block", C.c_int32), ("cls", C.c_uint8), ("rev", C.c_uint8), ("n_cover", C.c_uint16)]
+
+
+class Lifts(C.Structure):
+    _fields_ = [("n_hits", C.c_int64), ("hits", C.POINTER(LiftHit))]
+
+
+LIFT_HIT_DT = np.dtype([("idx", "<i4"), ("qpos", "<i4"), ("block", "<i4"), ("cls", "u1"), ("rev", "u1"), ("n_cover", "<u2")])
 BLOCK_CS_DT = np.dtype([("cs_off", "<i8"), ("n_cs", "<i4"), ("_pad", "<i4")])
 BLOCK_CIGAR_DT = np.dtype([("cig_off", "<i8"), ("n_cig", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"), ("_pad", "<i4")])
 CIGAR_LETTERS = "MIDNSHP=X"      # by BAM op code; the library writes I (1), D (2), = (7) and X (8)
-WANT_VARIANTS, WANT_CIGARS, WANT_CS = 1, 2, 4
+WANT_VARIANTS, WANT_CIGARS, WANT_CS, WANT_LIFT = 1, 2, 4, 16
+
+
+def lifts_array(l: "Lifts"):
+    """gsa_lifts -> LIFT_HIT_DT array (a copy)."""
+    n = int(l.n_hits)
+    return np.ctypeslib.as_array(C.cast(l.hits, C.POINTER(C.c_uint8)), shape=(n * LIFT_HIT_DT.itemsize,)).view(LIFT_HIT_DT).copy() if n else np.zeros(0, LIFT_HIT_DT)
 
 
 def cigars_arrays(cig: "Cigars"):
@@ -307,7 +324,7 @@ class DeviceContig:
             self.lib.gsa_device_free(self.device, C.c_void_p(self.ptr)); self.ptr = None
 
 
-def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False) -> None:
+def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False) -> None:
     """gsa_align_many: `contigs` (uint8 arrays, or DeviceContig objects -- all of one kind) on the given contexts, one host
     thread per context inside the library.  on_result(contig_index, Result) runs on the worker threads (the Result is valid
     during the call only).  in_order: hand the contigs out as listed (GSA_MANY_IN_ORDER) instead of longest first.
@@ -318,7 +335,9 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     (variants_array copies them out).
     cigars=True: gsa_align_many_ex with GSA_WANT_CIGARS (and GSA_WANT_VARIANTS when variants=True) -- on_result(contig_index, Result, Variants or None, Cigars)
     (cigars_arrays copies them out).
-    cs=True: GSA_WANT_CS as well (it implies the CIGARs) -- on_result gets a fifth argument, the contig's Cs (gsa_extras_cs; cs_arrays copies it out)."""
+    cs=True: GSA_WANT_CS as well (it implies the CIGARs) -- on_result gets a fifth argument, the contig's Cs (gsa_extras_cs; cs_arrays copies it out).
+    lift=True: gsa_align_many_ex with GSA_WANT_LIFT (every aligner holds positions: lift_set) -- on_result(contig_index, Result, Variants or None, Cigars or None[, Cs]) gets
+    one more argument, the contig's Lifts (gsa_extras_lift; lifts_array copies it out)."""
     lib = aligners[0].lib
     n = len(contigs)
     ctxs = (C.c_void_p * len(aligners))(*[a.ctx for a in aligners])
@@ -326,8 +345,9 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     qs = (C.c_char_p * n)(*[C.cast(c.ptr if on_dev else c.ctypes.data, C.c_char_p) for c in contigs])
     ql = (C.c_int32 * n)(*[int(c.size) for c in contigs])
     flags = (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16)
-    if cigars or cs:
+    if cigars or cs or lift:
         lib.gsa_extras_cs.argtypes = [C.POINTER(Extras), C.POINTER(Cs)]
+        lib.gsa_extras_lift.argtypes = [C.POINTER(Extras), C.POINTER(Lifts)]
 
         def ex_cb(user, ci, res, ex):
             e = ex.contents
@@ -338,10 +358,16 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
                 if rc_cs != 0:
                     return int(rc_cs)
                 args += (s,)
+            if lift:
+                lf = Lifts()
+                rc_l = lib.gsa_extras_lift(ex, C.byref(lf))
+                if rc_l != 0:
+                    return int(rc_l)
+                args += (lf,)
             return int((on_result(*args) if on_result else 0) or 0)
         cbx = RESULT_EX_FN(ex_cb)
         lib.gsa_align_many_ex.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.c_uint32, RESULT_EX_FN, C.c_void_p]
-        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, WANT_CIGARS | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0), cbx, None)
+        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0), cbx, None)
     elif variants:
         cbv = RESULT_VAR_FN(lambda user, ci, res, var: int((on_result(ci, res.contents, var.contents) if on_result else 0) or 0))
         lib.gsa_align_many_variants.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_VAR_FN, C.c_void_p]
@@ -352,7 +378,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
         rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, flags, cb, None)
     if rc != 0:
         msgs = [lib.gsa_last_error(a.ctx).decode() for a in aligners]
-        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
+        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
 
 
 def _p(a, t):
@@ -638,6 +664,26 @@ class Aligner:
         self.lib.gsa_block_cs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Cs)]
         self._ck(self.lib.gsa_block_cs(self.ctx, C.c_int32(k), C.byref(cs)))
         return cs_arrays(cs)
+
+    def lift_set(self, pos) -> None:
+        """gsa_lift_set: the reference positions (0-based forward global coordinates) this context lifts from now on; an empty list clears them."""
+        pos = np.ascontiguousarray(pos, dtype=np.int64)
+        self.lib.gsa_lift_set.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        self._ck(self.lib.gsa_lift_set(self.ctx, C.c_void_p(pos.ctypes.data) if pos.size else None, C.c_int64(pos.size)))
+
+    def lift(self, k: int = 0):
+        """gsa_lift on the stage-8 result this context holds (contig k of a bundle): LIFT_HIT_DT array, ascending in idx."""
+        l = Lifts()
+        self.lib.gsa_lift.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Lifts)]
+        self._ck(self.lib.gsa_lift(self.ctx, C.c_int32(k), C.byref(l)))
+        return lifts_array(l)
+
+    def lift_timing(self):
+        """(host wall ms inside gsa_lift on this context since it was created, number of calls)."""
+        ms, n = C.c_double(0), C.c_int64(0)
+        self.lib.gsa_get_lift_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        self._ck(self.lib.gsa_get_lift_timing(self.ctx, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     def cs_timing(self):
         """(host wall ms inside gsa_block_cs on this context since it was created, its CIGAR pass included; number of calls)."""

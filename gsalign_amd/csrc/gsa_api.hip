@@ -35,14 +35,16 @@ static int rewind_to_hits(gsa_ctx *c)
 	return stage1_restore_pdbm(c);
 }
 
-// What the three passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip) ask of the context before they run; `who`: the export, for the messages
-static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who)
+// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip) ask of the context before they run; `who`: the export, for the messages;
+// need_positions: the pass reads the positions of gsa_lift_set
+static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false)
 {
 	const std::string w(who);
 	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, w + ": the context holds no finished (stage 8) result");
 	// (the pass reads the contig's bases on the device: a prefetch into the slot that held them leaves another contig there)
 	if (c->q_cur == -2) return gsa_fail(c, GSA_ERR_STATE, w + ": the contig's device copy was overwritten by a prefetch");
 	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, w + ": contig index out of range");
+	if (need_positions && c->lift_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no positions (gsa_lift_set first)");
 	GSA_CHECK(c, hipSetDevice(c->device));
 	return GSA_OK;
 }
@@ -64,6 +66,19 @@ int cs_call(gsa_ctx *c, int32_t k, gsa_cs *out, gsa_cigars *cig)
 	const auto t0 = std::chrono::steady_clock::now();
 	rc = block_cs(c, k, out, cig);
 	c->cs_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->cs_calls++;
+	return rc;
+}
+
+// the positions of gsa_lift_set through the stage-8 result the context holds: k_lift.hip
+int lift_call(gsa_ctx *c, int32_t k, gsa_lifts *out)
+{
+	if (!c || !out) return GSA_ERR_ARG;
+	out->n_hits = 0; out->hits = nullptr;
+	int rc = result_pass_ready(c, k, "gsa_lift", true);
+	if (rc) return rc;
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = lift_positions(c, k, out);
+	c->lift_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->lift_calls++;
 	return rc;
 }
 
@@ -249,6 +264,25 @@ int gsa_get_cigar_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return 
 
 int gsa_block_cs(gsa_ctx *c, int32_t k, gsa_cs *out) { return cs_call(c, k, out, nullptr); }
 int gsa_get_cs_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::cs_ms_sum, &gsa_ctx::cs_calls, ms_sum, n_calls); }
+
+int gsa_lift_set(gsa_ctx *c, const int64_t *pos, int64_t n)
+{
+	if (!c || n < 0 || (n > 0 && !pos)) return GSA_ERR_ARG;
+	if (n >= (1ll << 31) - 256) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_lift_set: too many positions");
+	for (int64_t i = 0; i < n; i++) if (pos[i] < 0 || pos[i] >= c->G)
+		return gsa_fail(c, GSA_ERR_ARG, "gsa_lift_set: position " + std::to_string((long long)pos[i]) + " (entry " + std::to_string((long long)i) + ") lies outside the reference [0, " + std::to_string((long long)c->G) + ")");
+	if (n == 0) { c->lift_n = 0; return GSA_OK; }
+	GSA_CHECK(c, hipSetDevice(c->device));
+	// (the API is synchronous: no pass of this context reads the old positions any more)
+	c->lift_n = 0;      // (a failed allocation or copy leaves the context without positions, never with half of them)
+	ENS(i64, d_lpos, (size_t)n);
+	const hipError_t e = hipMemcpy(c->d_lpos.p, pos, (size_t)n * sizeof(i64), hipMemcpyHostToDevice);
+	if (e != hipSuccess) { return gsa_fail(c, GSA_ERR_HIP, std::string("gsa_lift_set (hipMemcpy H2D): ") + hipGetErrorString(e)); }
+	c->lift_n = n;
+	return GSA_OK;
+}
+int gsa_lift(gsa_ctx *c, int32_t k, gsa_lifts *out) { return lift_call(c, k, out); }
+int gsa_get_lift_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::lift_ms_sum, &gsa_ctx::lift_calls, ms_sum, n_calls); }
 
 int gsa_get_wall_sums(gsa_ctx *c, double ms[10], int64_t *n)
 {

@@ -94,6 +94,7 @@ template struct RawArr<gsa_variant>;
 template struct RawArr<gsa_block_cigar>;
 template struct RawArr<gsa_cs_block>;
 template struct RawArr<uint32_t>;
+template struct RawArr<gsa_lift_hit>;
 void ContigResult::assign(const gsa_result &r, bool summary_mode)
 {
 	summary = summary_mode;
@@ -507,6 +508,108 @@ void Emitter::paf_text(const QueryContig &q, ContigResult &r, const gsa_block_ci
 void Emitter::paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const gsa_cs_block *csb, const char *cs) const
 {
 	paf_text(q, r, blk, ops, [&](OutBuf &&o) { if (o.n) fwrite(o.p, 1, o.n, fp); }, csb, cs);
+}
+
+// ---- lifted reference positions ----------------------------------------------------------------------------------------------------------
+void gsah_lift(const HostIndex &ix, const ContigResult &r, const int64_t *pos, int64_t n, std::vector<gsa_lift_hit> &hits)
+{
+	hits.clear();
+	if (r.summary || n <= 0) return;      // (a summary result holds neither records nor strings)
+	// the blocks with records in the order of their first text position, the running maximum of their trimmed ends beside them
+	struct Blk { int64_t start, end, maxend; int32_t block; };
+	std::vector<Blk> tab;
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		if (b.n_frag <= 0) continue;
+		const gsa_frag first = r.frag(b.frag_off), last = r.frag(b.frag_off + b.n_frag - 1);
+		Blk v; v.start = first.rpos; v.end = last.rpos + last.rlen - extension(ix, b, last); v.maxend = 0; v.block = (int32_t)bi;
+		if (v.end > v.start) tab.push_back(v);
+	}
+	if (tab.empty()) return;
+	std::sort(tab.begin(), tab.end(), [](const Blk &x, const Blk &y) { return x.start != y.start ? x.start < y.start : x.block < y.block; });
+	for (size_t j = 0; j < tab.size(); j++) tab[j].maxend = j ? std::max(tab[j - 1].maxend, tab[j].end) : tab[j].end;
+	auto better = [&](int32_t x, int32_t y) {
+		const gsa_block &a = r.blocks[(size_t)x], &b = r.blocks[(size_t)y];
+		if ((a.bdup != 0) != (b.bdup != 0)) return a.bdup == 0;
+		if (a.score != b.score) return a.score > b.score;
+		return x < y;
+	};
+	auto cover = [&](int64_t t, int32_t &best, uint32_t &cnt) {
+		size_t j = (size_t)(std::upper_bound(tab.begin(), tab.end(), t, [](int64_t v, const Blk &b) { return v < b.start; }) - tab.begin());
+		while (j > 0 && tab[j - 1].maxend > t) {
+			j--;
+			if (tab[j].end <= t) continue;
+			cnt++;
+			if (best < 0 || better(tab[j].block, best)) best = tab[j].block;
+		}
+	};
+	std::vector<gsa_lift_hit> all((size_t)n);      // cls = 0: no block covers the position
+	auto one = [&](size_t ib, size_t ie) {
+		for (size_t i = ib; i < ie; i++) {
+			gsa_lift_hit &h = all[i];
+			memset(&h, 0, sizeof(h));
+			const int64_t p = pos[i];
+			if (p < 0 || p >= ix.G) continue;
+			int32_t best = -1; uint32_t cnt = 0;
+			cover(p, best, cnt); cover(2 * ix.G - 1 - p, best, cnt);
+			if (best < 0) continue;
+			const gsa_block &b = r.blocks[(size_t)best];
+			const int64_t t = b.bdir ? p : 2 * ix.G - 1 - p;
+			int64_t lo = b.frag_off, hi = b.frag_off + b.n_frag;      // the last record that starts at or before t
+			while (hi - lo > 1) { const int64_t m = (lo + hi) >> 1; if (r.frag(m).rpos <= t) lo = m; else hi = m; }
+			const gsa_frag f = r.frag(lo);
+			const int64_t d = t - f.rpos;
+			h.idx = (int32_t)i; h.block = best; h.rev = b.bdir ? 0 : 1; h.n_cover = (uint16_t)(cnt > 65535u ? 65535u : cnt);
+			if (f.bseed) { h.cls = (uint8_t)GSA_CIGAR_EQ; h.qpos = f.qpos + (int32_t)d; continue; }
+			const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+			int64_t rp = f.rpos; int32_t qp = f.qpos;
+			h.qpos = -1;
+			for (int c = 0; c < f.aln_len; c++) {
+				if (x1[c] != '-' && rp == t) {
+					if (x2[c] == '-') { h.cls = (uint8_t)GSA_CIGAR_DEL; h.qpos = qp - 1; }
+					else { h.cls = (uint8_t)column_class(x1[c], x2[c]); h.qpos = qp; }
+					break;
+				}
+				if (x1[c] != '-') rp++;
+				if (x2[c] != '-') qp++;
+			}
+		}
+	};
+	if ((size_t)n * sizeof(gsa_lift_hit) >= par_min_bytes()) par_ranges((size_t)n, (size_t)1 << 14, one); else one(0, (size_t)n);
+	for (size_t i = 0; i < (size_t)n; i++) if (all[i].cls) hits.push_back(all[i]);
+}
+
+// <prefix>.lift.tsv: one line per hit -- reference name, 1-based position, query name, 1-based query position, strand, class letter, the block's score as the MAF
+// prints it (trimmed; 1 for a duplicate), n_cover.  ref_chr / ref_pos: sequence and 1-based position of every input position (hit::idx indexes them)
+void Emitter::lift_text(bool first, const QueryContig &q, const ContigResult &r, const gsa_lift_hit *hits, int64_t n_hits, const int32_t *ref_chr, const int32_t *ref_pos,
+                        const std::function<void(OutBuf &&)> &sink) const
+{
+	OutBuf o;
+	if (first) o.append("#ref\tpos\tquery\tqpos\tstrand\tclass\tscore\tn_cover\n");
+	std::vector<int> score(r.blocks.size(), 0);
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		score[bi] = b.bdup ? 1 : b.score;
+		if (!b.bdup && b.n_frag > 0 && !r.summary) score[bi] -= extension(*idx, b, r.frag(b.frag_off + b.n_frag - 1));
+	}
+	for (int64_t i = 0; i < n_hits; i++) {
+		const gsa_lift_hit &h = hits[i];
+		if (h.block < 0 || (size_t)h.block >= r.blocks.size()) continue;
+		const std::string &rname = idx->chr_name[(size_t)ref_chr[h.idx]];
+		o.reserve(o.n + rname.size() + q.name.size() + 96);
+		char *w = o.p + o.n;
+		memcpy(w, rname.data(), rname.size()); w += rname.size(); *w++ = '\t';
+		w = put_int(w, ref_pos[h.idx]); *w++ = '\t';
+		memcpy(w, q.name.data(), q.name.size()); w += q.name.size(); *w++ = '\t';
+		w = put_int(w, (long long)h.qpos + 1); *w++ = '\t';
+		*w++ = h.rev ? '-' : '+'; *w++ = '\t';
+		*w++ = h.cls == GSA_CIGAR_EQ ? '=' : (h.cls == GSA_CIGAR_X ? 'X' : 'D'); *w++ = '\t';
+		w = put_int(w, score[(size_t)h.block]); *w++ = '\t';
+		w = put_int(w, h.n_cover); *w++ = '\n';
+		o.n = (size_t)(w - o.p);
+		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
+	}
+	if (o.n) sink(std::move(o));
 }
 
 void Emitter::aln(FILE *fp, const QueryContig &q, ContigResult &r) const

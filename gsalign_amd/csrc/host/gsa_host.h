@@ -115,6 +115,11 @@ void gsah_block_cs(const ContigResult &r, std::vector<gsa_cs_block> &blk, std::s
 // tail of a forward block's string, the head of a reverse-strand block's -- and a cut ":n" is printed again.  out = the cs of the trimmed ops.
 void gsah_cs_trim(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, int bdir, int64_t ext, std::string &out);
 
+// The positions pos[0 .. n) (0-based forward global reference coordinates) lifted through a finished contig, by the contract of gsa_lift (gsa_hip.h): coverage trimmed by
+// iExtension, the choice among covering blocks, the class and query position of the chosen column -- from the records and the two gapped strings.  The comparator of
+// gsa_lift, and the lift of a host that holds a gsa_result and no GPU context.  hits: ascending in idx, positions no block covers (or outside [0, G)) absent.
+void gsah_lift(const HostIndex &ix, const ContigResult &r, const int64_t *pos, int64_t n, std::vector<gsa_lift_hit> &hits);
+
 struct OutBuf;                             // par.h
 
 struct Emitter {
@@ -136,6 +141,11 @@ struct Emitter {
 	void paf_text(const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const std::function<void(OutBuf &&)> &sink,
 	              const gsa_cs_block *csb = nullptr, const char *cs = nullptr) const;
 	void paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_block_cigar *blk, const uint32_t *ops, const gsa_cs_block *csb = nullptr, const char *cs = nullptr) const;
+	// <prefix>.lift.tsv (-lift): one line per hit of gsa_lift / gsah_lift, in the order given -- reference name, 1-based position, query name, 1-based query position, + / -,
+	// class letter (= X D), the block's score as the MAF prints it (1 for a duplicate), n_cover; first: the header line in front.  ref_chr / ref_pos: reference sequence
+	// and 1-based position of every input position (gsa_lift_hit::idx indexes them)
+	void lift_text(bool first, const QueryContig &q, const ContigResult &r, const gsa_lift_hit *hits, int64_t n_hits, const int32_t *ref_chr, const int32_t *ref_pos,
+	               const std::function<void(OutBuf &&)> &sink) const;
 	// OutputAlignment (tools.cpp:222-286)
 	void aln(FILE *fp, const QueryContig &q, ContigResult &r) const;
 	// OutputDotplot (DotPloting.cpp:10-71): gnuplot script `gp_path` + one data file per plotted reference sequence

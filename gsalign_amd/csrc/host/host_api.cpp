@@ -270,6 +270,26 @@ long long gsah_c_cs_trim(const char *cs, long long n, const uint32_t *ops, long 
 	return (long long)o.size();
 }
 
+// gsah_lift through the C API: pos[n] lifted through one finished contig, on the host -- what gsa_lift gives.  out[cap]; returns the number of hits (call with cap = 0 to
+// size `out`), < 0 on error.  The index of the last prefix stays loaded, behind a lock, as in gsah_c_variants (only its sequence table is read).
+long long gsah_c_lift(const char *index_prefix, const gsa_result *res, const int64_t *pos, long long n, gsa_lift_hit *out, long long cap)
+{
+	static std::mutex mu; static std::string have; static HostIndex *idx = nullptr;
+	std::lock_guard<std::mutex> lock(mu);
+	if (!index_prefix || !res || n < 0 || (n > 0 && !pos) || (cap > 0 && !out)) return -1;
+	if (!idx || have != index_prefix) {
+		delete idx; idx = new HostIndex; have.clear(); std::string e;
+		if (!gsah_load_index(index_prefix, *idx, e)) { delete idx; idx = nullptr; return -2; }
+		have = index_prefix;
+	}
+	ContigResult cr; cr.assign(*res);
+	std::vector<gsa_lift_hit> h;
+	gsah_lift(*idx, cr, pos, n, h);
+	const size_t m = std::min<size_t>(h.size(), cap > 0 ? (size_t)cap : 0);
+	if (m) memcpy(out, h.data(), m * sizeof(gsa_lift_hit));
+	return (long long)h.size();
+}
+
 // OutputDotplot for one contig: script + data files (no gnuplot run).  Returns 1 if something was written.
 // The reference plots AFTER OutputMAF (GSAlign.cpp:543-546), which shortens the last record of a block that runs over the end of
 // its reference sequence (tools.cpp:149-220), and the plot shows the shortened block: the MAF emitter runs first here too.

@@ -262,6 +262,25 @@ def cs(index_prefix, seq, result):
     return blk, by
 
 
+def lift(index_prefix, seq, result, positions):
+    """gsah_c_lift: the reference positions (0-based forward global coordinates) lifted through one finished contig on the host, from the records and the gapped
+    strings -- what Aligner.lift computes on the GPU, by the contract of gsa_lift (include/gsa_hip.h).  result: a capi.Result, a dump dict (oracle layout) or a result
+    dict of capi.Aligner.  The index under index_prefix supplies the reference sequences' lengths (the trim); seq is not needed by the walk and may be None.
+    Returns a LIFT_HIT_DT array, ascending in idx; positions no block covers are absent."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    pos = np.ascontiguousarray(positions, dtype=np.int64)
+    lib = load()
+    lib.gsah_c_lift.restype = C.c_longlong
+    lib.gsah_c_lift.argtypes = [C.c_char_p, C.POINTER(capi.Result), C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
+    H = np.zeros(int(pos.size), capi.LIFT_HIT_DT)
+    n = lib.gsah_c_lift(index_prefix.encode(), C.byref(result), C.c_void_p(pos.ctypes.data), int(pos.size), C.c_void_p(H.ctypes.data), int(H.size))
+    if n < 0:
+        raise RuntimeError(f"gsah_c_lift -> {n}")
+    return H[:int(n)].copy()
+
+
 def cs_trim(cs_bytes, ops, bdir: bool, ext: int) -> bytes:
     """gsah_c_cs_trim: iExtension's trim on ONE block's cs string (of its untrimmed ops, output order) -- the last `ext` columns in walk order go, a cut ':n' is
     printed again.  Returns the string that stays: the cs of the trimmed ops."""

@@ -402,17 +402,49 @@ int gsa_block_cs(gsa_ctx *ctx, int32_t k, gsa_cs *out);
  * the number of calls.  Always on. */
 int gsa_get_cs_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 
+/* ---- lifting reference positions through the alignment ------------------------
+ * Where does a position of the reference lie on the query contig?  A reference position is a 0-based FORWARD global coordinate p in [0, G): the offset in
+ * the concatenation of the reference sequences.  It is text position p for forward-strand blocks and 2G - 1 - p for reverse-strand blocks (the mapping
+ * of GenCoordinateInfo, tools.cpp:120-140).
+ *   coverage  a block covers text position t when first.rpos <= t < end, end = last.rpos + last.rlen CLAMPED to the end of the block's chromosome copy: unlike the
+ *             CIGAR and cs answers this one is TRIMMED (the iExtension rule, tools.cpp:192-202) -- an untrimmed overrun would claim positions of the neighbouring sequence
+ *   choice    among the blocks that cover either text position of p: bdup == 0 before bdup != 0, then the greater gsa_block::score, then the smaller block index;
+ *             n_cover counts ALL covering blocks, duplicates included, and saturates at 65535
+ *   class     of the chosen block's column that holds the reference base, with the CIGAR's codes and the CIGAR's rule:
+ *             GSA_CIGAR_EQ / GSA_CIGAR_X  the base faces a query base: qpos = that base's 0-based position in the contig as stored (forward, whatever the strand)
+ *             GSA_CIGAR_DEL               the base faces '-': qpos = the query base consumed last in front of the column in walk order (it always exists: a gap follows a seed)
+ * The columns are the ones the CIGAR pass reads: a seed record is '=' over its whole length, an equal-length gap that needed no DP is classified by comparing the
+ * two bases, a DP gap is read from the op string of its DP job.  One hit per position that some block covers, ascending in idx; positions no block covers are absent. */
+typedef struct { int32_t idx;      /* index into the positions given to gsa_lift_set */
+                 int32_t qpos; int32_t block;   /* block: index among contig k's blocks (gsa_result::blocks) */
+                 uint8_t cls, rev; uint16_t n_cover; } gsa_lift_hit;          /* 16 bytes; rev = 1: the chosen block lies on the reverse strand */
+typedef struct { int64_t n_hits; const gsa_lift_hit *hits; } gsa_lifts;
+/* The positions to lift: n of them are copied to the context's device and stay until the next gsa_lift_set or gsa_destroy; n = 0 clears them.  A clone starts
+ * without positions.  A position outside [0, G): GSA_ERR_ARG with the first offender in gsa_last_error, nothing changed.  n >= 2^31 - 256: GSA_ERR_LIMIT.
+ * Device memory: about 8 (the position) + 16 (its hit) + 8 (its chosen block and n_cover between the two launches) bytes per position. */
+int gsa_lift_set(gsa_ctx *ctx, const int64_t *pos, int64_t n);
+/* The positions of gsa_lift_set lifted through the stage-8 result the context holds.  Validity, call order, k and the error codes are those of gsa_block_cigars;
+ * without positions GSA_ERR_STATE.  No blocks or no hits: n_hits = 0.  In a bundle qpos is relative to contig k, i.e. what the single-contig call on query[k]
+ * gives.  The answer lives in buffers of its own: a later gsa_block_cigars, gsa_block_cs or gsa_call_variants returns what it returned before, and so does
+ * this call after one of them.  Memory is owned by the context and valid until the next call on it; the hits come home in one copy into pinned memory. */
+int gsa_lift(gsa_ctx *ctx, int32_t k, gsa_lifts *out);
+/* measurement: host wall time the calling threads spent inside gsa_lift on this context since it was created, and the number of calls.  Always on. */
+int gsa_get_lift_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+
 /* gsa_align_many with optional passes run by the worker in front of the callback -- before the prefetch after next can touch the contig's
- * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs).  *ex and what it points to are valid during
- * the callback only, like *res. */
+ * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift).  *ex and what it
+ * points to are valid during the callback only, like *res. */
 #define GSA_WANT_VARIANTS 1u
 #define GSA_WANT_CIGARS   2u
 #define GSA_WANT_CS       4u   /* gsa_block_cs; implies GSA_WANT_CIGARS */
+#define GSA_WANT_LIFT     16u  /* gsa_lift of every contig; every context of ctx[] must hold positions (gsa_lift_set), else GSA_ERR_STATE before any contig is aligned */
 typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;   /* NULL where not asked for */
 /* The contig's cs strings inside the callback of gsa_align_many_ex: the library hands the callback a LARGER object whose head is the gsa_extras
  * (which keeps its two members and its 16 bytes), and this call reaches what lies behind it -- so it is valid for the `ex` the library passed
  * only, never for a gsa_extras the caller made.  GSA_ERR_STATE when GSA_WANT_CS was not asked for.  *out is valid during the callback only. */
 int gsa_extras_cs(const gsa_extras *ex, gsa_cs *out);
+/* The contig's lifted positions inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_LIFT was not asked for). */
+int gsa_extras_lift(const gsa_extras *ex, gsa_lifts *out);
 typedef int (*gsa_result_ex_fn)(void *user, int32_t contig, const gsa_result *res, const gsa_extras *ex);
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
                       uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user);
