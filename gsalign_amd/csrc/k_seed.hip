@@ -15,12 +15,13 @@
 #define SEED_WG 64              // lanes per chunk: ONE WAVE, and the kernel says so (threadIdx.x & 63, >> 6).  (128 lanes = two waves per chunk spent 27 % more VALU
                                 // wave-instructions on the same searches -- a wave iterates as long as its slowest lane: profiles/archive/r03_seed_shape_sweep.txt)
 #ifndef NSUB
-#define NSUB 96                // speculative sub-ranges per chunk (work items of the wave, drawn from an LDS queue: 64 lanes take the first 64, a lane
-                               // that is through early takes one of the other 32).  Swept 64 .. 512 on the bench: with 64-base text windows and four
-                               // presence bits per round trip fewer, longer walks win -- 384 was best before them, 128 with two waves per chunk)
+#define NSUB 64                // sub-ranges per chunk (work items of the wave, drawn from an LDS queue): ONE per lane.  A sub-range is only where a walk STARTS -- walks
+                               // cross sub-range ends until they meet memoised or claimed ground -- so every further one is one more speculative search (96 -> 64: a sixth
+                               // fewer requests per chunk), and the kernel is bound by its requests.  Swept 48 .. 96 on the bench: 64 wins by 4 % (profiles/seed_claims_ab.txt;
+                               // while walks stopped at sub-range ends 96 was best, and 64 is within 1 % of it there)
 #endif
 #ifndef ADV_STEPS
-#define ADV_STEPS 4             // advance steps (hops over memoised / ambiguous positions, opening a search) per round trip
+#define ADV_STEPS 4             // advance steps (taking an item, steps over ambiguous positions, opening a search) per round trip
 #endif
 #ifndef PLOOK
 #define PLOOK 3                 // presence bits looked up beside the one of the current start
@@ -33,22 +34,29 @@
 // sequential -- but "next start" is a pure function of the start position, i.e.
 // the chunk is a functional graph whose paths merge (two walks that are inside
 // the same exact match end at the same mismatch).  One WAVE owns a chunk and
-// cuts it into NSUB sub-ranges.  Round 1: lanes pull sub-ranges from an
-// LDS queue and walk each one speculatively from its left edge, memoising next(s)
-// per position.  Later rounds: a sub-range whose true entry (= the previous
-// sub-range's exit) differs from where it was entered is re-walked along the memo
-// (new searches only until it merges) until no exit moves.  The result is exactly
-// the reference's chain; the on-path bit per position selects which memoised
-// matches become seeds.  Query (2-bit packed + N bitmap), memo and exits live in
-// LDS; so do the on-path bits, in the query's words once the walks are over.
+// cuts it into NSUB sub-ranges.  The pass: lanes pull sub-ranges from an
+// LDS queue and walk from each one's left edge, memoising next(s) per position.
+// A walk goes on ACROSS sub-range ends until the start it arrives at is memoised,
+// CLAIMED by a search in flight (a bit per start, set when the search is opened)
+// or behind the chunk's end; then the lane takes the next sub-range.  Item 0
+// claims start 0, and whoever completes the search at a chain position claims the
+// next one or finds it claimed or memoised: when the pass is over the whole true
+// chain is memoised, and so is the memo path from every left edge.  The resolver
+// behind the pass reads LDS only: the exit of every sub-range along the memo,
+// the sub-ranges on the chain by pointer jumping, the exits of those from their
+// true entries, until no exit moves.  (A start it meets unsearched -- the claims
+// say that there is none -- gets a fallback pass of the loop.)  The result is
+// exactly the reference's chain; the on-path bit per position selects which
+// memoised matches become seeds.  Query (2-bit packed + N bitmap), memo, claims and
+// exits live in LDS; so do the on-path bits, in the query's words once the walks are over.
 // ---------------------------------------------------------------------------
 
 #ifndef SEED_MIN_WAVES
 #define SEED_MIN_WAVES 5        // waves per SIMD the register allocation must allow: 5 = 96 VGPRs (the loop wants ~150: some 40 live in ~200 bytes of scratch).  Round 6: what the
                                 // kernel leaves FREE on a CU is worth more than what the spills cost it -- see k_seed_wg.  (3 until round 6: 149 VGPRs, no scratch.)
 #endif
-// SEED_LDS_DIET = 1 (an experiment build, NOT the product: DESIGN.md section 8e): a chunk's LDS state cut from 11.5 KB to 8.4 KB -- 512 long-hop entries, and
-// only a chunk with an ambiguous base keeps an N bitmap, in the place of half of them -- so that twelve waves fit the LDS that eight take.
+// SEED_LDS_DIET = 1 (an experiment build, NOT the product: DESIGN.md section 8e): a chunk's LDS state cut from 12.0 KB to 9.0 KB -- 512 long-hop entries, and
+// only a chunk with an ambiguous base keeps an N bitmap, in the place of half of them -- so that eleven waves fit the LDS that eight take.
 #ifndef SEED_LDS_DIET
 #define SEED_LDS_DIET 0
 #endif
@@ -86,6 +94,13 @@ __device__ __forceinline__ void memo_set(u32 *memo, u32 *lhop, u32 lmask, int s,
 	}
 	*(volatile int *)abort_flag = 1;                                // table full: the chunk is redone by the dense kernels
 }
+// The memo path from s to the first position at or behind `end` (LDS reads only); -1 where it meets a start nobody has searched, which `unk` then names.
+__device__ __forceinline__ int memo_trace(const u32 *memo, const u32 *lhop, u32 lmask, int s, int end, int &unk)
+{
+	while (s < end) { const int m = memo_get(memo, lhop, lmask, s); if (!m) { unk = s; return -1; } s += m; }
+	return s;
+}
+#define CLAIM_WORDS ((GSA_CHUNK + 31) / 32)
 
 // Everything a wave keeps in LDS for its chunk.  One object per WAVE: a workgroup of k_seed_wg is SEED_WPW independent waves, each with its own chunk, queue,
 // memo and resolver state; nothing in seed_chunk synchronises across waves.  (One chunk per wave, one search per lane: the other shapes that were
@@ -105,10 +120,13 @@ struct SeedLds {
 	// accepted matches plus one per speculative sub-range), so such a chunk's table runs full and may hand the chunk over: the slower, still exact road.
 	u32 lhop[LHOP_WORDS];
 	uint16_t mblk[COUNT ? GSA_CHUNK : 1];   // Occ blocks the search from s read (accounting build only)
-	uint16_t entry_of[NSUB], exit_of[NSUB];
-	uint16_t pend_it[SEED_WG];                          // items to walk for real in this pass
-	uint16_t jmp[2][NSUB], walked_from[NSUB];           // pointer-jumping buffers; entry of the last real walk of a re-walked sub-range
-	u32 rewalked[(NSUB + 31) / 32], onchain[(NSUB + 31) / 32], s_npend;
+	uint16_t entry_of[NSUB], exit_of[NSUB];             // the resolver's: true entry of an on-chain sub-range; where the memo path from its entry leaves it
+	uint16_t pend_s[SEED_WG];                           // starts the resolver met unsearched: a fallback pass of the loop begins there
+	uint16_t jmp[2][NSUB];                              // pointer-jumping buffers
+	// One bit per start: a search from it has been opened in this pass (atomicOr; the old value decides who searches).  A walk that arrives at a claimed start leaves
+	// it to its owner and takes other work, so no start is searched twice and no accepted match is entered twice.
+	u32 claim[CLAIM_WORDS];
+	u32 onchain[(NSUB + 31) / 32], s_npend;
 	int s_last;
 };
 // A wave's own synchronisation point.  One wave per workgroup: __syncthreads() as ever (the barrier itself is elided for a one-wave workgroup, the fences
@@ -130,7 +148,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 	// (the N words go into the zeroed hop table's tail, and only those that have a flag set: hence the table first)
 	for (int p = j; p < MEMO_WORDS; p += SEED_WG) L.memo[p] = 0;
 	for (int p = j; p < LHOP_WORDS; p += SEED_WG) L.lhop[p] = 0;
-	for (int it = j; it < nitems; it += SEED_WG) L.entry_of[it] = (uint16_t)(it * S);
+	for (int p = j; p < CLAIM_WORDS; p += SEED_WG) L.claim[p] = 0;
 	if (j == 0) { L.s_ncand = 0; L.s_hits = 0; }
 	SEED_SYNC();
 	bool anyn = false;
@@ -150,14 +168,13 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 	// (lhop_cap: a power of two, the entries a test lets the table use -- gsa_set_option "seed_lhop"; LHOP_N otherwise)
 	const u32 lmask = (SEED_LDS_DIET && hasn && lhop_cap > (u32)LHOP_NN ? (u32)LHOP_NN : lhop_cap) - 1u;
 	if (j == 0) { L.s_queue = 0; L.s_npend = 0; L.s_abort = 0; }
-	if (j < (NSUB + 31) / 32) L.rewalked[j] = 0;
 	u32 all_blocks = 0, rounds = 0, iters = 0;
 #ifdef SEED_STATS
-	u32 st_it = 0, st_fm_any = 0, st_fm_only = 0, st_act = 0, st_fm = 0;
+	u32 st_it = 0, st_pend = 0, st_late = 0, st_act = 0, st_fm = 0;
 #endif
 	unsigned long long t_begin = wall_clock64(), t_round0 = 0, t_resolve = 0;
-	u32 dirty = 0;                                      // rounds >= 2: this lane has one item (fb_item) to walk for real
-	int fb_item = 0;
+	u32 dirty = 0;                                      // a fallback pass: this lane has one start (fb_start) to walk from
+	int fb_start = 0;
 	SEED_SYNC();
 	for (;;) {
 		// One flat loop per wave.  Every iteration each lane has exactly ONE memory request pending
@@ -165,7 +182,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 		// lanes issue their requests together, wait once, then consume by mode -- so lanes that are in
 		// different searches, or in different phases of a search, never serialise on each other's
 		// memory latency.
-		int item = -1, s = 0, bend = 0, pos = 0, mode = M_ADV; u32 kid = 0, pid = 0, pext = 0;
+		int s = 0, pos = 0, mode = M_ADV; u32 kid = 0, pid = 0, pext = 0;
 		int lclen = 0;                                        // the chunk's length once the lane holds an item
 		FmIntv ik = {0, 0, 0}; u32 blk = 0; i64 tp = 0;
 		bool need_item = true;
@@ -178,7 +195,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 			if (*(volatile int *)&L.s_abort) break;
 #ifdef SEED_STATS      // (experiments: what the wave-iterations are spent on -- sums over all waves instead of the maxima / timers)
 			{ const u64 bf = __ballot(mode == M_FM), ba = __ballot(mode != M_DONE);
-			  st_it++; st_fm_any += bf != 0; st_fm_only += bf != 0 && bf == ba; st_act += __popcll(ba); st_fm += __popcll(bf); }
+			  st_it++; st_late += rounds != 0; st_act += __popcll(ba); st_fm += __popcll(bf); }
 #endif
 			// ---- request phase (convergent): every kind of request is issued by every lane; a lane that does not want it reads entry 0 ----
 			u64 kk = 0, ll = 0; bool kn = true, ln = true;
@@ -215,11 +232,11 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 				if (!PRES4_TEST(0)) {                  // the first MinSeedLength bases do not occur: no seed here, next start s+1
 					memo_one(L.memo, s); s += 1; mode = M_ADV;
 					// ... and the same for the starts behind it, as long as nothing else is known about them (the advance step
-					// below owns every other rule: sub-range end, memoised hop, ambiguous bases, too close to the chunk end)
+					// below owns every other rule: chunk end, memoised or claimed start, ambiguous bases, too close to the chunk end)
 					const int ML = prm.MinSeedLength < 32 ? prm.MinSeedLength : 32;
 #pragma unroll
 					for (int k2 = 0; k2 < PLOOK; k2++) {
-						if (s >= bend || memo_nib(L.memo, s)) break;
+						if (s >= lclen || memo_nib(L.memo, s)) break;
 						const u32 nb = q_nbits32(qn, s, hasn);
 						if (s + prm.MinSeedLength > lclen || (nb & (ML == 32 ? ~0u : (1u << ML) - 1)) != 0) break;
 						if (k2 == 0 ? PRES4_TEST(1) : k2 == 1 ? PRES4_TEST(2) : PRES4_TEST(3)) break;          // occurs: needs its table entry (next iteration)
@@ -258,26 +275,26 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 				all_blocks += blk;
 				s += d; mode = M_ADV;
 			}
-			// ---- advance: take an item / hop over a memoised or ambiguous position / open the next search
-			// (a few steps per iteration: hops over memoised / ambiguous positions cost no memory access) ----
+			// ---- advance: take an item / step over an ambiguous position / open the next search.  The walk of an item ends where its start is memoised
+			// (from there on the memo is the path: the resolver follows it without a memory request), claimed by a search in flight, or behind the chunk's
+			// end -- never because a sub-range ends.  No lane waits for a claim: it takes other work.  (A few steps per iteration: none of them costs a memory access) ----
 			for (int step = 0; step < ADV_STEPS && mode == M_ADV; step++) {
 				if (need_item) {
-					if (rounds == 0) { const u32 it_ = atomicAdd(&L.s_queue, 1u); item = it_ < (u32)nitems ? (int)it_ : -1; }
-					else if (dirty) { dirty = 0; item = fb_item; }
-					else item = -1;
+					if (rounds == 0) { const u32 it_ = atomicAdd(&L.s_queue, 1u); s = it_ < (u32)nitems ? (int)it_ * S : -1; }
+					else if (dirty) { dirty = 0; s = fb_start; }
+					else s = -1;
 					need_item = false;
-					if (item < 0) { mode = M_DONE; break; }
+					if (s < 0) { mode = M_DONE; break; }
 					lclen = clen;
-					s = L.entry_of[item]; bend = (item + 1) * S < lclen ? (item + 1) * S : lclen;
 				}
-				if (s >= bend) { L.exit_of[item] = (uint16_t)s; need_item = true; continue; }
-				const int m_ = memo_get(L.memo, L.lhop, lmask, s);
-				if (m_) { s += m_; continue; }
+				if (s >= lclen || memo_nib(L.memo, s)) { need_item = true; continue; }
 				const u32 nb = q_nbits32(qn, s, hasn);
 				const int ML = prm.MinSeedLength < 32 ? prm.MinSeedLength : 32;
 				if (nb & 1u) { memo_one(L.memo, s); if (COUNT) L.mblk[s] = 0; s += 1; }
 				else if (!COUNT && (s + prm.MinSeedLength > lclen || (nb & (ML == 32 ? ~0u : (1u << ML) - 1)) != 0)) { memo_one(L.memo, s); s += 1; }      // cannot reach MinSeedLength
 				else {
+					const u32 cbit = 1u << (s & 31);
+					if (atomicOr(&L.claim[s >> 5], cbit) & cbit) { need_item = true; continue; }      // someone else's search
 					pos = s + 1; blk = 0; mode = M_FM;
 					// (the interval of the first base -- fm_init: three 5-way selects of 64-bit numbers -- only where the walk really starts
 					//  at the first base: next to the chunk end / an N, or behind a k-mer entry that says "absent")
@@ -298,54 +315,69 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 		if (L.s_abort) break;
 		if (rounds == 1) t_round0 = wall_clock64() - t_begin;
 		const unsigned long long t_r0 = wall_clock64();
-		// True entries.  A walk that enters sub-range `it` on a memoised position leaves it at exit_of[it]
-		// wherever it entered (all walks inside a sub-range merge), so at sub-range level the true chain is
-		// the orbit of 0 under it -> exit_of[it] / S: found by pointer jumping (log2 NSUB parallel rounds in
-		// LDS), the true entry of an on-chain sub-range being its predecessor's exit.  In round 1 only
-		// `it`'s own walk wrote memo[] inside `it`, so an entry e with memo[e] != 0 lies on that walk.  An
-		// entry the speculation never visited (a random >= MinSeedLength match made the speculative walk
-		// jump over it) needs a real walk: such sub-ranges are collected, ASSUMED to keep their exit, walked
-		// in parallel (one lane each) in another pass of the loop above, and the chain is resolved again.
-		for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems) { const int X = L.exit_of[v]; L.jmp[0][v] = (uint16_t)(X >= clen ? 0xffff : X / S); }
-		if (j < (NSUB + 31) / 32) L.onchain[j] = 0;
+		// True entries, from LDS alone.  When the pass is over the memo path from every left edge is complete, so a lane per sub-range follows it to the first
+		// position at or behind the sub-range's end: exit_of.  At sub-range level the chain is the orbit of 0 under v -> exit_of[v] / S: found by pointer jumping
+		// (log2 NSUB parallel rounds), the true entry of an on-chain sub-range being its predecessor's exit.  A sub-range that is entered elsewhere than its
+		// exit was traced from is traced from its true entry; where that moves its exit the chain is resolved again, until no exit moves.  (Sub-range 0 is
+		// right from the start, and every round makes the first wrong sub-range of the chain right: at most nitems rounds, one or two in practice.)
+		// A trace that meets a start nobody searched -- the claims say there is none -- ends the resolve: those starts are collected, searched in another
+		// pass of the loop above (the claims start afresh: every search of the last pass is complete and memoised), and everything is resolved again.
+		// Exactness rests on this guard alone, not on the claims.
 		if (j == 0) L.s_npend = 0;
 		SEED_SYNC();
-		if (j == 0) L.onchain[0] = 1u;
+		for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems) {
+			int u = 0;
+			const int X = memo_trace(L.memo, L.lhop, lmask, v * S, (v + 1) * S < clen ? (v + 1) * S : clen, u);
+			if (X < 0) { const u32 idx = atomicAdd(&L.s_npend, 1u); if (idx < SEED_WG) L.pend_s[idx] = (uint16_t)u; }
+			L.exit_of[v] = (uint16_t)(X < 0 ? clen : X);
+		}
 		SEED_SYNC();
-		int cur = 0;
-		for (int span = 1; span < nitems; span <<= 1) {
+		for (int rr = 0; L.s_npend == 0; rr++) {
+			if (rr > nitems) { *(volatile int *)&L.s_abort = 1; break; }      // (cannot happen, see above: the dense kernels are the exact road that is always open)
+			for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems) { const int X = L.exit_of[v]; L.jmp[0][v] = (uint16_t)(X >= clen ? 0xffff : X / S); }
+			if (j < (NSUB + 31) / 32) L.onchain[j] = 0;
+			if (j == 0) L.changed = 0;
+			SEED_SYNC();
+			if (j == 0) L.onchain[0] = 1u;
+			SEED_SYNC();
+			int cur = 0;
+			for (int span = 1; span < nitems; span <<= 1) {
+				for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems) {
+					const int t = L.jmp[cur][v];
+					if (t != 0xffff) {
+						if ((L.onchain[v >> 5] >> (v & 31)) & 1u) atomicOr(&L.onchain[t >> 5], 1u << (t & 31));
+						L.jmp[cur ^ 1][v] = L.jmp[cur][t];
+					} else L.jmp[cur ^ 1][v] = 0xffff;
+				}
+				SEED_SYNC();
+				cur ^= 1;
+			}
+			for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems) L.entry_of[v] = (uint16_t)(v ? clen : 0);      // off-chain: nothing to mark
+			SEED_SYNC();
+			for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems)
+				if ((L.onchain[v >> 5] >> (v & 31)) & 1u) { const int X = L.exit_of[v]; if (X < clen) L.entry_of[X / S] = (uint16_t)X; }
+			SEED_SYNC();
 			for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems) {
-				const int t = L.jmp[cur][v];
-				if (t != 0xffff) {
-					if ((L.onchain[v >> 5] >> (v & 31)) & 1u) atomicOr(&L.onchain[t >> 5], 1u << (t & 31));
-					L.jmp[cur ^ 1][v] = L.jmp[cur][t];
-				} else L.jmp[cur ^ 1][v] = 0xffff;
+				if (!((L.onchain[v >> 5] >> (v & 31)) & 1u)) continue;
+				int u = 0;
+				const int X = memo_trace(L.memo, L.lhop, lmask, L.entry_of[v], (v + 1) * S < clen ? (v + 1) * S : clen, u);
+				if (X < 0) { const u32 idx = atomicAdd(&L.s_npend, 1u); if (idx < SEED_WG) L.pend_s[idx] = (uint16_t)u; }
+				else if (X != (int)L.exit_of[v]) { L.exit_of[v] = (uint16_t)X; L.changed = 1; }
 			}
 			SEED_SYNC();
-			cur ^= 1;
+			const int moved = L.changed;
+			SEED_SYNC();
+			if (!moved) break;
 		}
-		for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems) L.entry_of[v] = (uint16_t)(v ? clen : 0);      // off-chain: nothing to mark
-		SEED_SYNC();
-		for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems)
-			if ((L.onchain[v >> 5] >> (v & 31)) & 1u) { const int X = L.exit_of[v]; if (X < clen) L.entry_of[X / S] = (uint16_t)X; }
-		SEED_SYNC();
-		for (int v = j; v < NSUB; v += SEED_WG) if (v < nitems) {
-			if (!((L.onchain[v >> 5] >> (v & 31)) & 1u)) continue;
-			const int e = L.entry_of[v];
-			const bool known = ((L.rewalked[v >> 5] >> (v & 31)) & 1u) ? e == L.walked_from[v] : memo_nib(L.memo, e) != 0;
-			if (!known) {
-				const u32 idx = atomicAdd(&L.s_npend, 1u);
-				if (idx < SEED_WG) { L.pend_it[idx] = (uint16_t)v; L.walked_from[v] = (uint16_t)e; atomicOr(&L.rewalked[v >> 5], 1u << (v & 31)); }
-			}
-		}
-		SEED_SYNC();
-		if (j == 0) { if (L.s_npend > SEED_WG) L.s_npend = SEED_WG; L.changed = L.s_npend > 0 ? 1 : 0; }
-		SEED_SYNC();
+		const u32 npend = L.s_npend < SEED_WG ? L.s_npend : SEED_WG;
 		t_resolve += wall_clock64() - t_r0;
-		const int again = L.changed;
-		if (again && j < (int)L.s_npend) { fb_item = L.pend_it[j]; dirty = 1; }
+		if (j < (int)npend) { fb_start = L.pend_s[j]; dirty = 1; }
+#ifdef SEED_STATS
+		st_pend += npend;
+#endif
+		if (!npend) break;
+		for (int p = j; p < CLAIM_WORDS; p += SEED_WG) L.claim[p] = 0;
 		SEED_SYNC();
-		if (!again) break;
 	}
 	const bool heavy = L.s_abort != 0;
 	if (heavy) {
@@ -378,7 +410,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 #endif
 	}
 #ifdef SEED_STATS
-	if (j == 0) { atomicAdd((unsigned long long *)&cnt[11], (unsigned long long)st_it); atomicAdd((unsigned long long *)&cnt[13], (unsigned long long)st_fm_any); atomicAdd((unsigned long long *)&cnt[14], (unsigned long long)st_fm_only);
+	if (j == 0) { atomicAdd((unsigned long long *)&cnt[11], (unsigned long long)st_it); atomicAdd((unsigned long long *)&cnt[13], (unsigned long long)st_pend); atomicAdd((unsigned long long *)&cnt[14], (unsigned long long)st_late);
 	              atomicAdd((unsigned long long *)&cnt[15], (unsigned long long)st_act); atomicAdd((unsigned long long *)&cnt[7], (unsigned long long)st_fm); }
 	if (false)
 #endif
@@ -429,7 +461,7 @@ __device__ __forceinline__ void seed_chunk(const DevIndex &di, const uint8_t *__
 // A CU that runs the seed kernel keeps 58 KB of LDS and ~320 VGPRs per SIMD lane free.
 #define SEED_TICKET 16
 #ifndef SEED_WPW
-#define SEED_WPW (SEED_LDS_DIET ? 12 : 8)      // waves (= chunks in flight) per workgroup = per CU (12: what fits the same LDS at SEED_LDS_DIET's 8.4 KB per chunk, an experiment build)
+#define SEED_WPW (SEED_LDS_DIET ? 11 : 8)      // waves (= chunks in flight) per workgroup = per CU (11: what fits the same LDS at SEED_LDS_DIET's 9.0 KB per chunk, an experiment build; 12 before the claim bitmap)
 #endif
 #ifndef SEED_WG_LDS
 #define SEED_WG_LDS 102400      // what a workgroup asks for, whatever its waves need: the 58 KB beside it are what the other contexts' kernels live on
