@@ -25,6 +25,7 @@ EXPORTS = [
     "gsa_block_cigars", "gsa_get_cigar_timing", "gsa_align_many_ex",
     "gsa_block_cs", "gsa_get_cs_timing", "gsa_extras_cs",
     "gsa_lift_set", "gsa_lift", "gsa_get_lift_timing", "gsa_extras_lift",
+    "gsa_track_set", "gsa_ref_track", "gsa_get_track_timing", "gsa_extras_track",
     "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
     "gsa_create_from_pac", "gsa_export_index_table",
 ]
@@ -136,17 +137,33 @@ class Lifts(C.Structure):
     _fields_ = [("n_hits", C.c_int64), ("hits", C.POINTER(LiftHit))]
 
 
+class TrackWin(C.Structure):
+    """gsa_track_win, 32 bytes (include/gsa_hip.h): one window of a reference sequence and what the counted blocks put into it."""
+    _fields_ = [("chr", C.c_int32), ("start", C.c_int32), ("len", C.c_int32), ("n_cov", C.c_uint32), ("n_eq", C.c_uint32), ("n_x", C.c_uint32), ("n_del", C.c_uint32), ("n_ins", C.c_uint32)]
+
+
+class Tracks(C.Structure):
+    _fields_ = [("n_win", C.c_int64), ("win", C.POINTER(TrackWin))]
+
+
+TRACK_WIN_DT = np.dtype([("chr", "<i4"), ("start", "<i4"), ("len", "<i4"), ("n_cov", "<u4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_del", "<u4"), ("n_ins", "<u4")])
 LIFT_HIT_DT = np.dtype([("idx", "<i4"), ("qpos", "<i4"), ("block", "<i4"), ("cls", "u1"), ("rev", "u1"), ("n_cover", "<u2")])
 BLOCK_CS_DT = np.dtype([("cs_off", "<i8"), ("n_cs", "<i4"), ("_pad", "<i4")])
 BLOCK_CIGAR_DT = np.dtype([("cig_off", "<i8"), ("n_cig", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"), ("_pad", "<i4")])
 CIGAR_LETTERS = "MIDNSHP=X"      # by BAM op code; the library writes I (1), D (2), = (7) and X (8)
-WANT_VARIANTS, WANT_CIGARS, WANT_CS, WANT_LIFT = 1, 2, 4, 16
+WANT_VARIANTS, WANT_CIGARS, WANT_CS, WANT_LIFT, WANT_TRACK = 1, 2, 4, 16, 32
 
 
 def lifts_array(l: "Lifts"):
     """gsa_lifts -> LIFT_HIT_DT array (a copy)."""
     n = int(l.n_hits)
     return np.ctypeslib.as_array(C.cast(l.hits, C.POINTER(C.c_uint8)), shape=(n * LIFT_HIT_DT.itemsize,)).view(LIFT_HIT_DT).copy() if n else np.zeros(0, LIFT_HIT_DT)
+
+
+def tracks_array(t: "Tracks"):
+    """gsa_tracks -> TRACK_WIN_DT array (a copy)."""
+    n = int(t.n_win)
+    return np.ctypeslib.as_array(C.cast(t.win, C.POINTER(C.c_uint8)), shape=(n * TRACK_WIN_DT.itemsize,)).view(TRACK_WIN_DT).copy() if n else np.zeros(0, TRACK_WIN_DT)
 
 
 def cigars_arrays(cig: "Cigars"):
@@ -324,7 +341,7 @@ class DeviceContig:
             self.lib.gsa_device_free(self.device, C.c_void_p(self.ptr)); self.ptr = None
 
 
-def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False) -> None:
+def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False, track: bool = False) -> None:
     """gsa_align_many: `contigs` (uint8 arrays, or DeviceContig objects -- all of one kind) on the given contexts, one host
     thread per context inside the library.  on_result(contig_index, Result) runs on the worker threads (the Result is valid
     during the call only).  in_order: hand the contigs out as listed (GSA_MANY_IN_ORDER) instead of longest first.
@@ -337,7 +354,9 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     (cigars_arrays copies them out).
     cs=True: GSA_WANT_CS as well (it implies the CIGARs) -- on_result gets a fifth argument, the contig's Cs (gsa_extras_cs; cs_arrays copies it out).
     lift=True: gsa_align_many_ex with GSA_WANT_LIFT (every aligner holds positions: lift_set) -- on_result(contig_index, Result, Variants or None, Cigars or None[, Cs]) gets
-    one more argument, the contig's Lifts (gsa_extras_lift; lifts_array copies it out)."""
+    one more argument, the contig's Lifts (gsa_extras_lift; lifts_array copies it out).
+    track=True: gsa_align_many_ex with GSA_WANT_TRACK (every aligner holds a window: track_set) -- on_result gets one more argument behind all of those, the contig's
+    Tracks (gsa_extras_track; tracks_array copies it out)."""
     lib = aligners[0].lib
     n = len(contigs)
     ctxs = (C.c_void_p * len(aligners))(*[a.ctx for a in aligners])
@@ -345,9 +364,10 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     qs = (C.c_char_p * n)(*[C.cast(c.ptr if on_dev else c.ctypes.data, C.c_char_p) for c in contigs])
     ql = (C.c_int32 * n)(*[int(c.size) for c in contigs])
     flags = (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16)
-    if cigars or cs or lift:
+    if cigars or cs or lift or track:
         lib.gsa_extras_cs.argtypes = [C.POINTER(Extras), C.POINTER(Cs)]
         lib.gsa_extras_lift.argtypes = [C.POINTER(Extras), C.POINTER(Lifts)]
+        lib.gsa_extras_track.argtypes = [C.POINTER(Extras), C.POINTER(Tracks)]
 
         def ex_cb(user, ci, res, ex):
             e = ex.contents
@@ -364,10 +384,16 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
                 if rc_l != 0:
                     return int(rc_l)
                 args += (lf,)
+            if track:
+                tk = Tracks()
+                rc_t = lib.gsa_extras_track(ex, C.byref(tk))
+                if rc_t != 0:
+                    return int(rc_t)
+                args += (tk,)
             return int((on_result(*args) if on_result else 0) or 0)
         cbx = RESULT_EX_FN(ex_cb)
         lib.gsa_align_many_ex.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.c_uint32, RESULT_EX_FN, C.c_void_p]
-        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0), cbx, None)
+        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0) | (WANT_TRACK if track else 0), cbx, None)
     elif variants:
         cbv = RESULT_VAR_FN(lambda user, ci, res, var: int((on_result(ci, res.contents, var.contents) if on_result else 0) or 0))
         lib.gsa_align_many_variants.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_VAR_FN, C.c_void_p]
@@ -378,7 +404,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
         rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, flags, cb, None)
     if rc != 0:
         msgs = [lib.gsa_last_error(a.ctx).decode() for a in aligners]
-        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
+        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift or track else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
 
 
 def _p(a, t):
@@ -683,6 +709,25 @@ class Aligner:
         ms, n = C.c_double(0), C.c_int64(0)
         self.lib.gsa_get_lift_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         self._ck(self.lib.gsa_get_lift_timing(self.ctx, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    def track_set(self, window: int) -> None:
+        """gsa_track_set: the window length W of this context's per-window reference track from now on; 0 clears it."""
+        self.lib.gsa_track_set.argtypes = [C.c_void_p, C.c_int32]
+        self._ck(self.lib.gsa_track_set(self.ctx, C.c_int32(int(window))))
+
+    def track(self, k: int = 0):
+        """gsa_ref_track on the stage-8 result this context holds (contig k of a bundle): TRACK_WIN_DT array, ascending by (chr, start)."""
+        t = Tracks()
+        self.lib.gsa_ref_track.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Tracks)]
+        self._ck(self.lib.gsa_ref_track(self.ctx, C.c_int32(k), C.byref(t)))
+        return tracks_array(t)
+
+    def track_timing(self):
+        """(host wall ms inside gsa_ref_track on this context since it was created, number of calls)."""
+        ms, n = C.c_double(0), C.c_int64(0)
+        self.lib.gsa_get_track_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        self._ck(self.lib.gsa_get_track_timing(self.ctx, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
     def cs_timing(self):

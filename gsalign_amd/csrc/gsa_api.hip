@@ -35,9 +35,9 @@ static int rewind_to_hits(gsa_ctx *c)
 	return stage1_restore_pdbm(c);
 }
 
-// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip) ask of the context before they run; `who`: the export, for the messages;
-// need_positions: the pass reads the positions of gsa_lift_set
-static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false)
+// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip) ask of the context before they run; `who`: the export, for the messages;
+// need_positions: the pass reads the positions of gsa_lift_set; need_window: the window of gsa_track_set
+static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false, bool need_window = false)
 {
 	const std::string w(who);
 	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, w + ": the context holds no finished (stage 8) result");
@@ -45,6 +45,7 @@ static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_p
 	if (c->q_cur == -2) return gsa_fail(c, GSA_ERR_STATE, w + ": the contig's device copy was overwritten by a prefetch");
 	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, w + ": contig index out of range");
 	if (need_positions && c->lift_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no positions (gsa_lift_set first)");
+	if (need_window && c->track_w <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no window (gsa_track_set first)");
 	GSA_CHECK(c, hipSetDevice(c->device));
 	return GSA_OK;
 }
@@ -79,6 +80,19 @@ int lift_call(gsa_ctx *c, int32_t k, gsa_lifts *out)
 	const auto t0 = std::chrono::steady_clock::now();
 	rc = lift_positions(c, k, out);
 	c->lift_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->lift_calls++;
+	return rc;
+}
+
+// the per-window track of the stage-8 result the context holds: k_track.hip
+int track_call(gsa_ctx *c, int32_t k, gsa_tracks *out)
+{
+	if (!c || !out) return GSA_ERR_ARG;
+	out->n_win = 0; out->win = nullptr;
+	int rc = result_pass_ready(c, k, "gsa_ref_track", false, true);
+	if (rc) return rc;
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = ref_track(c, k, out);
+	c->track_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->track_calls++;
 	return rc;
 }
 
@@ -283,6 +297,20 @@ int gsa_lift_set(gsa_ctx *c, const int64_t *pos, int64_t n)
 }
 int gsa_lift(gsa_ctx *c, int32_t k, gsa_lifts *out) { return lift_call(c, k, out); }
 int gsa_get_lift_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::lift_ms_sum, &gsa_ctx::lift_calls, ms_sum, n_calls); }
+
+int gsa_track_set(gsa_ctx *c, int32_t window)
+{
+	if (!c) return GSA_ERR_ARG;
+	if (window < 0) return gsa_fail(c, GSA_ERR_ARG, "gsa_track_set: the window is negative");
+	i64 nwin = 0;
+	if (window > 0) for (size_t i = 0; i < c->h_chr_len.size(); i++) nwin += ((i64)c->h_chr_len[i] + window - 1) / window;
+	if (nwin >= (1ll << 31) - 256) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_track_set: " + std::to_string((long long)nwin) + " windows (2^31 - 256 or more)");
+	// (the dense counts are all zero between calls, whatever the window was: a new length only lays them out anew)
+	c->track_w = window; c->track_nwin = nwin;
+	return GSA_OK;
+}
+int gsa_ref_track(gsa_ctx *c, int32_t k, gsa_tracks *out) { return track_call(c, k, out); }
+int gsa_get_track_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::track_ms_sum, &gsa_ctx::track_calls, ms_sum, n_calls); }
 
 int gsa_get_wall_sums(gsa_ctx *c, double ms[10], int64_t *n)
 {

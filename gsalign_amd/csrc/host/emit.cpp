@@ -95,6 +95,7 @@ template struct RawArr<gsa_block_cigar>;
 template struct RawArr<gsa_cs_block>;
 template struct RawArr<uint32_t>;
 template struct RawArr<gsa_lift_hit>;
+template struct RawArr<gsa_track_win>;
 void ContigResult::assign(const gsa_result &r, bool summary_mode)
 {
 	summary = summary_mode;
@@ -606,6 +607,108 @@ void Emitter::lift_text(bool first, const QueryContig &q, const ContigResult &r,
 		*w++ = h.cls == GSA_CIGAR_EQ ? '=' : (h.cls == GSA_CIGAR_X ? 'X' : 'D'); *w++ = '\t';
 		w = put_int(w, score[(size_t)h.block]); *w++ = '\t';
 		w = put_int(w, h.n_cover); *w++ = '\n';
+		o.n = (size_t)(w - o.p);
+		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
+	}
+	if (o.n) sink(std::move(o));
+}
+
+// ---- per-window reference track ----------------------------------------------------------------------------------------------------------
+void gsah_track(const HostIndex &ix, const ContigResult &r, int32_t W, std::vector<gsa_track_win> &win)
+{
+	win.clear();
+	if (r.summary || W <= 0) return;      // (a summary result holds neither records nor strings)
+	const size_t nchr = ix.chr_len.size();
+	std::vector<int64_t> win0(nchr + 1, 0);      // first window of every sequence in the dense array
+	for (size_t i = 0; i < nchr; i++) win0[i + 1] = win0[i] + ((int64_t)ix.chr_len[i] + W - 1) / W;
+	struct Iv { int32_t chr; int64_t s, e; };
+	std::vector<Iv> iv;                           // the counted blocks' trimmed spans in forward coordinates inside their sequence
+	std::vector<uint32_t> bin;                    // {n_eq, n_x, n_del, n_ins} per window
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		if (b.bdup != 0 || b.n_frag <= 0 || b.chr < 0 || (size_t)b.chr >= nchr) continue;
+		const gsa_frag first = r.frag(b.frag_off), last = r.frag(b.frag_off + b.n_frag - 1);
+		const int64_t start = first.rpos, end = last.rpos + last.rlen - extension(ix, b, last);
+		if (end <= start) continue;
+		const bool rev = !b.bdir;
+		const int64_t org = rev ? 2 * ix.G - 1 - ix.chr_fwd[b.chr] : ix.chr_fwd[b.chr], w0 = win0[(size_t)b.chr];
+		Iv v; v.chr = b.chr; v.s = rev ? org - (end - 1) : start - org; v.e = rev ? org - start + 1 : end - org;
+		iv.push_back(v);
+		if (bin.empty()) bin.assign((size_t)win0[nchr] * 4, 0u);
+		// a range of the block's records: the counts of one window are gathered while the walk stays in it and added when it leaves (several threads may meet in a window)
+		auto piece = [&](size_t fb, size_t fe) {
+			int64_t cur = -1; uint32_t cnt[4] = { 0, 0, 0, 0 };
+			auto flush = [&] {
+				if (cur >= 0) for (int f = 0; f < 4; f++) if (cnt[f]) __atomic_fetch_add(&bin[(size_t)cur * 4 + f], cnt[f], __ATOMIC_RELAXED);
+				cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+			};
+			// n columns of field f whose reference bases are the text positions t, t + 1, ...: split over the windows by arithmetic
+			auto run = [&](int64_t t, int64_t n, int f) {
+				if (t < start) { n -= start - t; t = start; }
+				if (t + n > end) n = end - t;
+				while (n > 0) {
+					const int64_t l = rev ? org - t : t - org, j = l / W;
+					const int64_t m = std::min<int64_t>(n, rev ? l - j * W + 1 : (j + 1) * W - l);
+					if (w0 + j != cur) { flush(); cur = w0 + j; }
+					cnt[f] += (uint32_t)m; t += m; n -= m;
+				}
+			};
+			for (size_t k = fb; k < fe; k++) {
+				const gsa_frag f = r.frag(b.frag_off + (int64_t)k);
+				if (f.bseed) { run(f.rpos, f.rlen, 0); continue; }
+				const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+				int64_t rp = f.rpos;
+				for (int c = 0; c < f.aln_len; c++) {
+					if (x1[c] == '-') { run(rp - 1, 1, 3); continue; }      // (an inserted query base belongs to the reference base consumed last)
+					run(rp, 1, x2[c] == '-' ? 2 : (column_class(x1[c], x2[c]) == GSA_CIGAR_EQ ? 0 : 1));
+					rp++;
+				}
+			}
+			flush();
+		};
+		if ((size_t)b.n_frag * 16 >= par_min_bytes()) par_ranges((size_t)b.n_frag, (size_t)1 << 13, piece); else piece(0, (size_t)b.n_frag);
+	}
+	if (iv.empty()) return;
+	std::sort(iv.begin(), iv.end(), [](const Iv &x, const Iv &y) { return x.chr != y.chr ? x.chr < y.chr : (x.s != y.s ? x.s < y.s : x.e < y.e); });
+	size_t n = 0;
+	for (size_t j = 0; j < iv.size(); j++) {
+		if (n && iv[n - 1].chr == iv[j].chr && iv[j].s <= iv[n - 1].e) iv[n - 1].e = std::max(iv[n - 1].e, iv[j].e);
+		else iv[n++] = iv[j];
+	}
+	// the windows the merged intervals touch, in order; n_cov: the union
+	for (size_t m = 0; m < n; m++) {
+		const int64_t len = ix.chr_len[(size_t)iv[m].chr];
+		for (int64_t j = iv[m].s / W; j <= (iv[m].e - 1) / W; j++) {
+			const int64_t lo = j * W, hi = std::min<int64_t>(lo + W, len);
+			const uint32_t ov = (uint32_t)(std::min(iv[m].e, hi) - std::max(iv[m].s, lo));
+			if (!win.empty() && win.back().chr == iv[m].chr && win.back().start == lo) { win.back().n_cov += ov; continue; }
+			const uint32_t *c = &bin[(size_t)(win0[(size_t)iv[m].chr] + j) * 4];
+			gsa_track_win w; w.chr = iv[m].chr; w.start = (int32_t)lo; w.len = (int32_t)(hi - lo); w.n_cov = ov; w.n_eq = c[0]; w.n_x = c[1]; w.n_del = c[2]; w.n_ins = c[3];
+			win.push_back(w);
+		}
+	}
+}
+
+// <prefix>.track.tsv: one line per window -- reference name, BED-style start and end inside the sequence, query name, and the five counts
+void Emitter::track_text(bool first, const QueryContig &q, const gsa_track_win *win, int64_t n_win, const std::function<void(OutBuf &&)> &sink) const
+{
+	OutBuf o;
+	if (first) o.append("#ref\tstart\tend\tquery\tcovered\tmatch\tmismatch\tdeleted\tinserted\n");
+	for (int64_t i = 0; i < n_win; i++) {
+		const gsa_track_win &t = win[i];
+		if (t.chr < 0 || (size_t)t.chr >= idx->chr_name.size()) continue;
+		const std::string &rname = idx->chr_name[(size_t)t.chr];
+		o.reserve(o.n + rname.size() + q.name.size() + 128);
+		char *w = o.p + o.n;
+		memcpy(w, rname.data(), rname.size()); w += rname.size(); *w++ = '\t';
+		w = put_int(w, t.start); *w++ = '\t';
+		w = put_int(w, (long long)t.start + t.len); *w++ = '\t';
+		memcpy(w, q.name.data(), q.name.size()); w += q.name.size(); *w++ = '\t';
+		w = put_int(w, (long long)t.n_cov); *w++ = '\t';
+		w = put_int(w, (long long)t.n_eq); *w++ = '\t';
+		w = put_int(w, (long long)t.n_x); *w++ = '\t';
+		w = put_int(w, (long long)t.n_del); *w++ = '\t';
+		w = put_int(w, (long long)t.n_ins); *w++ = '\n';
 		o.n = (size_t)(w - o.p);
 		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
 	}

@@ -120,6 +120,11 @@ void gsah_cs_trim(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops,
 // gsa_lift, and the lift of a host that holds a gsa_result and no GPU context.  hits: ascending in idx, positions no block covers (or outside [0, G)) absent.
 void gsah_lift(const HostIndex &ix, const ContigResult &r, const int64_t *pos, int64_t n, std::vector<gsa_lift_hit> &hits);
 
+// The per-window track of a finished contig over the reference sequences at window length W, by the contract of gsa_ref_track (gsa_hip.h): counted blocks, trimmed
+// coverage, column classes, the insertion rule -- from the records and the two gapped strings.  The comparator of gsa_ref_track, and the track of a host that holds a
+// gsa_result and no GPU context.  win: one record per window with n_cov > 0, ascending by (chr, start); empty for a summary result or W <= 0.
+void gsah_track(const HostIndex &ix, const ContigResult &r, int32_t W, std::vector<gsa_track_win> &win);
+
 struct OutBuf;                             // par.h
 
 struct Emitter {
@@ -146,6 +151,9 @@ struct Emitter {
 	// and 1-based position of every input position (gsa_lift_hit::idx indexes them)
 	void lift_text(bool first, const QueryContig &q, const ContigResult &r, const gsa_lift_hit *hits, int64_t n_hits, const int32_t *ref_chr, const int32_t *ref_pos,
 	               const std::function<void(OutBuf &&)> &sink) const;
+	// <prefix>.track.tsv (-track W): one line per window of gsa_ref_track / gsah_track, in the order given -- reference name, start and end (BED-style: 0-based, half-open,
+	// inside the sequence), query name, covered, match, mismatch, deleted, inserted; first: the header line in front
+	void track_text(bool first, const QueryContig &q, const gsa_track_win *win, int64_t n_win, const std::function<void(OutBuf &&)> &sink) const;
 	// OutputAlignment (tools.cpp:222-286)
 	void aln(FILE *fp, const QueryContig &q, ContigResult &r) const;
 	// OutputDotplot (DotPloting.cpp:10-71): gnuplot script `gp_path` + one data file per plotted reference sequence

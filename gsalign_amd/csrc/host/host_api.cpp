@@ -290,6 +290,26 @@ long long gsah_c_lift(const char *index_prefix, const gsa_result *res, const int
 	return (long long)h.size();
 }
 
+// gsah_track through the C API: the per-window track of one finished contig at window length W, on the host -- what gsa_ref_track gives.  out[cap]; returns the number
+// of windows (call with cap = 0 to size `out`), < 0 on error.  The index of the last prefix stays loaded, behind a lock, as in gsah_c_lift (only its sequence table is read).
+long long gsah_c_track(const char *index_prefix, const gsa_result *res, int32_t W, gsa_track_win *out, long long cap)
+{
+	static std::mutex mu; static std::string have; static HostIndex *idx = nullptr;
+	std::lock_guard<std::mutex> lock(mu);
+	if (!index_prefix || !res || W < 1 || (cap > 0 && !out)) return -1;
+	if (!idx || have != index_prefix) {
+		delete idx; idx = new HostIndex; have.clear(); std::string e;
+		if (!gsah_load_index(index_prefix, *idx, e)) { delete idx; idx = nullptr; return -2; }
+		have = index_prefix;
+	}
+	ContigResult cr; cr.assign(*res);
+	std::vector<gsa_track_win> w;
+	gsah_track(*idx, cr, W, w);
+	const size_t m = std::min<size_t>(w.size(), cap > 0 ? (size_t)cap : 0);
+	if (m) memcpy(out, w.data(), m * sizeof(gsa_track_win));
+	return (long long)w.size();
+}
+
 // OutputDotplot for one contig: script + data files (no gnuplot run).  Returns 1 if something was written.
 // The reference plots AFTER OutputMAF (GSAlign.cpp:543-546), which shortens the last record of a block that runs over the end of
 // its reference sequence (tools.cpp:149-220), and the plot shows the shortened block: the MAF emitter runs first here too.

@@ -8,6 +8,8 @@
 // GPU (gsa_build_index) instead of the host's suffix sorters; the files are the same bytes.  -memindex (with -r): no index file at all -- the reference FASTA is
 // parsed (gsah_reference_from_fasta) and the first GPU's context is made from its .pac bytes in device memory (gsa_create_from_pac).  -lift FILE: the reference positions
 // listed in FILE (name, 1-based position; a VCF works as it is) are carried through every contig's alignment on the GPU (gsa_lift) and written to <prefix>.lift.tsv.
+// -track W: the reference sequences in windows of W bases -- covered, matching, mismatching, deleted and inserted bases per window and query contig, computed on the GPU
+// (gsa_ref_track) and written to <prefix>.track.tsv.
 // The contigs go through gsa_align_many (the per-contig loop of GSAlign.cpp:483-548).  Round 5: a GPU worker thread only COPIES a finished
 // contig out of the library's memory; ONE formatter thread takes the contigs in contig order (OutputMAF appends per contig, VarVec grows in
 // contig order: GSAlign.cpp:543-546) and formats each with the host pool's threads (par.h: the text lines of a block, the variants of a
@@ -53,6 +55,7 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -timing        print where the wall time went (one JSON line on stderr)\n");
 	fprintf(stderr, "         -cs            with -fmt 3: add the cs:Z: difference string (short form) of every alignment, computed on the GPU (gsa_block_cs) [false]\n");
 	fprintf(stderr, "         -lift  FILE    lift the reference positions of FILE (tab-separated: sequence name, 1-based position; '#' lines skipped, a VCF works) to the query on the GPU (gsa_lift): <prefix>.lift.tsv\n");
+	fprintf(stderr, "         -track INT     per window of INT reference bases and query sequence: covered / matching / mismatching / deleted / inserted bases, computed on the GPU (gsa_ref_track): <prefix>.track.tsv\n");
 	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
 	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index), references up to 1.07 Gbp [false]\n", prog);
 	fprintf(stderr, "         -memindex      with -r: build the index in GPU memory (gsa_create_from_pac) and align against it; no index file is written or read, references up to 1.07 Gbp [false]\n\n");
@@ -137,6 +140,7 @@ int main(int argc, char *argv[])
 	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, want_cs = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
 	std::vector<int> gpus;
 	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL, *lift_file = NULL;
+	int track_w = 0;      // -track W (0: no track)
 	if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(argv[0], threads, prm, fmt); return 0; }
 	if (strcmp(argv[1], "index") == 0) {
 		bool on_gpu = false; int device = 0, a = 2;
@@ -168,6 +172,11 @@ int main(int argc, char *argv[])
 		else if (a == "-gpuvar") gpuvar = true;
 		else if (a == "-cs") want_cs = true;
 		else if (a == "-lift" && i + 1 < argc) lift_file = argv[++i];
+		else if (a == "-track" && i + 1 < argc) {
+			char *end = NULL; const long long w = strtoll(argv[++i], &end, 10);
+			if (end == argv[i] || *end || w < 1 || w > 0x7fffffffll) { fprintf(stderr, "-track: the window must be a number of bases from 1 to 2147483647 (got %s)\n", argv[i]); return 1; }
+			track_w = (int)w;
+		}
 		else if (a == "-gpuindex") gpuindex = true;
 		else if (a == "-memindex") memindex = true;
 		else if (a == "-dp") dotplot = true;
@@ -300,9 +309,10 @@ int main(int argc, char *argv[])
 		t_create += now_s() - t;
 	}
 	// (the positions go to every context, the clones included: a clone starts without)
+	if (track_w) for (gsa_ctx *c : ctxs) if (gsa_track_set(c, track_w) != GSA_OK) { fprintf(stderr, "-track: %s\n", gsa_last_error(c)); return 2; }
 	if (want_lift) for (gsa_ctx *c : ctxs) if (gsa_lift_set(c, lift_pos.data(), (int64_t)lift_pos.size()) != GSA_OK) { fprintf(stderr, "-lift: %s\n", gsa_last_error(c)); return 2; }
 
-	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv";
+	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv", trackn = std::string(out_prefix) + ".track.tsv";
 	Emitter em; em.idx = &idx; em.allow_dup = allow_dup;
 	long long n_aln = 0, tot_len = 0, tot_match = 0, n_dup = 0;
 	fprintf(stderr, "Step2. Sequence analysis for all query chromosomes\n");
@@ -318,8 +328,9 @@ int main(int argc, char *argv[])
 		std::vector<RawArr<gsa_block_cigar> > cblk; std::vector<RawArr<uint32_t> > cops;      // -fmt 3: the contig's CIGARs as gsa_block_cigars left them
 		std::vector<RawArr<gsa_cs_block> > sblk; std::vector<RawArr<char> > sbytes; bool want_cs = false;      // -cs: the contig's cs strings as gsa_block_cs left them
 		std::vector<RawArr<gsa_lift_hit> > lift; bool want_lift = false;      // -lift: the contig's hits as gsa_lift left them
+		std::vector<RawArr<gsa_track_win> > track; bool want_track = false;   // -track: the contig's windows as gsa_ref_track left them
 	} sink;
-	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size()); sink.sblk.resize(qs.size()); sink.sbytes.resize(qs.size()); sink.want_cs = want_cs; sink.lift.resize(qs.size()); sink.want_lift = want_lift;
+	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size()); sink.sblk.resize(qs.size()); sink.sbytes.resize(qs.size()); sink.want_cs = want_cs; sink.lift.resize(qs.size()); sink.want_lift = want_lift; sink.track.resize(qs.size()); sink.want_track = track_w != 0;
 	const bool var_on_gpu = gpuvar && vcf;          // (-no_vcf: nobody reads the variants)
 	// the MAF file: created by the first contig that has alignments ("w" for contig 0, "a" afterwards: tools.cpp:158-163 -- a run whose
 	// first contig aligns nowhere appends to whatever the file held, as the reference does)
@@ -328,8 +339,14 @@ int main(int argc, char *argv[])
 	size_t written = 0;
 	FILE *lift_fp = NULL;
 	if (want_lift && !(lift_fp = fopen(liftn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", liftn.c_str(), strerror(errno)); }
+	FILE *track_fp = NULL;
+	if (track_w && !(track_fp = fopen(trackn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", trackn.c_str(), strerror(errno)); }
 	auto write_contig = [&](size_t ci, ContigResult &cr) {
 		fprintf(stderr, "\tProcess query chromsomoe: %s...\n", qs[ci].name.c_str());
+		if (track_fp) {      // (query contigs in file order, a contig's windows ascending; a contig without alignments has none)
+			em.track_text(ci == 0, qs[ci], sink.track[ci].data(), (int64_t)sink.track[ci].size(), [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, track_fp) != o.n) out_failed = true; });
+			sink.track[ci].reset();
+		}
 		if (lift_fp) {      // (query contigs in file order, a contig's hits in input order; a contig without alignments has none)
 			em.lift_text(ci == 0, qs[ci], cr, sink.lift[ci].data(), (int64_t)sink.lift[ci].size(), lift_chr.data(), lift_at.data(), [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, lift_fp) != o.n) out_failed = true; });
 			sink.lift[ci].reset();
@@ -427,6 +444,11 @@ int main(int argc, char *argv[])
 			if (gsa_extras_lift(ex, &lf) != GSA_OK) return 1;
 			sk.lift[(size_t)ci].assign(lf.hits, (size_t)lf.n_hits);
 		}
+		if (sk.want_track) {
+			gsa_tracks tk;
+			if (gsa_extras_track(ex, &tk) != GSA_OK) return 1;
+			sk.track[(size_t)ci].assign(tk.win, (size_t)tk.n_win);
+		}
 		const double dt = now_s() - t;
 		{ std::lock_guard<std::mutex> lk(sk.mu); sk.ready[(size_t)ci] = 1; sk.copy_s += dt; }
 		sk.cv.notify_all();
@@ -434,7 +456,7 @@ int main(int argc, char *argv[])
 	};
 	if (timing && var_on_gpu) for (gsa_ctx *c : ctxs) (void)gsa_set_profiling(c, 8);      // (the variant passes' device time, for the GSA_VARIANT_PASS line)
 	const double ta = now_s(); t_at_align = ta - T0;
-	const int rc_many = (fmt == 3 || want_lift) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u), on_result_ex, &sink)
+	const int rc_many = (fmt == 3 || want_lift || track_w) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u), on_result_ex, &sink)
 	                  : var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
 	                               : gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
 	t_align = now_s() - ta;
@@ -443,6 +465,7 @@ int main(int argc, char *argv[])
 	double cigar_ms = 0;      // -fmt 3: wall time the workers spent inside gsa_block_cigars, all contexts
 	double cs_ms = 0;         // -cs: the same of gsa_block_cs (which runs the CIGAR walk itself: cigar_s is 0 then)
 	double lift_ms = 0;       // -lift: the same of gsa_lift
+	double track_ms = 0;      // -track: the same of gsa_ref_track
 	double var_dev_ms = 0; long long var_dev_n = 0;      // -gpuvar: device time of the variant passes (hipEvents), all contexts
 	double wall_sum[10] = { 0 }; double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 	for (gsa_ctx *c : ctxs) {
@@ -450,6 +473,7 @@ int main(int argc, char *argv[])
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_cigar_timing(c, &cm, &cn) == GSA_OK) cigar_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_cs_timing(c, &cm, &cn) == GSA_OK) cs_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_lift_timing(c, &cm, &cn) == GSA_OK) lift_ms += cm; }
+		{ double cm = 0; int64_t cn = 0; if (gsa_get_track_timing(c, &cm, &cn) == GSA_OK) track_ms += cm; }
 		double vm = 0; int64_t vn = 0; if (gsa_get_variant_timing(c, &vm, &vn) == GSA_OK) { var_dev_ms += vm; var_dev_n += vn; }
 		double am = 0; int64_t an = 0, ab = 0; if (gsa_get_alloc_stats(c, &am, &an, &ab) == GSA_OK) { alloc_ms += am; alloc_n += an; alloc_bytes += ab; }
 	}
@@ -461,6 +485,7 @@ int main(int argc, char *argv[])
 	std::thread destroyer([&] { if (rc_many != GSA_OK) return; const double t = now_s(); for (size_t k = ctxs.size(); k-- > 0;) gsa_destroy(ctxs[k]); t_destroy = now_s() - t; });      // clones before the owners of their index (after an error the contexts stay: their messages are printed below)
 	formatter.join();
 	if (lift_fp) { if (ferror(lift_fp) | fclose(lift_fp)) out_failed = true; lift_fp = NULL; }
+	if (track_fp) { if (ferror(track_fp) | fclose(track_fp)) out_failed = true; track_fp = NULL; }
 	double maf_write_s = 0; unsigned long long maf_bytes = 0;
 	// (the MAF writer still has its queue to write -- ~1 s at human scale: the VCF is sorted, formatted and written beside it, the MAF file is closed behind)
 	auto close_maf = [&] {
@@ -499,10 +524,10 @@ int main(int argc, char *argv[])
 		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, \"cigar_s\": %.3f, "
 		        "\"result_copy_s_sum\": %.3f, \"maf_format_s\": %.3f, \"variants_s\": %.3f, \"output_drain_after_align_s\": %.3f, \"maf_write_s\": %.3f, \"maf_bytes\": %llu, "
 		        "\"vcf_s\": %.3f, \"vcf_write_s\": %.3f, \"vcf_bytes\": %llu, \"destroy_s\": %.3f, \"host_threads\": %d, \"contexts\": %d, \"query_bp\": %lld, \"contigs\": %d, \"gbp_per_s_excl_index_build\": %.4f, "
-		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
+		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
 		        total, t_build, t_index, t_create, t_query, t_pin, t_align, cigar_ms / 1e3, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
-		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
+		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
 	}
 	if (timing && var_on_gpu) fprintf(stderr, "GSA_VARIANT_PASS {\"device_ms_sum\": %.3f, \"passes\": %lld, \"query_bp\": %lld}\n", var_dev_ms, var_dev_n, [&] { long long b = 0; for (const QueryContig &q : qs) b += (long long)q.seq.size(); return b; }());
 	// (everything is on disk and the GPU is released: the process ends here -- unwinding 20 GB of host buffers and the HIP runtime's own

@@ -281,6 +281,28 @@ def lift(index_prefix, seq, result, positions):
     return H[:int(n)].copy()
 
 
+def track(index_prefix, seq, result, W: int):
+    """gsah_c_track: the per-window track of one finished contig over the reference sequences at window length W, on the host, from the records and the gapped
+    strings -- what Aligner.track computes on the GPU, by the contract of gsa_ref_track (include/gsa_hip.h).  result: a capi.Result, a dump dict (oracle layout) or a
+    result dict of capi.Aligner.  The index under index_prefix supplies the reference sequences' lengths; seq is not needed by the walk and may be None.
+    Returns a TRACK_WIN_DT array: one record per window with n_cov > 0, ascending by (chr, start)."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    lib = load()
+    lib.gsah_c_track.restype = C.c_longlong
+    lib.gsah_c_track.argtypes = [C.c_char_p, C.POINTER(capi.Result), C.c_int32, C.c_void_p, C.c_longlong]
+    n = lib.gsah_c_track(index_prefix.encode(), C.byref(result), int(W), None, 0)
+    if n < 0:
+        raise RuntimeError(f"gsah_c_track -> {n}")
+    T = np.zeros(int(n), capi.TRACK_WIN_DT)
+    if n:
+        n2 = lib.gsah_c_track(index_prefix.encode(), C.byref(result), int(W), C.c_void_p(T.ctypes.data), int(T.size))
+        if n2 != n:
+            raise RuntimeError(f"gsah_c_track -> {n2} after {n}")
+    return T
+
+
 def cs_trim(cs_bytes, ops, bdir: bool, ext: int) -> bytes:
     """gsah_c_cs_trim: iExtension's trim on ONE block's cs string (of its untrimmed ops, output order) -- the last `ext` columns in walk order go, a cut ':n' is
     printed again.  Returns the string that stays: the cs of the trimmed ops."""

@@ -431,13 +431,44 @@ int gsa_lift(gsa_ctx *ctx, int32_t k, gsa_lifts *out);
 /* measurement: host wall time the calling threads spent inside gsa_lift on this context since it was created, and the number of calls.  Always on. */
 int gsa_get_lift_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 
+/* ---- per-window reference track ----------------------------------------------------
+ * How much of each reference sequence is aligned, how diverged, and where are the holes?  The reference sequences are cut into windows of W bases; the grid restarts at
+ * every sequence: sequence c of length L has ceil(L / W) windows, window j covers the local positions [j W, min((j + 1) W, L)), no window spans two sequences.
+ *   blocks    only the blocks of contig k with bdup == 0 are counted (the set gsa_call_variants walks)
+ *   coverage  TRIMMED exactly as gsa_lift trims it: a block covers the text positions first.rpos <= t < end, end = last.rpos + last.rlen clamped to the end of the block's
+ *             chromosome copy; text position t is forward position t for a forward-strand block and 2G - 1 - t for a reverse-strand block.  (The per-base clamp, not the
+ *             reference's cut of iExtension COLUMNS: the two agree wherever the overrun lies inside a final seed.)
+ *   columns   the CIGAR's classes by the CIGAR's rule: a seed record is '=' over its length, an equal-length gap that needed no DP is classified base against base, a DP
+ *             gap is read from the op string of its DP job, a pure deletion / insertion record is one class throughout
+ *   n_cov     bases of the window covered by at least one counted block (the union: n_cov <= len)
+ *   n_eq, n_x, n_del   columns of that class whose reference base lies in the window and is covered (t < end), summed over ALL counted blocks: a base under two blocks
+ *             counts twice, n_eq + n_x + n_del is the depth sum
+ *   n_ins     inserted query bases (CIGAR I columns), summed over all counted blocks; each belongs to the reference base consumed last in front of it in WALK order (it
+ *             exists: a gap follows a seed) and is dropped exactly when that base is trimmed
+ * One record per window with n_cov > 0, ascending by (chr, start). */
+typedef struct { int32_t chr, start, len; uint32_t n_cov, n_eq, n_x, n_del, n_ins; } gsa_track_win;   /* 32 bytes; start 0-based inside the sequence */
+typedef struct { int64_t n_win; const gsa_track_win *win; } gsa_tracks;
+/* The window length W of this context from now on; 0 clears it.  A clone starts without a window.  W < 0: GSA_ERR_ARG.  A total of 2^31 - 256 windows or more over all
+ * reference sequences: GSA_ERR_LIMIT, nothing changed.  Device memory: 16 bytes per window of the reference (allocated and cleared by the first gsa_ref_track after the
+ * call, kept clear by the pass itself) + 32 per window that comes home. */
+int gsa_track_set(gsa_ctx *ctx, int32_t window);
+/* The track of the stage-8 result the context holds.  Validity, call order, k and the error codes are those of gsa_block_cigars; without a window GSA_ERR_STATE.  No counted
+ * block: n_win = 0.  The counts are uint32_t: when the reference bases plus the query bases that the counted blocks of contig k span (last record's end minus first record's
+ * start on either side, summed over the blocks -- no count can exceed the sum of the columns, which this bounds) exceed 2^32 - 1, GSA_ERR_LIMIT before any launch.  The answer
+ * lives in buffers of its own: the four other passes return what they returned before, and so does this call after one of them.  Memory is owned by the context and valid
+ * until the next call on it; the windows come home in one copy into pinned memory. */
+int gsa_ref_track(gsa_ctx *ctx, int32_t k, gsa_tracks *out);
+/* measurement: host wall time the calling threads spent inside gsa_ref_track on this context since it was created, and the number of calls.  Always on. */
+int gsa_get_track_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+
 /* gsa_align_many with optional passes run by the worker in front of the callback -- before the prefetch after next can touch the contig's
- * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift).  *ex and what it
+ * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track).  *ex and what it
  * points to are valid during the callback only, like *res. */
 #define GSA_WANT_VARIANTS 1u
 #define GSA_WANT_CIGARS   2u
 #define GSA_WANT_CS       4u   /* gsa_block_cs; implies GSA_WANT_CIGARS */
 #define GSA_WANT_LIFT     16u  /* gsa_lift of every contig; every context of ctx[] must hold positions (gsa_lift_set), else GSA_ERR_STATE before any contig is aligned */
+#define GSA_WANT_TRACK    32u  /* gsa_ref_track of every contig; every context of ctx[] must hold a window (gsa_track_set), else GSA_ERR_STATE before any contig is aligned */
 typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;   /* NULL where not asked for */
 /* The contig's cs strings inside the callback of gsa_align_many_ex: the library hands the callback a LARGER object whose head is the gsa_extras
  * (which keeps its two members and its 16 bytes), and this call reaches what lies behind it -- so it is valid for the `ex` the library passed
@@ -445,6 +476,8 @@ typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;  
 int gsa_extras_cs(const gsa_extras *ex, gsa_cs *out);
 /* The contig's lifted positions inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_LIFT was not asked for). */
 int gsa_extras_lift(const gsa_extras *ex, gsa_lifts *out);
+/* The contig's track inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_TRACK was not asked for). */
+int gsa_extras_track(const gsa_extras *ex, gsa_tracks *out);
 typedef int (*gsa_result_ex_fn)(void *user, int32_t contig, const gsa_result *res, const gsa_extras *ex);
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
                       uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user);
