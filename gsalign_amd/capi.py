@@ -26,6 +26,7 @@ EXPORTS = [
     "gsa_block_cs", "gsa_get_cs_timing", "gsa_extras_cs",
     "gsa_lift_set", "gsa_lift", "gsa_get_lift_timing", "gsa_extras_lift",
     "gsa_track_set", "gsa_ref_track", "gsa_get_track_timing", "gsa_extras_track",
+    "gsa_block_segs", "gsa_get_seg_timing", "gsa_extras_segs",
     "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
     "gsa_create_from_pac", "gsa_export_index_table",
 ]
@@ -146,12 +147,28 @@ class Tracks(C.Structure):
     _fields_ = [("n_win", C.c_int64), ("win", C.POINTER(TrackWin))]
 
 
+class Seg(C.Structure):
+    """gsa_seg, 12 bytes (include/gsa_hip.h): one data line of a chain -- an aligned segment and the gap behind it in output order."""
+    _fields_ = [("size", C.c_int32), ("dt", C.c_int32), ("dq", C.c_int32)]
+
+
+class SegBlock(C.Structure):
+    """gsa_seg_block, 16 bytes: where a block's triples lie and how many there are."""
+    _fields_ = [("seg_off", C.c_int64), ("n_seg", C.c_int32), ("_pad", C.c_int32)]
+
+
+class Segs(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("n_segs", C.c_int64), ("blk", C.POINTER(SegBlock)), ("seg", C.POINTER(Seg))]
+
+
+SEG_DT = np.dtype([("size", "<i4"), ("dt", "<i4"), ("dq", "<i4")])
+SEG_BLOCK_DT = np.dtype([("seg_off", "<i8"), ("n_seg", "<i4"), ("_pad", "<i4")])
 TRACK_WIN_DT = np.dtype([("chr", "<i4"), ("start", "<i4"), ("len", "<i4"), ("n_cov", "<u4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_del", "<u4"), ("n_ins", "<u4")])
 LIFT_HIT_DT = np.dtype([("idx", "<i4"), ("qpos", "<i4"), ("block", "<i4"), ("cls", "u1"), ("rev", "u1"), ("n_cover", "<u2")])
 BLOCK_CS_DT = np.dtype([("cs_off", "<i8"), ("n_cs", "<i4"), ("_pad", "<i4")])
 BLOCK_CIGAR_DT = np.dtype([("cig_off", "<i8"), ("n_cig", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"), ("_pad", "<i4")])
 CIGAR_LETTERS = "MIDNSHP=X"      # by BAM op code; the library writes I (1), D (2), = (7) and X (8)
-WANT_VARIANTS, WANT_CIGARS, WANT_CS, WANT_LIFT, WANT_TRACK = 1, 2, 4, 16, 32
+WANT_VARIANTS, WANT_CIGARS, WANT_CS, WANT_LIFT, WANT_TRACK, WANT_SEGS = 1, 2, 4, 16, 32, 64
 
 
 def lifts_array(l: "Lifts"):
@@ -164,6 +181,14 @@ def tracks_array(t: "Tracks"):
     """gsa_tracks -> TRACK_WIN_DT array (a copy)."""
     n = int(t.n_win)
     return np.ctypeslib.as_array(C.cast(t.win, C.POINTER(C.c_uint8)), shape=(n * TRACK_WIN_DT.itemsize,)).view(TRACK_WIN_DT).copy() if n else np.zeros(0, TRACK_WIN_DT)
+
+
+def segs_arrays(sg: "Segs"):
+    """gsa_segs -> (SEG_BLOCK_DT array, SEG_DT array), both copies; block b's triples are seg[seg_off : seg_off + n_seg]."""
+    nb, n = int(sg.n_blocks), int(sg.n_segs)
+    blk = np.ctypeslib.as_array(C.cast(sg.blk, C.POINTER(C.c_uint8)), shape=(nb * SEG_BLOCK_DT.itemsize,)).view(SEG_BLOCK_DT).copy() if nb else np.zeros(0, SEG_BLOCK_DT)
+    seg = np.ctypeslib.as_array(C.cast(sg.seg, C.POINTER(C.c_uint8)), shape=(n * SEG_DT.itemsize,)).view(SEG_DT).copy() if n else np.zeros(0, SEG_DT)
+    return blk, seg
 
 
 def cigars_arrays(cig: "Cigars"):
@@ -341,7 +366,7 @@ class DeviceContig:
             self.lib.gsa_device_free(self.device, C.c_void_p(self.ptr)); self.ptr = None
 
 
-def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False, track: bool = False) -> None:
+def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False, track: bool = False, segs: bool = False) -> None:
     """gsa_align_many: `contigs` (uint8 arrays, or DeviceContig objects -- all of one kind) on the given contexts, one host
     thread per context inside the library.  on_result(contig_index, Result) runs on the worker threads (the Result is valid
     during the call only).  in_order: hand the contigs out as listed (GSA_MANY_IN_ORDER) instead of longest first.
@@ -356,7 +381,9 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     lift=True: gsa_align_many_ex with GSA_WANT_LIFT (every aligner holds positions: lift_set) -- on_result(contig_index, Result, Variants or None, Cigars or None[, Cs]) gets
     one more argument, the contig's Lifts (gsa_extras_lift; lifts_array copies it out).
     track=True: gsa_align_many_ex with GSA_WANT_TRACK (every aligner holds a window: track_set) -- on_result gets one more argument behind all of those, the contig's
-    Tracks (gsa_extras_track; tracks_array copies it out)."""
+    Tracks (gsa_extras_track; tracks_array copies it out).
+    segs=True: gsa_align_many_ex with GSA_WANT_SEGS (it implies the CIGARs) -- on_result gets one more argument behind all of those, the contig's Segs (gsa_extras_segs;
+    segs_arrays copies it out)."""
     lib = aligners[0].lib
     n = len(contigs)
     ctxs = (C.c_void_p * len(aligners))(*[a.ctx for a in aligners])
@@ -364,10 +391,11 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     qs = (C.c_char_p * n)(*[C.cast(c.ptr if on_dev else c.ctypes.data, C.c_char_p) for c in contigs])
     ql = (C.c_int32 * n)(*[int(c.size) for c in contigs])
     flags = (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16)
-    if cigars or cs or lift or track:
+    if cigars or cs or lift or track or segs:
         lib.gsa_extras_cs.argtypes = [C.POINTER(Extras), C.POINTER(Cs)]
         lib.gsa_extras_lift.argtypes = [C.POINTER(Extras), C.POINTER(Lifts)]
         lib.gsa_extras_track.argtypes = [C.POINTER(Extras), C.POINTER(Tracks)]
+        lib.gsa_extras_segs.argtypes = [C.POINTER(Extras), C.POINTER(Segs)]
 
         def ex_cb(user, ci, res, ex):
             e = ex.contents
@@ -390,10 +418,16 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
                 if rc_t != 0:
                     return int(rc_t)
                 args += (tk,)
+            if segs:
+                sg = Segs()
+                rc_g = lib.gsa_extras_segs(ex, C.byref(sg))
+                if rc_g != 0:
+                    return int(rc_g)
+                args += (sg,)
             return int((on_result(*args) if on_result else 0) or 0)
         cbx = RESULT_EX_FN(ex_cb)
         lib.gsa_align_many_ex.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.c_uint32, RESULT_EX_FN, C.c_void_p]
-        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0) | (WANT_TRACK if track else 0), cbx, None)
+        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0) | (WANT_TRACK if track else 0) | (WANT_SEGS if segs else 0), cbx, None)
     elif variants:
         cbv = RESULT_VAR_FN(lambda user, ci, res, var: int((on_result(ci, res.contents, var.contents) if on_result else 0) or 0))
         lib.gsa_align_many_variants.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_VAR_FN, C.c_void_p]
@@ -404,7 +438,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
         rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, flags, cb, None)
     if rc != 0:
         msgs = [lib.gsa_last_error(a.ctx).decode() for a in aligners]
-        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift or track else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
+        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift or track or segs else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
 
 
 def _p(a, t):
@@ -728,6 +762,20 @@ class Aligner:
         ms, n = C.c_double(0), C.c_int64(0)
         self.lib.gsa_get_track_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         self._ck(self.lib.gsa_get_track_timing(self.ctx, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    def block_segs(self, k: int = 0):
+        """gsa_block_segs on the stage-8 result this context holds (contig k of a bundle): (SEG_BLOCK_DT array, one entry per block; SEG_DT array of all triples)."""
+        sg = Segs()
+        self.lib.gsa_block_segs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Segs)]
+        self._ck(self.lib.gsa_block_segs(self.ctx, C.c_int32(k), C.byref(sg)))
+        return segs_arrays(sg)
+
+    def seg_timing(self):
+        """(host wall ms inside gsa_block_segs on this context since it was created, its CIGAR pass included; number of calls)."""
+        ms, n = C.c_double(0), C.c_int64(0)
+        self.lib.gsa_get_seg_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        self._ck(self.lib.gsa_get_seg_timing(self.ctx, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
     def cs_timing(self):

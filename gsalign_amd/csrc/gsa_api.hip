@@ -35,7 +35,7 @@ static int rewind_to_hits(gsa_ctx *c)
 	return stage1_restore_pdbm(c);
 }
 
-// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip) ask of the context before they run; `who`: the export, for the messages;
+// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip) ask of the context before they run; `who`: the export, for the messages;
 // need_positions: the pass reads the positions of gsa_lift_set; need_window: the window of gsa_track_set
 static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false, bool need_window = false)
 {
@@ -93,6 +93,20 @@ int track_call(gsa_ctx *c, int32_t k, gsa_tracks *out)
 	const auto t0 = std::chrono::steady_clock::now();
 	rc = ref_track(c, k, out);
 	c->track_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->track_calls++;
+	return rc;
+}
+
+// the chain triples of every block of the stage-8 result the context holds: k_segs.hip
+int segs_call(gsa_ctx *c, int32_t k, gsa_segs *out, gsa_cigars *cig, const gsa_cigars *have)
+{
+	if (!c || !out) return GSA_ERR_ARG;
+	out->n_blocks = 0; out->n_segs = 0; out->blk = nullptr; out->seg = nullptr;
+	if (cig) { cig->n_blocks = 0; cig->n_ops = 0; cig->blk = nullptr; cig->ops = nullptr; }
+	int rc = result_pass_ready(c, k, "gsa_block_segs");
+	if (rc) return rc;
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = block_segs(c, k, out, cig, have);
+	c->seg_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->seg_calls++;
 	return rc;
 }
 
@@ -311,6 +325,9 @@ int gsa_track_set(gsa_ctx *c, int32_t window)
 }
 int gsa_ref_track(gsa_ctx *c, int32_t k, gsa_tracks *out) { return track_call(c, k, out); }
 int gsa_get_track_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::track_ms_sum, &gsa_ctx::track_calls, ms_sum, n_calls); }
+
+int gsa_block_segs(gsa_ctx *c, int32_t k, gsa_segs *out) { return segs_call(c, k, out, nullptr, nullptr); }
+int gsa_get_seg_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::seg_ms_sum, &gsa_ctx::seg_calls, ms_sum, n_calls); }
 
 int gsa_get_wall_sums(gsa_ctx *c, double ms[10], int64_t *n)
 {

@@ -91,7 +91,7 @@ static std::vector<std::vector<int32_t> > plan_units(const std::vector<int32_t> 
 }
 
 // what the callback of gsa_align_many_ex is handed: the public gsa_extras at the head, the answers of later passes behind it
-struct ExtrasFull { gsa_extras ex; const gsa_cs *cs; const gsa_lifts *lift; const gsa_tracks *track; };
+struct ExtrasFull { gsa_extras ex; const gsa_cs *cs; const gsa_lifts *lift; const gsa_tracks *track; const gsa_segs *segs; };
 // gsa_align_many, gsa_align_many_variants and gsa_align_many_ex: one loop, three ways to hand a finished contig over (the passes asked for run first, in the worker that finished it)
 struct ManySink { gsa_result_fn on_result = nullptr; gsa_result_var_fn on_var = nullptr; gsa_result_ex_fn on_ex = nullptr; uint32_t want = 0; };
 static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n, uint32_t flags, const ManySink &sk, void *user)
@@ -101,12 +101,14 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 	auto deliver = [&](gsa_ctx *c, int32_t k, int32_t ci, const gsa_result *res) -> int {
 		if (sk.on_var) { gsa_variants var; const int rcv = gsa_call_variants(c, k, &var); return rcv != GSA_OK ? rcv : sk.on_var(user, ci, res, &var); }
 		if (sk.on_ex) {
-			gsa_variants var; gsa_cigars cig; gsa_cs cs; gsa_lifts lift; gsa_tracks trk; ExtrasFull full = { { nullptr, nullptr }, nullptr, nullptr, nullptr }; gsa_extras &ex = full.ex;
+			gsa_variants var; gsa_cigars cig; gsa_cs cs; gsa_lifts lift; gsa_tracks trk; gsa_segs sg; ExtrasFull full = { { nullptr, nullptr }, nullptr, nullptr, nullptr, nullptr }; gsa_extras &ex = full.ex;
 			// (the variants are copied by no one before the CIGAR pass runs, and both live in buffers of their own: the second pass leaves the first one's answer alone)
 			if (sk.want & GSA_WANT_VARIANTS) { const int rcv = gsa_call_variants(c, k, &var); if (rcv != GSA_OK) return rcv; ex.var = &var; }
 			// (the cs pass runs the CIGAR walk itself, into the CIGAR pass's buffers: its ops are the ones handed out, no second walk)
 			if (sk.want & GSA_WANT_CS) { const int rcs = cs_call(c, k, &cs, &cig); if (rcs != GSA_OK) return rcs; full.cs = &cs; ex.cig = &cig; }
-			else if (sk.want & GSA_WANT_CIGARS) { const int rcc = gsa_block_cigars(c, k, &cig); if (rcc != GSA_OK) return rcc; ex.cig = &cig; }
+			// (the segs pass runs the CIGAR walk itself too -- behind the cs pass it reads what that walk has just left on the device, no second walk; its ops are the ones handed out)
+			if (sk.want & GSA_WANT_SEGS) { const bool walked = (sk.want & GSA_WANT_CS) != 0; const int rcg = segs_call(c, k, &sg, walked ? nullptr : &cig, walked ? &cig : nullptr); if (rcg != GSA_OK) return rcg; full.segs = &sg; ex.cig = &cig; }
+			else if (!(sk.want & GSA_WANT_CS) && (sk.want & GSA_WANT_CIGARS)) { const int rcc = gsa_block_cigars(c, k, &cig); if (rcc != GSA_OK) return rcc; ex.cig = &cig; }
 			if (sk.want & GSA_WANT_LIFT) { const int rcl = lift_call(c, k, &lift); if (rcl != GSA_OK) return rcl; full.lift = &lift; }
 			if (sk.want & GSA_WANT_TRACK) { const int rct = track_call(c, k, &trk); if (rct != GSA_OK) return rct; full.track = &trk; }
 			return sk.on_ex(user, ci, res, &ex);
@@ -211,7 +213,7 @@ int gsa_align_many_variants(gsa_ctx *const *ctx, int32_t n_ctx, const char *cons
 }
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n, uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user)
 {
-	if (!on_result || (want & ~(uint32_t)(GSA_WANT_VARIANTS | GSA_WANT_CIGARS | GSA_WANT_CS | GSA_WANT_LIFT | GSA_WANT_TRACK))) return GSA_ERR_ARG;
+	if (!on_result || (want & ~(uint32_t)(GSA_WANT_VARIANTS | GSA_WANT_CIGARS | GSA_WANT_CS | GSA_WANT_LIFT | GSA_WANT_TRACK | GSA_WANT_SEGS))) return GSA_ERR_ARG;
 	ManySink sk; sk.on_ex = on_result; sk.want = want;
 	return align_many_impl(ctx, n_ctx, query, qlen, n, flags, sk, user);
 }
@@ -234,6 +236,16 @@ int gsa_extras_lift(const gsa_extras *ex, gsa_lifts *out)
 	const gsa_lifts *l = ((const ExtrasFull *)ex)->lift;
 	if (!l) return GSA_ERR_STATE;
 	*out = *l;
+	return GSA_OK;
+}
+// the chain segments behind it (GSA_WANT_SEGS)
+int gsa_extras_segs(const gsa_extras *ex, gsa_segs *out)
+{
+	if (!ex || !out) return GSA_ERR_ARG;
+	out->n_blocks = 0; out->n_segs = 0; out->blk = nullptr; out->seg = nullptr;
+	const gsa_segs *s = ((const ExtrasFull *)ex)->segs;
+	if (!s) return GSA_ERR_STATE;
+	*out = *s;
 	return GSA_OK;
 }
 // the per-window track behind it (GSA_WANT_TRACK)

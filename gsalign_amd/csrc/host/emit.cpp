@@ -96,6 +96,8 @@ template struct RawArr<gsa_cs_block>;
 template struct RawArr<uint32_t>;
 template struct RawArr<gsa_lift_hit>;
 template struct RawArr<gsa_track_win>;
+template struct RawArr<gsa_seg_block>;
+template struct RawArr<gsa_seg>;
 void ContigResult::assign(const gsa_result &r, bool summary_mode)
 {
 	summary = summary_mode;
@@ -511,6 +513,57 @@ void Emitter::paf(FILE *fp, const QueryContig &q, ContigResult &r, const gsa_blo
 	paf_text(q, r, blk, ops, [&](OutBuf &&o) { if (o.n) fwrite(o.p, 1, o.n, fp); }, csb, cs);
 }
 
+// ---- chain segments -----------------------------------------------------------------------------------------------------------------------
+void gsah_block_segs(const ContigResult &r, std::vector<gsa_seg_block> &blk, std::vector<gsa_seg> &segs)
+{
+	blk.assign(r.blocks.size(), gsa_seg_block());
+	segs.clear();
+	std::vector<gsa_seg> w;                       // the block's triples in walk order: {size, gap behind it}
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		w.clear();
+		bool in_seg = false; int32_t dt = 0, dq = 0;      // the gap columns seen since the last aligned one
+		auto aligned = [&](int64_t n) {
+			if (n <= 0) return;
+			if (!in_seg) { if (!w.empty()) { w.back().dt = dt; w.back().dq = dq; } const gsa_seg s = { 0, 0, 0 }; w.push_back(s); in_seg = true; }
+			w.back().size += (int32_t)n;
+		};
+		auto gap = [&](bool ref_base) { if (in_seg) { in_seg = false; dt = dq = 0; } if (ref_base) dt++; else dq++; };      // (in front of the first segment: counted and never stored)
+		for (int64_t k = 0; k < b.n_frag; k++) {
+			const gsa_frag f = r.frag(b.frag_off + k);
+			if (f.bseed) aligned(f.qlen);
+			else {
+				const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+				for (int i = 0; i < f.aln_len; i++) { if (x1[i] == '-') gap(false); else if (x2[i] == '-') gap(true); else aligned(1); }
+			}
+		}
+		blk[bi].seg_off = (int64_t)segs.size(); blk[bi].n_seg = (int32_t)w.size(); blk[bi]._pad = 0;
+		if (b.bdir) segs.insert(segs.end(), w.begin(), w.end());
+		else for (size_t k = w.size(); k-- > 0;) { gsa_seg s = { w[k].size, 0, 0 }; if (k > 0) { s.dt = w[k - 1].dt; s.dq = w[k - 1].dq; } segs.push_back(s); }      // SelfComplementarySeq: back to front, the gap in front comes behind
+	}
+}
+
+void gsah_segs_trim(const gsa_seg *segs, int64_t n, int bdir, int64_t ext, std::vector<gsa_seg> &out)
+{
+	int64_t lo = 0, hi = n, edge = -1;      // the triples that stay: [lo, hi); edge: what is left of the segment at the cut
+	while (ext > 0 && lo < hi) {
+		const gsa_seg &s = segs[bdir ? hi - 1 : lo];
+		if (ext < s.size) { edge = s.size - ext; ext = 0; break; }
+		ext -= s.size;
+		if (bdir) hi--; else lo++;
+		if (lo >= hi) break;
+		// the gap that is now at the end, in walk order in front of the segment that went: a forward block's lies in the triple in front, a reverse-strand block's in the triple that went
+		const gsa_seg &g = bdir ? segs[hi - 1] : s;
+		const int64_t cols = (int64_t)g.dt + g.dq;
+		ext -= ext < cols ? ext : cols;
+	}
+	out.assign(segs + lo, segs + hi);
+	if (!out.empty()) {
+		if (edge >= 0) { if (bdir) out.back().size = (int32_t)edge; else out.front().size = (int32_t)edge; }
+		out.back().dt = 0; out.back().dq = 0;
+	}
+}
+
 // ---- lifted reference positions ----------------------------------------------------------------------------------------------------------
 void gsah_lift(const HostIndex &ix, const ContigResult &r, const int64_t *pos, int64_t n, std::vector<gsa_lift_hit> &hits)
 {
@@ -611,6 +664,69 @@ void Emitter::lift_text(bool first, const QueryContig &q, const ContigResult &r,
 		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
 	}
 	if (o.n) sink(std::move(o));
+}
+
+// ---- UCSC chain ----------------------------------------------------------------------------------------------------------------------------
+void Emitter::chain_text(const QueryContig &q, const ContigResult &r, const gsa_seg_block *blk, const gsa_seg *seg, int64_t *id, const std::function<void(OutBuf &&)> &sink) const
+{
+	std::vector<gsa_seg_block> own_blk; std::vector<gsa_seg> own_seg, cut;
+	if (r.summary) return;      // (a summary result holds no untrimmed last record per block in the place this walk looks, and the comparator needs the strings)
+	if (!blk) { gsah_block_segs(r, own_blk, own_seg); blk = own_blk.data(); seg = own_seg.data(); }
+	OutBuf o;
+	const long long qsize = (long long)q.seq.size();
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		if (!allow_dup && b.bdup) continue;
+		if (b.n_frag <= 0 || blk[bi].n_seg <= 0) continue;
+		const gsa_frag first = r.frag(b.frag_off), last = r.frag(b.frag_off + b.n_frag - 1);
+		const int ext = extension(*idx, b, last);
+		const gsa_seg *bs = seg + blk[bi].seg_off; int64_t ns = blk[bi].n_seg;
+		if (ext > 0) { gsah_segs_trim(bs, ns, b.bdir, ext, cut); bs = cut.data(); ns = (int64_t)cut.size(); }
+		if (ns <= 0) continue;
+		long long tbases = 0, qbases = 0;
+		for (int64_t k = 0; k < ns; k++) { tbases += (long long)bs[k].size + bs[k].dt; qbases += (long long)bs[k].size + bs[k].dq; }
+		long long ts, qs;
+		if (b.bdir) { ts = b.gpos - 1; qs = first.qpos; }
+		else {
+			// the block ends, in walk order, where it starts in the output.  The MAF line starts at the end of the last record shortened by ext (tools.cpp:192-202, every cut
+			// column taken as a base of either side); gap columns the cut left at that edge go with their gap, and their bases move the start on
+			long long rem_d = 0, rem_i = 0;
+			if (ext > 0) {
+				int64_t skip = ext; bool done = false;
+				for (int64_t k = b.n_frag - 1; k >= 0 && !done; k--) {
+					const gsa_frag f = r.frag(b.frag_off + k);
+					const int64_t L = f.bseed ? f.qlen : f.aln_len;
+					if (L <= 0) continue;
+					if (skip >= L) { skip -= L; continue; }
+					if (f.bseed) break;
+					const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+					for (int64_t i = L - 1 - skip; i >= 0; i--) { if (x1[i] == '-') rem_i++; else if (x2[i] == '-') rem_d++; else { done = true; break; } }
+					skip = 0;
+				}
+			}
+			int d, c, g; idx->coordinate(last.rpos + last.rlen - ext - rem_d - 1, &d, &c, &g); ts = g - 1;
+			qs = qsize - ((long long)last.qpos + last.qlen - ext - rem_i);
+		}
+		const std::string &rname = idx->chr_name[b.chr];
+		o.reserve(o.n + q.name.size() + rname.size() + 256 + (size_t)ns * 36);
+		char *w = o.p + o.n;
+		memcpy(w, "chain ", 6); w += 6; w = put_int(w, b.bdup ? 1 : b.score - ext); *w++ = ' ';
+		memcpy(w, rname.data(), rname.size()); w += rname.size(); *w++ = ' ';
+		w = put_int(w, idx->chr_len[b.chr]); memcpy(w, " + ", 3); w += 3; w = put_int(w, ts); *w++ = ' '; w = put_int(w, ts + tbases); *w++ = ' ';
+		memcpy(w, q.name.data(), q.name.size()); w += q.name.size(); *w++ = ' ';
+		w = put_int(w, qsize); *w++ = ' '; *w++ = b.bdir ? '+' : '-'; *w++ = ' '; w = put_int(w, qs); *w++ = ' '; w = put_int(w, qs + qbases); *w++ = ' ';
+		w = put_int(w, ++*id); *w++ = '\n';
+		for (int64_t k = 0; k + 1 < ns; k++) { w = put_int(w, bs[k].size); *w++ = '\t'; w = put_int(w, bs[k].dt); *w++ = '\t'; w = put_int(w, bs[k].dq); *w++ = '\n'; }
+		w = put_int(w, bs[ns - 1].size); *w++ = '\n'; *w++ = '\n';
+		o.n = (size_t)(w - o.p);
+		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
+	}
+	if (o.n) sink(std::move(o));
+}
+
+void Emitter::chain(FILE *fp, const QueryContig &q, const ContigResult &r, const gsa_seg_block *blk, const gsa_seg *seg, int64_t *id) const
+{
+	chain_text(q, r, blk, seg, id, [&](OutBuf &&o) { if (o.n) fwrite(o.p, 1, o.n, fp); });
 }
 
 // ---- per-window reference track ----------------------------------------------------------------------------------------------------------

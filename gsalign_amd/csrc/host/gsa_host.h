@@ -115,6 +115,15 @@ void gsah_block_cs(const ContigResult &r, std::vector<gsa_cs_block> &blk, std::s
 // tail of a forward block's string, the head of a reverse-strand block's -- and a cut ":n" is printed again.  out = the cs of the trimmed ops.
 void gsah_cs_trim(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, int bdir, int64_t ext, std::string &out);
 
+// The chain triples of every block of a finished contig (gsa_seg_block / gsa_seg as in gsa_hip.h), UNTRIMMED: the column walk of gsah_block_cigars over the records
+// and the two gapped strings with a merge of its own -- a state machine over aligned / gap columns, no CIGAR ops in between.  The comparator of gsa_block_segs, and the
+// chain source of a host that holds a gsa_result and no GPU context.
+void gsah_block_segs(const ContigResult &r, std::vector<gsa_seg_block> &blk, std::vector<gsa_seg> &segs);
+// iExtension's trim on ONE block's triples (segs[n], output order): the last `ext` columns IN WALK ORDER go -- they are taken off the last triples of a forward block,
+// off the FIRST ones of a reverse-strand block.  A cut that falls inside a gap or at its edge takes the whole gap: a chain neither starts nor ends with one.  out = the
+// triples that stay (the last one with dt = dq = 0; empty when nothing stays).  Needs only the triples.
+void gsah_segs_trim(const gsa_seg *segs, int64_t n, int bdir, int64_t ext, std::vector<gsa_seg> &out);
+
 // The positions pos[0 .. n) (0-based forward global reference coordinates) lifted through a finished contig, by the contract of gsa_lift (gsa_hip.h): coverage trimmed by
 // iExtension, the choice among covering blocks, the class and query position of the chosen column -- from the records and the two gapped strings.  The comparator of
 // gsa_lift, and the lift of a host that holds a gsa_result and no GPU context.  hits: ascending in idx, positions no block covers (or outside [0, G)) absent.
@@ -154,6 +163,17 @@ struct Emitter {
 	// <prefix>.track.tsv (-track W): one line per window of gsa_ref_track / gsah_track, in the order given -- reference name, start and end (BED-style: 0-based, half-open,
 	// inside the sequence), query name, covered, match, mismatch, deleted, inserted; first: the header line in front
 	void track_text(bool first, const QueryContig &q, const gsa_track_win *win, int64_t n_win, const std::function<void(OutBuf &&)> &sink) const;
+	// <prefix>.chain (-chain): a UCSC chain per block, blocks selected like OutputMAF's (-unique), from the block's UNTRIMMED triples blk / seg (gsa_block_segs; NULL: computed
+	// here, gsah_block_segs) cut by iExtension (gsah_segs_trim) --
+	//   chain <score> <tName> <tSize> + <tStart> <tEnd> <qName> <qSize> <+|-> <qStart> <qEnd> <id> / "size dt dq" per triple but the last / "size" / an empty line
+	// score as the MAF prints it (trimmed; 1 for a duplicate); coordinates 0-based, half-open, for '-' on the query's reverse strand (the MAF `s` line's convention), and
+	// tEnd - tStart = sum(size + dt), qEnd - qStart = sum(size + dq).  A forward block starts where its MAF line starts; a reverse-strand block starts where its MAF line
+	// starts (the end of its last record, shortened by the `ext` columns as the MAF shortens it) moved on by the bases of the gap columns the trim left at that edge,
+	// which go with their gap.  *id: the last id given (the file's ids count from 1 in output order); a block left without a
+	// segment prints nothing and takes none.  r is not changed: the trim is read off the untrimmed last record, so the call goes IN FRONT of maf_text / paf_text / aln,
+	// which shorten it -- once.
+	void chain_text(const QueryContig &q, const ContigResult &r, const gsa_seg_block *blk, const gsa_seg *seg, int64_t *id, const std::function<void(OutBuf &&)> &sink) const;
+	void chain(FILE *fp, const QueryContig &q, const ContigResult &r, const gsa_seg_block *blk, const gsa_seg *seg, int64_t *id) const;
 	// OutputAlignment (tools.cpp:222-286)
 	void aln(FILE *fp, const QueryContig &q, ContigResult &r) const;
 	// OutputDotplot (DotPloting.cpp:10-71): gnuplot script `gp_path` + one data file per plotted reference sequence

@@ -121,7 +121,7 @@ int gsah_c_emit(const char *index_prefix, const char *query_fa, const char *maf_
 }
 
 static int emit_impl(const char *index_prefix, const char *query_fa, const char *maf_path, const char *vcf_path, const char *reference_label,
-                     int allow_dup, int fmt, bool with_cs, gsah_result_cb cb, void *user, char *err);
+                     int allow_dup, int fmt, bool with_cs, gsah_result_cb cb, void *user, char *err, const char *chain_path = nullptr);
 
 // fmt 1: MAF (OutputMAF), fmt 2: ALN (OutputAlignment) -- the -fmt flag of the CLI (main.cpp:284); fmt 3: PAF, the CIGARs from the host comparator (gsah_block_cigars)
 int gsah_c_emit_fmt(const char *index_prefix, const char *query_fa, const char *maf_path, const char *vcf_path, const char *reference_label,
@@ -137,17 +137,29 @@ int gsah_c_emit_paf_cs(const char *index_prefix, const char *query_fa, const cha
 	return emit_impl(index_prefix, query_fa, paf_path, vcf_path, reference_label, allow_dup, 3, true, cb, user, err);
 }
 
+// any of those with a UCSC chain file beside it (the -chain flag of the CLI): triples from the host comparator (gsah_block_segs), cut and printed by Emitter::chain
+int gsah_c_emit_chain(const char *index_prefix, const char *query_fa, const char *maf_path, const char *vcf_path, const char *reference_label,
+                      int allow_dup, int fmt, int with_cs, const char *chain_path, gsah_result_cb cb, void *user, char *err)
+{
+	if (!chain_path) return -1;
+	return emit_impl(index_prefix, query_fa, maf_path, vcf_path, reference_label, allow_dup, fmt, with_cs != 0 && fmt == 3, cb, user, err, chain_path);
+}
+
 static int emit_impl(const char *index_prefix, const char *query_fa, const char *maf_path, const char *vcf_path, const char *reference_label,
-                     int allow_dup, int fmt, bool with_cs, gsah_result_cb cb, void *user, char *err)
+                     int allow_dup, int fmt, bool with_cs, gsah_result_cb cb, void *user, char *err, const char *chain_path)
 {
 	std::string e; HostIndex idx; std::vector<QueryContig> qs;
 	if (!gsah_load_index(index_prefix, idx, e) || !gsah_load_query(query_fa, qs, e)) { if (err) { strncpy(err, e.c_str(), 255); err[255] = 0; } return -1; }
 	Emitter em; em.idx = &idx; em.allow_dup = allow_dup != 0;
+	FILE *chain_fp = nullptr; int64_t chain_id = 0;
+	if (chain_path && !(chain_fp = fopen(chain_path, "w"))) { if (err) strcpy(err, "cannot open chain output"); return -3; }
+	struct Closer { FILE *&f; ~Closer() { if (f) fclose(f); } } closer = { chain_fp };
 	for (size_t ci = 0; ci < qs.size(); ci++) {
 		gsa_result res; memset(&res, 0, sizeof(res));
 		if (cb(user, (int)ci, qs[ci].seq.data(), (int)qs[ci].seq.size(), &res) != 0) { if (err) strcpy(err, "result callback failed"); return -2; }
 		if (res.n_blocks == 0) continue;                         // GSAlign.cpp:541
 		ContigResult cr; cr.assign(res);
+		if (chain_fp) em.chain(chain_fp, qs[ci], cr, nullptr, nullptr, &chain_id);      // (in front of the emitters that shorten a block's last record)
 		FILE *fp = fopen(maf_path, ci == 0 ? "w" : "a");         // tools.cpp:158-163
 		if (!fp) { if (err) strcpy(err, "cannot open MAF output"); return -3; }
 		if (fmt == 3 && with_cs) {
@@ -267,6 +279,31 @@ long long gsah_c_cs_trim(const char *cs, long long n, const uint32_t *ops, long 
 	gsah_cs_trim(cs, n, ops, n_ops, bdir, ext, o);
 	if (o.size() > (size_t)n) return -2;
 	if (!o.empty()) memcpy(out, o.data(), o.size());
+	return (long long)o.size();
+}
+
+// The chain triples of every block of one finished contig (gsa_seg_block / gsa_seg, gsa_hip.h), on the host, from the gapped strings and seed records, untrimmed: what
+// gsa_block_segs gives.  blk[res->n_blocks] is always filled; seg[cap]; returns the number of triples (call with cap = 0 to size `seg`), < 0 on error.  Needs no index.
+long long gsah_c_segs(const gsa_result *res, gsa_seg_block *blk, gsa_seg *seg, long long cap)
+{
+	if (!res || (res->n_blocks > 0 && !blk) || (cap > 0 && !seg)) return -1;
+	ContigResult cr; cr.assign(*res);
+	std::vector<gsa_seg_block> b; std::vector<gsa_seg> o;
+	gsah_block_segs(cr, b, o);
+	if (!b.empty()) memcpy(blk, b.data(), b.size() * sizeof(gsa_seg_block));
+	const size_t m = std::min<size_t>(o.size(), cap > 0 ? (size_t)cap : 0);
+	if (m) memcpy(seg, o.data(), m * sizeof(gsa_seg));
+	return (long long)o.size();
+}
+
+// gsah_segs_trim on one block's triples segs[n]: out[n] receives the triples that stay; returns their number
+long long gsah_c_segs_trim(const gsa_seg *segs, long long n, int bdir, long long ext, gsa_seg *out)
+{
+	if (n < 0 || (n > 0 && (!segs || !out))) return -1;
+	std::vector<gsa_seg> o;
+	gsah_segs_trim(segs, n, bdir, ext, o);
+	if (o.size() > (size_t)n) return -2;
+	if (!o.empty()) memcpy(out, o.data(), o.size() * sizeof(gsa_seg));
 	return (long long)o.size();
 }
 

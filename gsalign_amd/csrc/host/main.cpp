@@ -9,7 +9,8 @@
 // parsed (gsah_reference_from_fasta) and the first GPU's context is made from its .pac bytes in device memory (gsa_create_from_pac).  -lift FILE: the reference positions
 // listed in FILE (name, 1-based position; a VCF works as it is) are carried through every contig's alignment on the GPU (gsa_lift) and written to <prefix>.lift.tsv.
 // -track W: the reference sequences in windows of W bases -- covered, matching, mismatching, deleted and inserted bases per window and query contig, computed on the GPU
-// (gsa_ref_track) and written to <prefix>.track.tsv.
+// (gsa_ref_track) and written to <prefix>.track.tsv.  -chain: every alignment as a UCSC chain (for liftOver, CrossMap, bcftools +liftover), its size / dt / dq lines
+// computed on the GPU (gsa_block_segs) and written to <prefix>.chain.
 // The contigs go through gsa_align_many (the per-contig loop of GSAlign.cpp:483-548).  Round 5: a GPU worker thread only COPIES a finished
 // contig out of the library's memory; ONE formatter thread takes the contigs in contig order (OutputMAF appends per contig, VarVec grows in
 // contig order: GSAlign.cpp:543-546) and formats each with the host pool's threads (par.h: the text lines of a block, the variants of a
@@ -56,6 +57,7 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -cs            with -fmt 3: add the cs:Z: difference string (short form) of every alignment, computed on the GPU (gsa_block_cs) [false]\n");
 	fprintf(stderr, "         -lift  FILE    lift the reference positions of FILE (tab-separated: sequence name, 1-based position; '#' lines skipped, a VCF works) to the query on the GPU (gsa_lift): <prefix>.lift.tsv\n");
 	fprintf(stderr, "         -track INT     per window of INT reference bases and query sequence: covered / matching / mismatching / deleted / inserted bases, computed on the GPU (gsa_ref_track): <prefix>.track.tsv\n");
+	fprintf(stderr, "         -chain         write every alignment as a UCSC chain (liftOver, CrossMap), its segments computed on the GPU (gsa_block_segs): <prefix>.chain [false]\n");
 	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
 	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index), references up to 1.07 Gbp [false]\n", prog);
 	fprintf(stderr, "         -memindex      with -r: build the index in GPU memory (gsa_create_from_pac) and align against it; no index file is written or read, references up to 1.07 Gbp [false]\n\n");
@@ -137,7 +139,7 @@ int main(int argc, char *argv[])
 	//  kernel and faulting it in again for the next contig)
 	mallopt(M_MMAP_THRESHOLD, 1 << 30); mallopt(M_TRIM_THRESHOLD, 1 << 30); mallopt(M_TOP_PAD, 256 << 20);
 	gsa_params prm; gsa_default_params(&prm);
-	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, want_cs = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
+	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, want_cs = false, want_chain = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
 	std::vector<int> gpus;
 	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL, *lift_file = NULL;
 	int track_w = 0;      // -track W (0: no track)
@@ -171,6 +173,7 @@ int main(int argc, char *argv[])
 		else if (a == "-timing") timing = true;
 		else if (a == "-gpuvar") gpuvar = true;
 		else if (a == "-cs") want_cs = true;
+		else if (a == "-chain") want_chain = true;
 		else if (a == "-lift" && i + 1 < argc) lift_file = argv[++i];
 		else if (a == "-track" && i + 1 < argc) {
 			char *end = NULL; const long long w = strtoll(argv[++i], &end, 10);
@@ -312,7 +315,7 @@ int main(int argc, char *argv[])
 	if (track_w) for (gsa_ctx *c : ctxs) if (gsa_track_set(c, track_w) != GSA_OK) { fprintf(stderr, "-track: %s\n", gsa_last_error(c)); return 2; }
 	if (want_lift) for (gsa_ctx *c : ctxs) if (gsa_lift_set(c, lift_pos.data(), (int64_t)lift_pos.size()) != GSA_OK) { fprintf(stderr, "-lift: %s\n", gsa_last_error(c)); return 2; }
 
-	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv", trackn = std::string(out_prefix) + ".track.tsv";
+	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv", trackn = std::string(out_prefix) + ".track.tsv", chainn = std::string(out_prefix) + ".chain";
 	Emitter em; em.idx = &idx; em.allow_dup = allow_dup;
 	long long n_aln = 0, tot_len = 0, tot_match = 0, n_dup = 0;
 	fprintf(stderr, "Step2. Sequence analysis for all query chromosomes\n");
@@ -325,12 +328,14 @@ int main(int argc, char *argv[])
 	struct Sink {
 		std::mutex mu; std::condition_variable cv; std::vector<ContigResult> res; std::vector<char> ready; bool abort = false; double copy_s = 0;
 		std::vector<RawArr<gsa_variant> > var;      // -gpuvar: the contig's variants as gsa_call_variants left them
-		std::vector<RawArr<gsa_block_cigar> > cblk; std::vector<RawArr<uint32_t> > cops;      // -fmt 3: the contig's CIGARs as gsa_block_cigars left them
+		bool want_cig = false; std::vector<RawArr<gsa_block_cigar> > cblk; std::vector<RawArr<uint32_t> > cops;      // -fmt 3: the contig's CIGARs as gsa_block_cigars left them
 		std::vector<RawArr<gsa_cs_block> > sblk; std::vector<RawArr<char> > sbytes; bool want_cs = false;      // -cs: the contig's cs strings as gsa_block_cs left them
 		std::vector<RawArr<gsa_lift_hit> > lift; bool want_lift = false;      // -lift: the contig's hits as gsa_lift left them
 		std::vector<RawArr<gsa_track_win> > track; bool want_track = false;   // -track: the contig's windows as gsa_ref_track left them
+		std::vector<RawArr<gsa_seg_block> > gblk; std::vector<RawArr<gsa_seg> > gseg; bool want_segs = false;   // -chain: the contig's triples as gsa_block_segs left them
 	} sink;
-	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size()); sink.sblk.resize(qs.size()); sink.sbytes.resize(qs.size()); sink.want_cs = want_cs; sink.lift.resize(qs.size()); sink.want_lift = want_lift; sink.track.resize(qs.size()); sink.want_track = track_w != 0;
+	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size()); sink.sblk.resize(qs.size()); sink.sbytes.resize(qs.size()); sink.want_cs = want_cs; sink.want_cig = fmt == 3; sink.lift.resize(qs.size()); sink.want_lift = want_lift; sink.track.resize(qs.size()); sink.want_track = track_w != 0;
+	sink.gblk.resize(qs.size()); sink.gseg.resize(qs.size()); sink.want_segs = want_chain;
 	const bool var_on_gpu = gpuvar && vcf;          // (-no_vcf: nobody reads the variants)
 	// the MAF file: created by the first contig that has alignments ("w" for contig 0, "a" afterwards: tools.cpp:158-163 -- a run whose
 	// first contig aligns nowhere appends to whatever the file held, as the reference does)
@@ -341,8 +346,15 @@ int main(int argc, char *argv[])
 	if (want_lift && !(lift_fp = fopen(liftn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", liftn.c_str(), strerror(errno)); }
 	FILE *track_fp = NULL;
 	if (track_w && !(track_fp = fopen(trackn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", trackn.c_str(), strerror(errno)); }
+	FILE *chain_fp = NULL; int64_t chain_id = 0;
+	if (want_chain && !(chain_fp = fopen(chainn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", chainn.c_str(), strerror(errno)); }
 	auto write_contig = [&](size_t ci, ContigResult &cr) {
 		fprintf(stderr, "\tProcess query chromsomoe: %s...\n", qs[ci].name.c_str());
+		if (chain_fp) {      // (in front of the emitters that shorten a block's last record: the chain reads the trim off the untrimmed one and changes nothing; never the host comparator in place of a missing device answer)
+			if (sink.gblk[ci].size() != cr.blocks.size()) { if (!cr.blocks.empty()) { out_failed = true; fprintf(stderr, "Error! %d blocks, chain segments of %d\n", (int)cr.blocks.size(), (int)sink.gblk[ci].size()); } }
+			else if (!cr.blocks.empty()) em.chain_text(qs[ci], cr, sink.gblk[ci].data(), sink.gseg[ci].data(), &chain_id, [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, chain_fp) != o.n) out_failed = true; });
+			sink.gblk[ci].reset(); sink.gseg[ci].reset();
+		}
 		if (track_fp) {      // (query contigs in file order, a contig's windows ascending; a contig without alignments has none)
 			em.track_text(ci == 0, qs[ci], sink.track[ci].data(), (int64_t)sink.track[ci].size(), [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, track_fp) != o.n) out_failed = true; });
 			sink.track[ci].reset();
@@ -433,7 +445,7 @@ int main(int argc, char *argv[])
 		const double t = now_s();
 		sk.res[(size_t)ci].assign(*res);
 		if (ex->var) sk.var[(size_t)ci].assign(ex->var->v, (size_t)ex->var->n);
-		if (ex->cig) { sk.cblk[(size_t)ci].assign(ex->cig->blk, (size_t)ex->cig->n_blocks); sk.cops[(size_t)ci].assign(ex->cig->ops, (size_t)ex->cig->n_ops); }
+		if (ex->cig && sk.want_cig) { sk.cblk[(size_t)ci].assign(ex->cig->blk, (size_t)ex->cig->n_blocks); sk.cops[(size_t)ci].assign(ex->cig->ops, (size_t)ex->cig->n_ops); }
 		if (sk.want_cs) {
 			gsa_cs cs;
 			if (gsa_extras_cs(ex, &cs) != GSA_OK) return 1;
@@ -443,6 +455,11 @@ int main(int argc, char *argv[])
 			gsa_lifts lf;
 			if (gsa_extras_lift(ex, &lf) != GSA_OK) return 1;
 			sk.lift[(size_t)ci].assign(lf.hits, (size_t)lf.n_hits);
+		}
+		if (sk.want_segs) {
+			gsa_segs sg;
+			if (gsa_extras_segs(ex, &sg) != GSA_OK) return 1;
+			sk.gblk[(size_t)ci].assign(sg.blk, (size_t)sg.n_blocks); sk.gseg[(size_t)ci].assign(sg.seg, (size_t)sg.n_segs);
 		}
 		if (sk.want_track) {
 			gsa_tracks tk;
@@ -456,7 +473,7 @@ int main(int argc, char *argv[])
 	};
 	if (timing && var_on_gpu) for (gsa_ctx *c : ctxs) (void)gsa_set_profiling(c, 8);      // (the variant passes' device time, for the GSA_VARIANT_PASS line)
 	const double ta = now_s(); t_at_align = ta - T0;
-	const int rc_many = (fmt == 3 || want_lift || track_w) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u), on_result_ex, &sink)
+	const int rc_many = (fmt == 3 || want_lift || track_w || want_chain) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u) | (want_chain ? GSA_WANT_SEGS : 0u), on_result_ex, &sink)
 	                  : var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
 	                               : gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
 	t_align = now_s() - ta;
@@ -466,6 +483,7 @@ int main(int argc, char *argv[])
 	double cs_ms = 0;         // -cs: the same of gsa_block_cs (which runs the CIGAR walk itself: cigar_s is 0 then)
 	double lift_ms = 0;       // -lift: the same of gsa_lift
 	double track_ms = 0;      // -track: the same of gsa_ref_track
+	double chain_ms = 0;      // -chain: the same of gsa_block_segs (its CIGAR walk included unless -cs ran it)
 	double var_dev_ms = 0; long long var_dev_n = 0;      // -gpuvar: device time of the variant passes (hipEvents), all contexts
 	double wall_sum[10] = { 0 }; double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 	for (gsa_ctx *c : ctxs) {
@@ -474,6 +492,7 @@ int main(int argc, char *argv[])
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_cs_timing(c, &cm, &cn) == GSA_OK) cs_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_lift_timing(c, &cm, &cn) == GSA_OK) lift_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_track_timing(c, &cm, &cn) == GSA_OK) track_ms += cm; }
+		{ double cm = 0; int64_t cn = 0; if (gsa_get_seg_timing(c, &cm, &cn) == GSA_OK) chain_ms += cm; }
 		double vm = 0; int64_t vn = 0; if (gsa_get_variant_timing(c, &vm, &vn) == GSA_OK) { var_dev_ms += vm; var_dev_n += vn; }
 		double am = 0; int64_t an = 0, ab = 0; if (gsa_get_alloc_stats(c, &am, &an, &ab) == GSA_OK) { alloc_ms += am; alloc_n += an; alloc_bytes += ab; }
 	}
@@ -486,6 +505,7 @@ int main(int argc, char *argv[])
 	formatter.join();
 	if (lift_fp) { if (ferror(lift_fp) | fclose(lift_fp)) out_failed = true; lift_fp = NULL; }
 	if (track_fp) { if (ferror(track_fp) | fclose(track_fp)) out_failed = true; track_fp = NULL; }
+	if (chain_fp) { if (ferror(chain_fp) | fclose(chain_fp)) out_failed = true; chain_fp = NULL; }
 	double maf_write_s = 0; unsigned long long maf_bytes = 0;
 	// (the MAF writer still has its queue to write -- ~1 s at human scale: the VCF is sorted, formatted and written beside it, the MAF file is closed behind)
 	auto close_maf = [&] {
@@ -524,10 +544,10 @@ int main(int argc, char *argv[])
 		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, \"cigar_s\": %.3f, "
 		        "\"result_copy_s_sum\": %.3f, \"maf_format_s\": %.3f, \"variants_s\": %.3f, \"output_drain_after_align_s\": %.3f, \"maf_write_s\": %.3f, \"maf_bytes\": %llu, "
 		        "\"vcf_s\": %.3f, \"vcf_write_s\": %.3f, \"vcf_bytes\": %llu, \"destroy_s\": %.3f, \"host_threads\": %d, \"contexts\": %d, \"query_bp\": %lld, \"contigs\": %d, \"gbp_per_s_excl_index_build\": %.4f, "
-		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
+		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"chain_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
 		        total, t_build, t_index, t_create, t_query, t_pin, t_align, cigar_ms / 1e3, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
-		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
+		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, chain_ms / 1e3, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
 	}
 	if (timing && var_on_gpu) fprintf(stderr, "GSA_VARIANT_PASS {\"device_ms_sum\": %.3f, \"passes\": %lld, \"query_bp\": %lld}\n", var_dev_ms, var_dev_n, [&] { long long b = 0; for (const QueryContig &q : qs) b += (long long)q.seq.size(); return b; }());
 	// (everything is on disk and the GPU is released: the process ends here -- unwinding 20 GB of host buffers and the HIP runtime's own

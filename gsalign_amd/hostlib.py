@@ -115,16 +115,19 @@ def result_from_dump(d: dict, keep: list):
     return r
 
 
-def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, reference_label: str, per_contig, allow_dup: bool = True, fmt: int = 1, summary: bool = False, cs: bool = False) -> None:
+def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, reference_label: str, per_contig, allow_dup: bool = True, fmt: int = 1, summary: bool = False, cs: bool = False, chain: str = None) -> None:
     """per_contig(ci, seq_uint8) -> dump dict of the finished contig (stage 8 layout).  fmt 1 = MAF, 2 = ALN, 3 = PAF with the host comparator's CIGARs (written to maf_path).
     summary=True (fmt 3 only; gsah_c_emit_summary): the PAF is formatted from a summary result -- blocks and block ends, taken out of the full dump, with the
     comparator's CIGARs -- and no VCF is written (vcf_path is not opened).
-    cs=True (fmt 3 only; gsah_c_emit_paf_cs): every line also gets the cs:Z: field, from the host comparator gsah_block_cs."""
+    cs=True (fmt 3 only; gsah_c_emit_paf_cs): every line also gets the cs:Z: field, from the host comparator gsah_block_cs.
+    chain=path (not with summary=True; gsah_c_emit_chain): a UCSC chain file is written there beside the other files, its triples from the host comparator gsah_block_segs."""
     keep: list = []
     if cs and (fmt != 3 or summary):
         raise ValueError("cs=True goes with fmt=3 (and not with summary=True)")
     if summary and fmt != 3:
         raise ValueError("summary=True formats PAF only (fmt=3)")
+    if chain is not None and summary:
+        raise ValueError("chain= needs the records and strings a summary result does not hold")
 
     def cb(user, ci, seq, ln, out):
         s = np.frombuffer(C.string_at(seq, ln), dtype=np.uint8)
@@ -137,6 +140,12 @@ def emit(index_prefix: str, query_fa: str, maf_path: str, vcf_path: str, referen
         rc = load().gsah_c_emit_summary(index_prefix.encode(), query_fa.encode(), maf_path.encode(), 1 if allow_dup else 0, RESULT_CB(cb), None, err)
         if rc != 0:
             raise RuntimeError(f"gsah_c_emit_summary -> {rc}: {err.value.decode()}")
+        return
+    if chain is not None:
+        rc = load().gsah_c_emit_chain(index_prefix.encode(), query_fa.encode(), maf_path.encode(), vcf_path.encode(), reference_label.encode(), 1 if allow_dup else 0, int(fmt), 1 if cs else 0,
+                                      chain.encode(), RESULT_CB(cb), None, err)
+        if rc != 0:
+            raise RuntimeError(f"gsah_c_emit_chain -> {rc}: {err.value.decode()}")
         return
     if cs:
         rc = load().gsah_c_emit_paf_cs(index_prefix.encode(), query_fa.encode(), maf_path.encode(), vcf_path.encode(), reference_label.encode(), 1 if allow_dup else 0, RESULT_CB(cb), None, err)
@@ -301,6 +310,41 @@ def track(index_prefix, seq, result, W: int):
         if n2 != n:
             raise RuntimeError(f"gsah_c_track -> {n2} after {n}")
     return T
+
+
+def segs(index_prefix, seq, result):
+    """gsah_c_segs: the chain triples of every block of one finished contig on the host, from the gapped strings and seed records, untrimmed -- what Aligner.block_segs
+    computes on the GPU.  result: a capi.Result, a dump dict (oracle layout) or a result dict of capi.Aligner.  index_prefix and seq are not needed by the walk and may be
+    None (kept for symmetry with cigars()).  Returns (SEG_BLOCK_DT array, SEG_DT array); block b's triples are seg[seg_off : seg_off + n_seg]."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    lib = load()
+    lib.gsah_c_segs.restype = C.c_longlong
+    lib.gsah_c_segs.argtypes = [C.POINTER(capi.Result), C.c_void_p, C.c_void_p, C.c_longlong]
+    blk = np.zeros(int(result.n_blocks), capi.SEG_BLOCK_DT)
+    n = lib.gsah_c_segs(C.byref(result), C.c_void_p(blk.ctypes.data), None, 0)
+    if n < 0:
+        raise RuntimeError(f"gsah_c_segs -> {n}")
+    sg = np.zeros(int(n), capi.SEG_DT)
+    if n:
+        n2 = lib.gsah_c_segs(C.byref(result), C.c_void_p(blk.ctypes.data), C.c_void_p(sg.ctypes.data), n)
+        assert n2 == n
+    return blk, sg
+
+
+def segs_trim(triples, bdir: bool, ext: int):
+    """gsah_c_segs_trim: iExtension's trim on ONE block's triples (output order) -- the last `ext` columns in walk order go, and a gap the cut falls into or ends at goes
+    whole.  Returns the SEG_DT array that stays (its last triple with dt = dq = 0)."""
+    t = np.ascontiguousarray(triples, dtype=capi.SEG_DT)
+    out = np.zeros(max(t.size, 1), capi.SEG_DT)
+    lib = load()
+    lib.gsah_c_segs_trim.restype = C.c_longlong
+    lib.gsah_c_segs_trim.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_longlong, C.c_void_p]
+    n = lib.gsah_c_segs_trim(C.c_void_p(t.ctypes.data), int(t.size), 1 if bdir else 0, int(ext), C.c_void_p(out.ctypes.data))
+    if n < 0:
+        raise RuntimeError(f"gsah_c_segs_trim -> {n}")
+    return out[:n].copy()
 
 
 def cs_trim(cs_bytes, ops, bdir: bool, ext: int) -> bytes:

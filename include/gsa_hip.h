@@ -461,14 +461,42 @@ int gsa_ref_track(gsa_ctx *ctx, int32_t k, gsa_tracks *out);
 /* measurement: host wall time the calling threads spent inside gsa_ref_track on this context since it was created, and the number of calls.  Always on. */
 int gsa_get_track_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 
+/* ---- per-block chain segments (UCSC chain files, for liftOver / CrossMap / bcftools +liftover) --------------
+ * ("Chain" already names the seed-chaining stage of this library: the word for the new thing is SEGS.)
+ * For every block of gsa_result::blocks take its columns in OUTPUT order -- the order in which gsa_block_cigars delivers ops: reference-forward, so a
+ * reverse-strand block is taken back to front.
+ *   aligned column   CIGAR class '=' or 'X'
+ *   gap column       class 'I' or 'D'
+ *   segment          a maximal run of aligned columns
+ *   gap              the gap columns between two segments: dt counts its D columns (reference bases facing '-'), dq its I columns (query bases facing '-').
+ *                    Both may be non-zero (an I run that touches a D run), never both zero.
+ * A block with n segments gives n triples {size, dt, dq}, the gap being the one BEHIND the segment in output order; the last triple has dt = dq = 0.  These
+ * are the data lines of a chain.  Like the CIGAR and cs answers this one is UNTRIMMED: the iExtension trim is the emitter's business (gsah_segs_trim in
+ * libgsa_host.so cuts triples).  An untrimmed block starts and ends with a seed, so with a segment; a block without records gives no segment.
+ * blk[b] = where block b's triples lie in `seg` and how many there are. */
+typedef struct { int32_t size, dt, dq; } gsa_seg;                                  /* 12 bytes */
+typedef struct { int64_t seg_off; int32_t n_seg; int32_t _pad; } gsa_seg_block;   /* 16 bytes; one per block of gsa_result::blocks, same order */
+typedef struct { int32_t n_blocks; int64_t n_segs; const gsa_seg_block *blk; const gsa_seg *seg; } gsa_segs;   /* 32 bytes */
+/* The triples of ALL blocks of the stage-8 result the context holds, duplicates included (the caller filters).  Validity, call order, k and the error codes are
+ * those of gsa_block_cigars: before stage 8, or after a prefetch has overwritten the contig, GSA_ERR_STATE; k out of range GSA_ERR_ARG; no blocks: n_blocks = 0.
+ * The call runs the CIGAR walk itself (its errors pass through) and then four launches at run granularity -- no column is looked at twice.  2^31 - 256 segments
+ * or more: GSA_ERR_LIMIT.  The answer lives in buffers of its own: gsa_block_cigars, gsa_block_cs, gsa_call_variants, gsa_lift and gsa_ref_track return what
+ * they returned before, and so does this call after one of them.  Memory is owned by the context and valid until the next call on it; block table and triples
+ * come home in one copy each into pinned memory.  Device memory: 4 bytes per CIGAR op + 32 per segment. */
+int gsa_block_segs(gsa_ctx *ctx, int32_t k, gsa_segs *out);
+/* measurement: host wall time the calling threads spent inside gsa_block_segs on this context since it was created (its CIGAR pass included), and the
+ * number of calls.  Always on. */
+int gsa_get_seg_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+
 /* gsa_align_many with optional passes run by the worker in front of the callback -- before the prefetch after next can touch the contig's
- * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track).  *ex and what it
+ * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track) | GSA_WANT_SEGS (gsa_block_segs).  *ex and what it
  * points to are valid during the callback only, like *res. */
 #define GSA_WANT_VARIANTS 1u
 #define GSA_WANT_CIGARS   2u
 #define GSA_WANT_CS       4u   /* gsa_block_cs; implies GSA_WANT_CIGARS */
 #define GSA_WANT_LIFT     16u  /* gsa_lift of every contig; every context of ctx[] must hold positions (gsa_lift_set), else GSA_ERR_STATE before any contig is aligned */
 #define GSA_WANT_TRACK    32u  /* gsa_ref_track of every contig; every context of ctx[] must hold a window (gsa_track_set), else GSA_ERR_STATE before any contig is aligned */
+#define GSA_WANT_SEGS     64u  /* gsa_block_segs; implies GSA_WANT_CIGARS */
 typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;   /* NULL where not asked for */
 /* The contig's cs strings inside the callback of gsa_align_many_ex: the library hands the callback a LARGER object whose head is the gsa_extras
  * (which keeps its two members and its 16 bytes), and this call reaches what lies behind it -- so it is valid for the `ex` the library passed
@@ -478,6 +506,8 @@ int gsa_extras_cs(const gsa_extras *ex, gsa_cs *out);
 int gsa_extras_lift(const gsa_extras *ex, gsa_lifts *out);
 /* The contig's track inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_TRACK was not asked for). */
 int gsa_extras_track(const gsa_extras *ex, gsa_tracks *out);
+/* The contig's chain segments inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_SEGS was not asked for). */
+int gsa_extras_segs(const gsa_extras *ex, gsa_segs *out);
 typedef int (*gsa_result_ex_fn)(void *user, int32_t contig, const gsa_result *res, const gsa_extras *ex);
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
                       uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user);
