@@ -27,6 +27,7 @@ EXPORTS = [
     "gsa_lift_set", "gsa_lift", "gsa_get_lift_timing", "gsa_extras_lift",
     "gsa_track_set", "gsa_ref_track", "gsa_get_track_timing", "gsa_extras_track",
     "gsa_block_segs", "gsa_get_seg_timing", "gsa_extras_segs",
+    "gsa_proj_open", "gsa_proj_close", "gsa_proj_clear", "gsa_project", "gsa_proj_fetch", "gsa_proj_merge", "gsa_get_proj_timing",
     "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
     "gsa_create_from_pac", "gsa_export_index_table",
 ]
@@ -168,7 +169,14 @@ LIFT_HIT_DT = np.dtype([("idx", "<i4"), ("qpos", "<i4"), ("block", "<i4"), ("cls
 BLOCK_CS_DT = np.dtype([("cs_off", "<i8"), ("n_cs", "<i4"), ("_pad", "<i4")])
 BLOCK_CIGAR_DT = np.dtype([("cig_off", "<i8"), ("n_cig", "<i4"), ("n_eq", "<i4"), ("n_x", "<i4"), ("n_ins", "<i4"), ("n_del", "<i4"), ("_pad", "<i4")])
 CIGAR_LETTERS = "MIDNSHP=X"      # by BAM op code; the library writes I (1), D (2), = (7) and X (8)
-WANT_VARIANTS, WANT_CIGARS, WANT_CS, WANT_LIFT, WANT_TRACK, WANT_SEGS = 1, 2, 4, 16, 32, 64
+WANT_VARIANTS, WANT_CIGARS, WANT_CS, WANT_LIFT, WANT_TRACK, WANT_SEGS, WANT_PROJ = 1, 2, 4, 16, 32, 64, 128
+PROJ_NO_DUP = 1
+PROJ_LETTERS = "nACGTN-"         # by the low three bits of an accumulator word (0: uncovered)
+
+
+class ProjStat(C.Structure):
+    """gsa_proj_stat, 16 bytes (include/gsa_hip.h): blocks painted, words offered."""
+    _fields_ = [("n_blocks", C.c_int32), ("_pad", C.c_int32), ("n_cols", C.c_int64)]
 
 
 def lifts_array(l: "Lifts"):
@@ -366,7 +374,7 @@ class DeviceContig:
             self.lib.gsa_device_free(self.device, C.c_void_p(self.ptr)); self.ptr = None
 
 
-def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False, track: bool = False, segs: bool = False) -> None:
+def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False, track: bool = False, segs: bool = False, proj: bool = False) -> None:
     """gsa_align_many: `contigs` (uint8 arrays, or DeviceContig objects -- all of one kind) on the given contexts, one host
     thread per context inside the library.  on_result(contig_index, Result) runs on the worker threads (the Result is valid
     during the call only).  in_order: hand the contigs out as listed (GSA_MANY_IN_ORDER) instead of longest first.
@@ -383,7 +391,9 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     track=True: gsa_align_many_ex with GSA_WANT_TRACK (every aligner holds a window: track_set) -- on_result gets one more argument behind all of those, the contig's
     Tracks (gsa_extras_track; tracks_array copies it out).
     segs=True: gsa_align_many_ex with GSA_WANT_SEGS (it implies the CIGARs) -- on_result gets one more argument behind all of those, the contig's Segs (gsa_extras_segs;
-    segs_arrays copies it out)."""
+    segs_arrays copies it out).
+    proj=True: gsa_align_many_ex with GSA_WANT_PROJ (every aligner holds an accumulator: proj_open) -- the worker paints every contig behind the other passes; on_result
+    gets nothing more.  Some aligners without an accumulator: -4; none with one: -1, like an unknown bit."""
     lib = aligners[0].lib
     n = len(contigs)
     ctxs = (C.c_void_p * len(aligners))(*[a.ctx for a in aligners])
@@ -391,7 +401,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     qs = (C.c_char_p * n)(*[C.cast(c.ptr if on_dev else c.ctypes.data, C.c_char_p) for c in contigs])
     ql = (C.c_int32 * n)(*[int(c.size) for c in contigs])
     flags = (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16)
-    if cigars or cs or lift or track or segs:
+    if cigars or cs or lift or track or segs or proj:
         lib.gsa_extras_cs.argtypes = [C.POINTER(Extras), C.POINTER(Cs)]
         lib.gsa_extras_lift.argtypes = [C.POINTER(Extras), C.POINTER(Lifts)]
         lib.gsa_extras_track.argtypes = [C.POINTER(Extras), C.POINTER(Tracks)]
@@ -427,7 +437,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
             return int((on_result(*args) if on_result else 0) or 0)
         cbx = RESULT_EX_FN(ex_cb)
         lib.gsa_align_many_ex.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.c_uint32, RESULT_EX_FN, C.c_void_p]
-        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0) | (WANT_TRACK if track else 0) | (WANT_SEGS if segs else 0), cbx, None)
+        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0) | (WANT_TRACK if track else 0) | (WANT_SEGS if segs else 0) | (WANT_PROJ if proj else 0), cbx, None)
     elif variants:
         cbv = RESULT_VAR_FN(lambda user, ci, res, var: int((on_result(ci, res.contents, var.contents) if on_result else 0) or 0))
         lib.gsa_align_many_variants.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_VAR_FN, C.c_void_p]
@@ -438,7 +448,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
         rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, flags, cb, None)
     if rc != 0:
         msgs = [lib.gsa_last_error(a.ctx).decode() for a in aligners]
-        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift or track or segs else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
+        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift or track or segs or proj else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
 
 
 def _p(a, t):
@@ -776,6 +786,51 @@ class Aligner:
         ms, n = C.c_double(0), C.c_int64(0)
         self.lib.gsa_get_seg_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         self._ck(self.lib.gsa_get_seg_timing(self.ctx, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    def proj_open(self, share: "Aligner" = None, no_dup: bool = False) -> None:
+        """gsa_proj_open: an accumulator of G words on this context's device (share=None), or the one `share` holds on the same device.  no_dup: GSA_PROJ_NO_DUP."""
+        self.lib.gsa_proj_open.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self._ck(self.lib.gsa_proj_open(self.ctx, share.ctx if share is not None else None, C.c_uint32(PROJ_NO_DUP if no_dup else 0)))
+
+    def proj_close(self) -> None:
+        """gsa_proj_close: this context lets go of its accumulator (the last holder frees it)."""
+        self.lib.gsa_proj_close.argtypes = [C.c_void_p]
+        self._ck(self.lib.gsa_proj_close(self.ctx))
+
+    def proj_clear(self) -> None:
+        """gsa_proj_clear: every word back to 0."""
+        self.lib.gsa_proj_clear.argtypes = [C.c_void_p]
+        self._ck(self.lib.gsa_proj_clear(self.ctx))
+
+    def project(self, k: int = 0):
+        """gsa_project: the stage-8 result this context holds (contig k of a bundle) painted into its accumulator.  Returns (blocks painted, words offered)."""
+        st = ProjStat()
+        self.lib.gsa_project.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ProjStat)]
+        self._ck(self.lib.gsa_project(self.ctx, C.c_int32(k), C.byref(st)))
+        return int(st.n_blocks), int(st.n_cols)
+
+    def proj_fetch(self, p0: int = 0, n: int = None, words: bool = False):
+        """gsa_proj_fetch of positions [p0, p0 + n) (n=None: to the end of the reference): the characters as bytes, or with words=True (bytes, uint32 array)."""
+        n = int(self.idx.G) - int(p0) if n is None else int(n)
+        text = np.zeros(max(n, 1), np.uint8)
+        w = np.zeros(max(n, 1), np.uint32) if words else None
+        self.lib.gsa_proj_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        self._ck(self.lib.gsa_proj_fetch(self.ctx, C.c_int64(p0), C.c_int64(n), C.c_void_p(text.ctypes.data), C.c_void_p(w.ctypes.data) if words else None))
+        t = text[:max(n, 0)].tobytes()
+        return (t, w[:max(n, 0)]) if words else t
+
+    def proj_merge(self, words, p0: int = 0) -> None:
+        """gsa_proj_merge: host words (another device's accumulator, as proj_fetch(words=True) returns them) into positions [p0, p0 + len(words)): the maximum stays."""
+        w = np.ascontiguousarray(words, dtype=np.uint32)
+        self.lib.gsa_proj_merge.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        self._ck(self.lib.gsa_proj_merge(self.ctx, C.c_int64(p0), C.c_int64(w.size), C.c_void_p(w.ctypes.data) if w.size else None))
+
+    def proj_timing(self):
+        """(host wall ms inside gsa_project on this context since it was created, number of calls)."""
+        ms, n = C.c_double(0), C.c_int64(0)
+        self.lib.gsa_get_proj_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        self._ck(self.lib.gsa_get_proj_timing(self.ctx, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
     def cs_timing(self):

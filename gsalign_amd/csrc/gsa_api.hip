@@ -35,9 +35,9 @@ static int rewind_to_hits(gsa_ctx *c)
 	return stage1_restore_pdbm(c);
 }
 
-// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip) ask of the context before they run; `who`: the export, for the messages;
-// need_positions: the pass reads the positions of gsa_lift_set; need_window: the window of gsa_track_set
-static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false, bool need_window = false)
+// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip, k_proj.hip) ask of the context before they run; `who`: the export, for the messages;
+// need_positions: the pass reads the positions of gsa_lift_set; need_window: the window of gsa_track_set; need_acc: it paints into the accumulator of gsa_proj_open
+static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false, bool need_window = false, bool need_acc = false)
 {
 	const std::string w(who);
 	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, w + ": the context holds no finished (stage 8) result");
@@ -46,6 +46,7 @@ static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_p
 	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, w + ": contig index out of range");
 	if (need_positions && c->lift_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no positions (gsa_lift_set first)");
 	if (need_window && c->track_w <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no window (gsa_track_set first)");
+	if (need_acc && !c->proj) return gsa_fail(c, GSA_ERR_STATE, w + ": no accumulator (gsa_proj_open first)");
 	GSA_CHECK(c, hipSetDevice(c->device));
 	return GSA_OK;
 }
@@ -107,6 +108,19 @@ int segs_call(gsa_ctx *c, int32_t k, gsa_segs *out, gsa_cigars *cig, const gsa_c
 	const auto t0 = std::chrono::steady_clock::now();
 	rc = block_segs(c, k, out, cig, have);
 	c->seg_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->seg_calls++;
+	return rc;
+}
+
+// the blocks of the stage-8 result the context holds painted into its accumulator: k_proj.hip
+int proj_call(gsa_ctx *c, int32_t k, gsa_proj_stat *out)
+{
+	if (!c) return GSA_ERR_ARG;
+	if (out) { out->n_blocks = 0; out->_pad = 0; out->n_cols = 0; }
+	int rc = result_pass_ready(c, k, "gsa_project", false, false, true);
+	if (rc) return rc;
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = project_blocks(c, k, out);
+	c->proj_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->proj_calls++;
 	return rc;
 }
 
@@ -328,6 +342,41 @@ int gsa_get_track_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return 
 
 int gsa_block_segs(gsa_ctx *c, int32_t k, gsa_segs *out) { return segs_call(c, k, out, nullptr, nullptr); }
 int gsa_get_seg_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::seg_ms_sum, &gsa_ctx::seg_calls, ms_sum, n_calls); }
+
+int gsa_proj_open(gsa_ctx *c, gsa_ctx *share, uint32_t flags) { return c ? proj_open(c, share, flags) : GSA_ERR_ARG; }
+int gsa_proj_close(gsa_ctx *c)
+{
+	if (!c) return GSA_ERR_ARG;
+	if (!c->proj) return gsa_fail(c, GSA_ERR_STATE, "gsa_proj_close: no accumulator (gsa_proj_open first)");
+	return proj_release(c);
+}
+int gsa_proj_clear(gsa_ctx *c)
+{
+	if (!c) return GSA_ERR_ARG;
+	if (!c->proj) return gsa_fail(c, GSA_ERR_STATE, "gsa_proj_clear: no accumulator (gsa_proj_open first)");
+	return proj_clear(c);
+}
+int gsa_project(gsa_ctx *c, int32_t k, gsa_proj_stat *out) { return proj_call(c, k, out); }
+// (the two range calls share their checks; `who` for the messages)
+static int proj_range_ready(gsa_ctx *c, int64_t p0, int64_t n, const char *who)
+{
+	if (!c) return GSA_ERR_ARG;
+	if (!c->proj) return gsa_fail(c, GSA_ERR_STATE, std::string(who) + ": no accumulator (gsa_proj_open first)");
+	if (n < 0 || p0 < 0 || p0 > c->proj->G || n > c->proj->G - p0) return gsa_fail(c, GSA_ERR_ARG, std::string(who) + ": the range lies outside the reference [0, " + std::to_string((long long)c->proj->G) + ")");
+	return GSA_OK;
+}
+int gsa_proj_fetch(gsa_ctx *c, int64_t p0, int64_t n, char *text, uint32_t *words)
+{
+	if (const int rc = proj_range_ready(c, p0, n, "gsa_proj_fetch")) return rc;
+	return (n == 0 || (!text && !words)) ? GSA_OK : proj_fetch(c, p0, n, text, words);
+}
+int gsa_proj_merge(gsa_ctx *c, int64_t p0, int64_t n, const uint32_t *words)
+{
+	if (const int rc = proj_range_ready(c, p0, n, "gsa_proj_merge")) return rc;
+	if (n == 0) return GSA_OK;
+	return words ? proj_merge(c, p0, n, words) : GSA_ERR_ARG;
+}
+int gsa_get_proj_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::proj_ms_sum, &gsa_ctx::proj_calls, ms_sum, n_calls); }
 
 int gsa_get_wall_sums(gsa_ctx *c, double ms[10], int64_t *n)
 {

@@ -292,6 +292,7 @@ void gsa_destroy(gsa_ctx *c)
 	for (int i = 0; i < 2; i++) slot_wait(c->qs[i]);
 	uploader_stop(c);
 	if (c->lender) c->lender->n_borrowers.fetch_sub(1);      // (`parent` outlives its clones: gsa_hip.h)
+	(void)proj_release(c);      // (its reference to a projection accumulator, if it holds one: the last holder frees the array)
 	// (a gsa_clone context borrows the index through `di` only: its index DevBufs are empty, a presence bitmap it built after
 	//  a parameter change is its own)
 #define X(n) if (c->n.p) hipFree(c->n.p);

@@ -111,6 +111,8 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 			else if (!(sk.want & GSA_WANT_CS) && (sk.want & GSA_WANT_CIGARS)) { const int rcc = gsa_block_cigars(c, k, &cig); if (rcc != GSA_OK) return rcc; ex.cig = &cig; }
 			if (sk.want & GSA_WANT_LIFT) { const int rcl = lift_call(c, k, &lift); if (rcl != GSA_OK) return rcl; full.lift = &lift; }
 			if (sk.want & GSA_WANT_TRACK) { const int rct = track_call(c, k, &trk); if (rct != GSA_OK) return rct; full.track = &trk; }
+			// (the projection paints into the contexts' accumulator and hands the callback nothing)
+			if (sk.want & GSA_WANT_PROJ) { const int rcp = proj_call(c, k, nullptr); if (rcp != GSA_OK) return rcp; }
 			return sk.on_ex(user, ci, res, &ex);
 		}
 		return sk.on_result ? sk.on_result(user, ci, res) : GSA_OK;
@@ -123,6 +125,14 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 	// (GSA_WANT_LIFT: a context without positions would fail its first contig with the others under way)
 	if (sk.want & GSA_WANT_LIFT) for (int k = 0; k < n_ctx; k++) if (ctx[k]->lift_n <= 0) return gsa_fail(ctx[k], GSA_ERR_STATE, "gsa_align_many_ex (GSA_WANT_LIFT): the context holds no positions (gsa_lift_set first)");
 	if (sk.want & GSA_WANT_TRACK) for (int k = 0; k < n_ctx; k++) if (ctx[k]->track_w <= 0) return gsa_fail(ctx[k], GSA_ERR_STATE, "gsa_align_many_ex (GSA_WANT_TRACK): the context holds no window (gsa_track_set first)");
+	// (GSA_WANT_PROJ: the bit exists for callers that have opened an accumulator.  Where NO context of ctx[] holds one it is refused like any bit the call does not know --
+	//  GSA_ERR_ARG, what 128 gave before the pass existed; where some hold one and others do not, the call is half set up: GSA_ERR_STATE.  Either way before any contig is aligned)
+	if (sk.want & GSA_WANT_PROJ) {
+		int held = 0;
+		for (int k = 0; k < n_ctx; k++) if (ctx[k]->proj) held++;
+		if (held == 0) return gsa_fail(ctx[0], GSA_ERR_ARG, "gsa_align_many_ex (GSA_WANT_PROJ): no context holds an accumulator (gsa_proj_open first)");
+		for (int k = 0; k < n_ctx; k++) if (!ctx[k]->proj) return gsa_fail(ctx[k], GSA_ERR_STATE, "gsa_align_many_ex (GSA_WANT_PROJ): the context holds no accumulator (gsa_proj_open first)");
+	}
 	if (n == 0) return GSA_OK;
 	// longest first: with dynamic hand-out this is the longest-processing-time-first rule
 	std::vector<int32_t> order((size_t)n);
@@ -213,7 +223,7 @@ int gsa_align_many_variants(gsa_ctx *const *ctx, int32_t n_ctx, const char *cons
 }
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n, uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user)
 {
-	if (!on_result || (want & ~(uint32_t)(GSA_WANT_VARIANTS | GSA_WANT_CIGARS | GSA_WANT_CS | GSA_WANT_LIFT | GSA_WANT_TRACK | GSA_WANT_SEGS))) return GSA_ERR_ARG;
+	if (!on_result || (want & ~(uint32_t)(GSA_WANT_VARIANTS | GSA_WANT_CIGARS | GSA_WANT_CS | GSA_WANT_LIFT | GSA_WANT_TRACK | GSA_WANT_SEGS | GSA_WANT_PROJ))) return GSA_ERR_ARG;
 	ManySink sk; sk.on_ex = on_result; sk.want = want;
 	return align_many_impl(ctx, n_ctx, query, qlen, n, flags, sk, user);
 }

@@ -831,6 +831,74 @@ void Emitter::track_text(bool first, const QueryContig &q, const gsa_track_win *
 	if (o.n) sink(std::move(o));
 }
 
+// ---- the query projected onto the reference ------------------------------------------------------------------------------------------------
+void gsah_project(const HostIndex &ix, const char *seq, const ContigResult &r, uint32_t flags, uint32_t *words, gsa_proj_stat *stat)
+{
+	if (stat) { stat->n_blocks = 0; stat->_pad = 0; stat->n_cols = 0; }
+	if (r.summary || !words) return;      // (a summary result holds neither records nor strings)
+	std::atomic<int64_t> cols(0);
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		if (b.n_frag <= 0 || (b.bdup != 0 && (flags & GSA_PROJ_NO_DUP))) continue;
+		const gsa_frag first = r.frag(b.frag_off), last = r.frag(b.frag_off + b.n_frag - 1);
+		const int64_t start = first.rpos, end = last.rpos + last.rlen - extension(ix, b, last);
+		if (end <= start) continue;
+		const bool rev = !b.bdir;
+		const uint32_t key = (b.bdup == 0 ? 0x80000000u : 0u) | ((uint32_t)std::min<int64_t>(std::max<int64_t>(b.score, 0), (1 << 28) - 1) << 3);
+		// a range of the block's records; several blocks (and threads) may meet in a word: the maximum is taken atomically
+		auto piece = [&](size_t fb, size_t fe) {
+			int64_t n = 0;
+			auto offer = [&](int64_t t, uint32_t code) {
+				if (t < start || t >= end) return;
+				const int64_t p = rev ? 2 * ix.G - 1 - t : t;
+				if (p < 0 || p >= ix.G) return;
+				const uint32_t v = key | ((rev && code <= 4u) ? 5u - code : code);
+				uint32_t cur = __atomic_load_n(&words[p], __ATOMIC_RELAXED);
+				while (cur < v && !__atomic_compare_exchange_n(&words[p], &cur, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+				n++;
+			};
+			for (size_t k = fb; k < fe; k++) {
+				const gsa_frag f = r.frag(b.frag_off + (int64_t)k);
+				if (f.bseed) { for (int i = 0; i < f.rlen; i++) offer(f.rpos + i, seq ? (uint32_t)nt4((unsigned char)seq[f.qpos + i]) + 1u : 5u); continue; }
+				const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+				int64_t rp = f.rpos;
+				for (int c = 0; c < f.aln_len; c++) {
+					if (x1[c] == '-') continue;      // (an inserted query base has no reference base)
+					offer(rp, x2[c] == '-' ? 6u : (uint32_t)nt4((unsigned char)x2[c]) + 1u);
+					rp++;
+				}
+			}
+			cols.fetch_add(n);
+		};
+		if ((size_t)b.n_frag * 16 >= par_min_bytes()) par_ranges((size_t)b.n_frag, (size_t)1 << 13, piece); else piece(0, (size_t)b.n_frag);
+		if (stat) stat->n_blocks++;
+	}
+	if (stat) stat->n_cols = cols.load();
+}
+
+void gsah_proj_text(const uint32_t *words, int64_t n, char *text)
+{
+	static const char tab[8] = { 'n', 'A', 'C', 'G', 'T', 'N', '-', '?' };
+	auto piece = [&](size_t ib, size_t ie) { for (size_t i = ib; i < ie; i++) text[i] = tab[words[i] & 7u]; };
+	if (n > 0 && (size_t)n * 4 >= par_min_bytes()) par_ranges((size_t)n, (size_t)1 << 16, piece); else if (n > 0) piece(0, (size_t)n);
+}
+
+// <prefix>.proj.fa: '>' + the reference sequence's name, then the sequence's characters (text[0 .. chr_len)) 60 per line
+void Emitter::proj_text(int chr, const char *text, const std::function<void(OutBuf &&)> &sink) const
+{
+	if (chr < 0 || (size_t)chr >= idx->chr_name.size()) return;
+	const std::string &name = idx->chr_name[(size_t)chr];
+	const int64_t len = idx->chr_len[(size_t)chr];
+	OutBuf o;
+	o.reserve((size_t)std::min<int64_t>(len + len / 60 + 2, (int64_t)5 << 20) + name.size() + 2);
+	o.append(">", 1); o.append(name); o.append("\n", 1);
+	for (int64_t at = 0; at < len; at += 60) {
+		o.append(text + at, (size_t)std::min<int64_t>(60, len - at)); o.append("\n", 1);
+		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
+	}
+	if (o.n) sink(std::move(o));
+}
+
 void Emitter::aln(FILE *fp, const QueryContig &q, ContigResult &r) const
 {
 	std::string t1, t2;

@@ -134,6 +134,13 @@ void gsah_lift(const HostIndex &ix, const ContigResult &r, const int64_t *pos, i
 // gsa_result and no GPU context.  win: one record per window with n_cov > 0, ascending by (chr, start); empty for a summary result or W <= 0.
 void gsah_track(const HostIndex &ix, const ContigResult &r, int32_t W, std::vector<gsa_track_win> &win);
 
+// A finished contig painted into the caller's accumulator words[0 .. G) by the contract of gsa_project (gsa_hip.h): trimmed coverage, the CIGAR pass's columns, key | code,
+// the maximum stays (taken atomically: several threads may meet in a word) -- from the records, the two gapped strings and, for the seeds, the query contig seq (NULL: a
+// seed's bases count as 'N').  flags: GSA_PROJ_NO_DUP.  The comparator of gsa_project, and the projection of a host that holds a gsa_result and no GPU context.
+void gsah_project(const HostIndex &ix, const char *seq, const ContigResult &r, uint32_t flags, uint32_t *words, gsa_proj_stat *stat = nullptr);
+// words -> characters (codes 1..6: A C G T N -, word 0: n), n of them, no NUL
+void gsah_proj_text(const uint32_t *words, int64_t n, char *text);
+
 struct OutBuf;                             // par.h
 
 struct Emitter {
@@ -174,6 +181,9 @@ struct Emitter {
 	// which shorten it -- once.
 	void chain_text(const QueryContig &q, const ContigResult &r, const gsa_seg_block *blk, const gsa_seg *seg, int64_t *id, const std::function<void(OutBuf &&)> &sink) const;
 	void chain(FILE *fp, const QueryContig &q, const ContigResult &r, const gsa_seg_block *blk, const gsa_seg *seg, int64_t *id) const;
+	// <prefix>.proj.fa (-proj): one FASTA record of the projected query -- '>' and reference sequence `chr`'s name as the .ann round trip delivers it, then its characters
+	// text[0 .. chr_len) (gsa_proj_fetch / gsah_proj_text of the sequence's positions), 60 per line
+	void proj_text(int chr, const char *text, const std::function<void(OutBuf &&)> &sink) const;
 	// OutputAlignment (tools.cpp:222-286)
 	void aln(FILE *fp, const QueryContig &q, ContigResult &r) const;
 	// OutputDotplot (DotPloting.cpp:10-71): gnuplot script `gp_path` + one data file per plotted reference sequence

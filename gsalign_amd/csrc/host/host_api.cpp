@@ -6,6 +6,7 @@
 #include <cstring>
 #include <mutex>
 #include "gsa_host.h"
+#include "par.h"
 #include "exact_sort.h"
 
 extern "C" {
@@ -345,6 +346,51 @@ long long gsah_c_track(const char *index_prefix, const gsa_result *res, int32_t 
 	const size_t m = std::min<size_t>(w.size(), cap > 0 ? (size_t)cap : 0);
 	if (m) memcpy(out, w.data(), m * sizeof(gsa_track_win));
 	return (long long)w.size();
+}
+
+// gsah_project through the C API: one finished contig painted into words[n_words] (n_words = G of the index), on the host -- what gsa_project paints.  seq: the query
+// contig (its bases stand in the seeds' columns).  stat may be NULL.  Returns 0, < 0 on error (-3: n_words is not the reference's length).  The index of the last
+// prefix stays loaded, behind a lock, as in gsah_c_lift (only its sequence table is read).
+int gsah_c_project(const char *index_prefix, const char *seq, const gsa_result *res, uint32_t flags, uint32_t *words, long long n_words, gsa_proj_stat *stat)
+{
+	static std::mutex mu; static std::string have; static HostIndex *idx = nullptr;
+	std::lock_guard<std::mutex> lock(mu);
+	if (!index_prefix || !res || !words || (flags & ~(uint32_t)GSA_PROJ_NO_DUP)) return -1;
+	if (!idx || have != index_prefix) {
+		delete idx; idx = new HostIndex; have.clear(); std::string e;
+		if (!gsah_load_index(index_prefix, *idx, e)) { delete idx; idx = nullptr; return -2; }
+		have = index_prefix;
+	}
+	if (n_words != idx->G) return -3;
+	ContigResult cr; cr.assign(*res);
+	gsah_project(*idx, seq, cr, flags, words, stat);
+	return 0;
+}
+// gsah_proj_text through the C API
+int gsah_c_proj_text(const uint32_t *words, long long n, char *text)
+{
+	if (n < 0 || (n > 0 && (!words || !text))) return -1;
+	gsah_proj_text(words, n, text);
+	return 0;
+}
+// Emitter::proj_text through the C API: the FASTA text of words[G] for every sequence of the index, as -proj writes it.  out[cap]; returns the number of bytes (call with
+// cap = 0 to size `out`), < 0 on error.
+long long gsah_c_emit_proj(const char *index_prefix, const uint32_t *words, long long n_words, char *out, long long cap)
+{
+	std::string e; HostIndex idx;
+	if (!index_prefix || !words || (cap > 0 && !out)) return -1;
+	if (!gsah_load_index(index_prefix, idx, e)) return -2;
+	if (n_words != idx.G) return -3;
+	Emitter em; em.idx = &idx;
+	std::string all, text;
+	for (size_t c = 0; c < idx.chr_name.size(); c++) {
+		text.resize((size_t)idx.chr_len[c]);
+		gsah_proj_text(words + idx.chr_fwd[c], idx.chr_len[c], &text[0]);
+		em.proj_text((int)c, text.data(), [&](OutBuf &&o) { all.append(o.p, o.n); });
+	}
+	const size_t m = std::min<size_t>(all.size(), cap > 0 ? (size_t)cap : 0);
+	if (m) memcpy(out, all.data(), m);
+	return (long long)all.size();
 }
 
 // OutputDotplot for one contig: script + data files (no gnuplot run).  Returns 1 if something was written.

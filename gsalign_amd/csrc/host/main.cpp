@@ -9,7 +9,8 @@
 // parsed (gsah_reference_from_fasta) and the first GPU's context is made from its .pac bytes in device memory (gsa_create_from_pac).  -lift FILE: the reference positions
 // listed in FILE (name, 1-based position; a VCF works as it is) are carried through every contig's alignment on the GPU (gsa_lift) and written to <prefix>.lift.tsv.
 // -track W: the reference sequences in windows of W bases -- covered, matching, mismatching, deleted and inserted bases per window and query contig, computed on the GPU
-// (gsa_ref_track) and written to <prefix>.track.tsv.  -chain: every alignment as a UCSC chain (for liftOver, CrossMap, bcftools +liftover), its size / dt / dq lines
+// (gsa_ref_track) and written to <prefix>.track.tsv.  -proj: the query in reference coordinates -- one character per reference base over all
+// query contigs, painted on the GPU into one accumulator per device (gsa_project) and written to <prefix>.proj.fa.  -chain: every alignment as a UCSC chain (for liftOver, CrossMap, bcftools +liftover), its size / dt / dq lines
 // computed on the GPU (gsa_block_segs) and written to <prefix>.chain.
 // The contigs go through gsa_align_many (the per-contig loop of GSAlign.cpp:483-548).  Round 5: a GPU worker thread only COPIES a finished
 // contig out of the library's memory; ONE formatter thread takes the contigs in contig order (OutputMAF appends per contig, VarVec grows in
@@ -56,6 +57,7 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -timing        print where the wall time went (one JSON line on stderr)\n");
 	fprintf(stderr, "         -cs            with -fmt 3: add the cs:Z: difference string (short form) of every alignment, computed on the GPU (gsa_block_cs) [false]\n");
 	fprintf(stderr, "         -lift  FILE    lift the reference positions of FILE (tab-separated: sequence name, 1-based position; '#' lines skipped, a VCF works) to the query on the GPU (gsa_lift): <prefix>.lift.tsv\n");
+	fprintf(stderr, "         -proj          project the query onto the reference on the GPU (gsa_project): one character per reference base over all query sequences -- the aligned query base, '-' deleted, 'n' not aligned: <prefix>.proj.fa\n");
 	fprintf(stderr, "         -track INT     per window of INT reference bases and query sequence: covered / matching / mismatching / deleted / inserted bases, computed on the GPU (gsa_ref_track): <prefix>.track.tsv\n");
 	fprintf(stderr, "         -chain         write every alignment as a UCSC chain (liftOver, CrossMap), its segments computed on the GPU (gsa_block_segs): <prefix>.chain [false]\n");
 	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
@@ -139,7 +141,7 @@ int main(int argc, char *argv[])
 	//  kernel and faulting it in again for the next contig)
 	mallopt(M_MMAP_THRESHOLD, 1 << 30); mallopt(M_TRIM_THRESHOLD, 1 << 30); mallopt(M_TOP_PAD, 256 << 20);
 	gsa_params prm; gsa_default_params(&prm);
-	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, want_cs = false, want_chain = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
+	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, want_cs = false, want_chain = false, want_proj = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
 	std::vector<int> gpus;
 	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL, *lift_file = NULL;
 	int track_w = 0;      // -track W (0: no track)
@@ -174,6 +176,7 @@ int main(int argc, char *argv[])
 		else if (a == "-gpuvar") gpuvar = true;
 		else if (a == "-cs") want_cs = true;
 		else if (a == "-chain") want_chain = true;
+		else if (a == "-proj") want_proj = true;
 		else if (a == "-lift" && i + 1 < argc) lift_file = argv[++i];
 		else if (a == "-track" && i + 1 < argc) {
 			char *end = NULL; const long long w = strtoll(argv[++i], &end, 10);
@@ -313,9 +316,14 @@ int main(int argc, char *argv[])
 	}
 	// (the positions go to every context, the clones included: a clone starts without)
 	if (track_w) for (gsa_ctx *c : ctxs) if (gsa_track_set(c, track_w) != GSA_OK) { fprintf(stderr, "-track: %s\n", gsa_last_error(c)); return 2; }
+	// -proj: one accumulator per GPU -- its first context opens it, the clones on that GPU paint into the same array (without the duplicates under -unique)
+	if (want_proj) for (size_t i = 0; i < ctxs.size(); i++) {
+		gsa_ctx *first = i < gpus.size() ? NULL : ctxs[(i - gpus.size()) % gpus.size()];
+		if (gsa_proj_open(ctxs[i], first, allow_dup ? 0u : GSA_PROJ_NO_DUP) != GSA_OK) { fprintf(stderr, "-proj: %s\n", gsa_last_error(ctxs[i])); return 2; }
+	}
 	if (want_lift) for (gsa_ctx *c : ctxs) if (gsa_lift_set(c, lift_pos.data(), (int64_t)lift_pos.size()) != GSA_OK) { fprintf(stderr, "-lift: %s\n", gsa_last_error(c)); return 2; }
 
-	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv", trackn = std::string(out_prefix) + ".track.tsv", chainn = std::string(out_prefix) + ".chain";
+	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv", trackn = std::string(out_prefix) + ".track.tsv", chainn = std::string(out_prefix) + ".chain", projn = std::string(out_prefix) + ".proj.fa";
 	Emitter em; em.idx = &idx; em.allow_dup = allow_dup;
 	long long n_aln = 0, tot_len = 0, tot_match = 0, n_dup = 0;
 	fprintf(stderr, "Step2. Sequence analysis for all query chromosomes\n");
@@ -348,6 +356,8 @@ int main(int argc, char *argv[])
 	if (track_w && !(track_fp = fopen(trackn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", trackn.c_str(), strerror(errno)); }
 	FILE *chain_fp = NULL; int64_t chain_id = 0;
 	if (want_chain && !(chain_fp = fopen(chainn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", chainn.c_str(), strerror(errno)); }
+	FILE *proj_fp = NULL;
+	if (want_proj && !(proj_fp = fopen(projn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", projn.c_str(), strerror(errno)); }
 	auto write_contig = [&](size_t ci, ContigResult &cr) {
 		fprintf(stderr, "\tProcess query chromsomoe: %s...\n", qs[ci].name.c_str());
 		if (chain_fp) {      // (in front of the emitters that shorten a block's last record: the chain reads the trim off the untrimmed one and changes nothing; never the host comparator in place of a missing device answer)
@@ -473,7 +483,7 @@ int main(int argc, char *argv[])
 	};
 	if (timing && var_on_gpu) for (gsa_ctx *c : ctxs) (void)gsa_set_profiling(c, 8);      // (the variant passes' device time, for the GSA_VARIANT_PASS line)
 	const double ta = now_s(); t_at_align = ta - T0;
-	const int rc_many = (fmt == 3 || want_lift || track_w || want_chain) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u) | (want_chain ? GSA_WANT_SEGS : 0u), on_result_ex, &sink)
+	const int rc_many = (fmt == 3 || want_lift || track_w || want_chain || want_proj) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u) | (want_chain ? GSA_WANT_SEGS : 0u) | (want_proj ? GSA_WANT_PROJ : 0u), on_result_ex, &sink)
 	                  : var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
 	                               : gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
 	t_align = now_s() - ta;
@@ -484,6 +494,7 @@ int main(int argc, char *argv[])
 	double lift_ms = 0;       // -lift: the same of gsa_lift
 	double track_ms = 0;      // -track: the same of gsa_ref_track
 	double chain_ms = 0;      // -chain: the same of gsa_block_segs (its CIGAR walk included unless -cs ran it)
+	double proj_ms = 0;       // -proj: the same of gsa_project, plus the fetch, merge and write below
 	double var_dev_ms = 0; long long var_dev_n = 0;      // -gpuvar: device time of the variant passes (hipEvents), all contexts
 	double wall_sum[10] = { 0 }; double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 	for (gsa_ctx *c : ctxs) {
@@ -493,9 +504,33 @@ int main(int argc, char *argv[])
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_lift_timing(c, &cm, &cn) == GSA_OK) lift_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_track_timing(c, &cm, &cn) == GSA_OK) track_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_seg_timing(c, &cm, &cn) == GSA_OK) chain_ms += cm; }
+		{ double cm = 0; int64_t cn = 0; if (gsa_get_proj_timing(c, &cm, &cn) == GSA_OK) proj_ms += cm; }
 		double vm = 0; int64_t vn = 0; if (gsa_get_variant_timing(c, &vm, &vn) == GSA_OK) { var_dev_ms += vm; var_dev_n += vn; }
 		double am = 0; int64_t an = 0, ab = 0; if (gsa_get_alloc_stats(c, &am, &an, &ab) == GSA_OK) { alloc_ms += am; alloc_n += an; alloc_bytes += ab; }
 	}
+	// -proj: every contig is painted (gsa_align_many_ex has returned).  The words of every further GPU go into the first GPU's array, in chunks; the text comes home
+	// sequence by sequence and is written as FASTA -- before the contexts are destroyed
+	if (proj_fp && rc_many == GSA_OK) {
+		const double t = now_s();
+		bool ok = true;
+		std::vector<uint32_t> wbuf;
+		for (size_t g = 1; g < gpus.size() && ok; g++)
+			for (int64_t p0 = 0; p0 < idx.G && ok; p0 += (int64_t)1 << 24) {
+				const int64_t m = std::min<int64_t>((int64_t)1 << 24, idx.G - p0);
+				wbuf.resize((size_t)m);
+				if (gsa_proj_fetch(ctxs[g], p0, m, NULL, wbuf.data()) != GSA_OK) { fprintf(stderr, "-proj: %s\n", gsa_last_error(ctxs[g])); ok = false; }
+				else if (gsa_proj_merge(ctxs[0], p0, m, wbuf.data()) != GSA_OK) { fprintf(stderr, "-proj: %s\n", gsa_last_error(ctxs[0])); ok = false; }
+			}
+		std::string text;
+		for (size_t c = 0; c < idx.chr_len.size() && ok; c++) {
+			text.resize((size_t)idx.chr_len[c]);
+			if (gsa_proj_fetch(ctxs[0], idx.chr_fwd[c], idx.chr_len[c], &text[0], NULL) != GSA_OK) { fprintf(stderr, "-proj: %s\n", gsa_last_error(ctxs[0])); ok = false; break; }
+			em.proj_text((int)c, text.data(), [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, proj_fp) != o.n) out_failed = true; });
+		}
+		if (!ok) out_failed = true;
+		proj_ms += (now_s() - t) * 1e3;
+	}
+	if (proj_fp) { if (ferror(proj_fp) | fclose(proj_fp)) out_failed = true; proj_fp = NULL; }
 	{ std::lock_guard<std::mutex> lk(sink.mu); if (rc_many != GSA_OK) sink.abort = true; }
 	sink.cv.notify_all();
 	const double td = now_s();
@@ -544,10 +579,10 @@ int main(int argc, char *argv[])
 		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, \"cigar_s\": %.3f, "
 		        "\"result_copy_s_sum\": %.3f, \"maf_format_s\": %.3f, \"variants_s\": %.3f, \"output_drain_after_align_s\": %.3f, \"maf_write_s\": %.3f, \"maf_bytes\": %llu, "
 		        "\"vcf_s\": %.3f, \"vcf_write_s\": %.3f, \"vcf_bytes\": %llu, \"destroy_s\": %.3f, \"host_threads\": %d, \"contexts\": %d, \"query_bp\": %lld, \"contigs\": %d, \"gbp_per_s_excl_index_build\": %.4f, "
-		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"chain_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
+		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"proj_s\": %.3f, \"chain_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
 		        total, t_build, t_index, t_create, t_query, t_pin, t_align, cigar_ms / 1e3, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
-		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, chain_ms / 1e3, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
+		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, proj_ms / 1e3, chain_ms / 1e3, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
 	}
 	if (timing && var_on_gpu) fprintf(stderr, "GSA_VARIANT_PASS {\"device_ms_sum\": %.3f, \"passes\": %lld, \"query_bp\": %lld}\n", var_dev_ms, var_dev_n, [&] { long long b = 0; for (const QueryContig &q : qs) b += (long long)q.seq.size(); return b; }());
 	// (everything is on disk and the GPU is released: the process ends here -- unwinding 20 GB of host buffers and the HIP runtime's own

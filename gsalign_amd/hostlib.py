@@ -312,6 +312,56 @@ def track(index_prefix, seq, result, W: int):
     return T
 
 
+def project(index_prefix, seq, result, words, flags: int = 0):
+    """gsah_c_project: one finished contig painted into the caller's accumulator `words` (a C-contiguous uint32 array of G entries, changed in place: the maximum stays)
+    on the host, from the records, the gapped strings and the query contig seq (uint8 array or bytes: its bases stand in the seeds' columns) -- what Aligner.project
+    paints on the GPU, by the contract of gsa_project (include/gsa_hip.h).  result: a capi.Result, a dump dict (oracle layout) or a result dict of capi.Aligner.
+    flags: capi.PROJ_NO_DUP.  Returns (blocks painted, words offered)."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    if not (isinstance(words, np.ndarray) and words.dtype == np.uint32 and words.flags.c_contiguous and words.flags.writeable):
+        raise TypeError("words: a writeable C-contiguous uint32 array")
+    q = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if isinstance(seq, (bytes, bytearray)) else seq, dtype=np.uint8)
+    st = capi.ProjStat()
+    lib = load()
+    lib.gsah_c_project.restype = C.c_int
+    lib.gsah_c_project.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(capi.Result), C.c_uint32, C.c_void_p, C.c_longlong, C.POINTER(capi.ProjStat)]
+    rc = lib.gsah_c_project(index_prefix.encode(), C.c_void_p(q.ctypes.data), C.byref(result), int(flags), C.c_void_p(words.ctypes.data), int(words.size), C.byref(st))
+    if rc < 0:
+        raise RuntimeError(f"gsah_c_project -> {rc}")
+    return int(st.n_blocks), int(st.n_cols)
+
+
+def proj_text(words) -> bytes:
+    """gsah_c_proj_text: accumulator words -> characters (codes 1..6: A C G T N -, word 0: n)."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    out = np.zeros(max(int(w.size), 1), np.uint8)
+    lib = load()
+    lib.gsah_c_proj_text.restype = C.c_int
+    lib.gsah_c_proj_text.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
+    rc = lib.gsah_c_proj_text(C.c_void_p(w.ctypes.data), int(w.size), C.c_void_p(out.ctypes.data))
+    if rc < 0:
+        raise RuntimeError(f"gsah_c_proj_text -> {rc}")
+    return out[:int(w.size)].tobytes()
+
+
+def emit_proj(index_prefix, words) -> bytes:
+    """gsah_c_emit_proj: the FASTA text -proj writes for the accumulator `words` (G entries): one record per reference sequence, 60 characters per line."""
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    lib = load()
+    lib.gsah_c_emit_proj.restype = C.c_longlong
+    lib.gsah_c_emit_proj.argtypes = [C.c_char_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
+    n = lib.gsah_c_emit_proj(index_prefix.encode(), C.c_void_p(w.ctypes.data), int(w.size), None, 0)
+    if n < 0:
+        raise RuntimeError(f"gsah_c_emit_proj -> {n}")
+    out = np.zeros(max(int(n), 1), np.uint8)
+    n2 = lib.gsah_c_emit_proj(index_prefix.encode(), C.c_void_p(w.ctypes.data), int(w.size), C.c_void_p(out.ctypes.data), int(n))
+    if n2 != n:
+        raise RuntimeError(f"gsah_c_emit_proj -> {n2} after {n}")
+    return out[:int(n)].tobytes()
+
+
 def segs(index_prefix, seq, result):
     """gsah_c_segs: the chain triples of every block of one finished contig on the host, from the gapped strings and seed records, untrimmed -- what Aligner.block_segs
     computes on the GPU.  result: a capi.Result, a dump dict (oracle layout) or a result dict of capi.Aligner.  index_prefix and seq are not needed by the walk and may be

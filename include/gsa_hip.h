@@ -488,8 +488,51 @@ int gsa_block_segs(gsa_ctx *ctx, int32_t k, gsa_segs *out);
  * number of calls.  Always on. */
 int gsa_get_seg_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 
+/* ---- the query projected onto the reference ------------------------------------------------------------------
+ * One character per forward reference position p in [0, G): the query base the best alignment puts there, '-' where the base is deleted, a marker where nothing
+ * aligns -- accumulated over every contig (context, device) that paints.  The only pass whose answer is not per contig.
+ *   accumulator  one uint32_t word per p; 0: uncovered, else
+ *                  bit 31      bdup == 0 of the painting block
+ *                  bits 30..3  min(max(gsa_block::score, 0), 2^28 - 1)
+ *                  bits 2..0   code: 1 A, 2 C, 3 G, 4 T, 5 N, 6 gap
+ *   painting     a block's covered text positions are first.rpos <= t < end, end = last.rpos + last.rlen CLAMPED to the end of the block's chromosome copy -- TRIMMED
+ *                exactly as gsa_lift trims; p = t for a forward-strand block, 2G - 1 - t for a reverse-strand block.  The columns are the CIGAR pass's: a seed is '='
+ *                over its length, an equal-length gap that needed no DP faces base to base, a DP gap is read from the op string of its DP job, a pure deletion is gap
+ *                throughout; inserted query bases have no reference base and are not projected.  A reference base that faces a query byte gets that byte's code --
+ *                acgtACGT 1..4, anything else 5 -- complemented on a reverse-strand block (5 - code for 1..4, 5 stays): the character the MAF prints in the query row
+ *                of that column.  A reference base that faces '-' gets code 6.  Every covered column offers key | code to word p and the word keeps the MAXIMUM.
+ *   order        so: a block that is no duplicate before a duplicate, then the greater (clamped) score, then the greater code.  gsa_lift breaks score ties by the
+ *                smaller block index; here the tie rule is chosen so that the result does not depend on the order in which blocks, contigs, contexts and devices
+ *                arrive.  Wherever the two best covering blocks differ in (dup, clamped score) the character is the one gsa_lift's hit implies: query[qpos]
+ *                (complemented when rev) for '=' / 'X', '-' for 'D'.
+ *   text         codes 1..6 -> A C G T N -, word 0 -> n. */
+#define GSA_PROJ_NO_DUP 1u   /* blocks with bdup != 0 are not painted (the CLI's -unique) */
+typedef struct { int32_t n_blocks; int32_t _pad; int64_t n_cols; } gsa_proj_stat;   /* 16 bytes: blocks painted, words offered */
+/* An accumulator for the context.  share == NULL: G zeroed words on the context's device (4 bytes per reference base: 12.4 GB for a human reference); a failed
+ * allocation is GSA_ERR_NOMEM with nothing changed.  share != NULL: that context's accumulator, which must lie on the SAME device (else GSA_ERR_ARG, the reason
+ * in gsa_last_error) -- both contexts then paint into the one array (integer maxima from several streams commute).  The array is reference counted:
+ * gsa_proj_close and gsa_destroy drop a reference, the last one frees it once the stream is quiet.  A clone starts without an accumulator.  A context that
+ * holds one already: GSA_ERR_STATE; unknown flags: GSA_ERR_ARG. */
+int gsa_proj_open(gsa_ctx *ctx, gsa_ctx *share, uint32_t flags);
+int gsa_proj_close(gsa_ctx *ctx);   /* without an accumulator: GSA_ERR_STATE */
+int gsa_proj_clear(gsa_ctx *ctx);   /* every word back to 0 (and the array no longer dirty, see gsa_project) */
+/* Paints the blocks of the stage-8 result the context holds (contig k of a bundle: the painted content does not depend on whether the contig was aligned alone or in
+ * a bundle).  Validity, call order, k and the error codes are those of gsa_block_cigars; without an accumulator GSA_ERR_STATE.  No blocks: the stat is zero, the
+ * words untouched.  The pass has buffers of its own: the six other passes return what they returned before, in any call order.  A DP record without a job, or a
+ * column outside its record or sequence, is counted on the device and fails the call with GSA_ERR_STATE; the accumulator is then DIRTY, and gsa_proj_fetch and
+ * gsa_project return GSA_ERR_STATE on it until gsa_proj_clear.  out may be NULL. */
+int gsa_project(gsa_ctx *ctx, int32_t k, gsa_proj_stat *out);
+/* Positions [p0, p0 + n) as characters (text, n bytes, no NUL) and / or as words; either may be NULL.  A range outside [0, G) or n < 0: GSA_ERR_ARG; n == 0: nothing
+ * happens.  Fetch and merge wait for the context's OWN stream only: the caller orders them against other contexts that share the array (gsa_align_many_ex has
+ * returned by then).  The characters are made on the device; everything comes home through pinned staging in bounded chunks. */
+int gsa_proj_fetch(gsa_ctx *ctx, int64_t p0, int64_t n, char *text, uint32_t *words);
+/* Host words (another device's, another run's) into positions [p0, p0 + n): uploaded in bounded chunks, the element-wise maximum stays. */
+int gsa_proj_merge(gsa_ctx *ctx, int64_t p0, int64_t n, const uint32_t *words);
+/* measurement: host wall time the calling threads spent inside gsa_project on this context since it was created, and the number of calls.  Always on. */
+int gsa_get_proj_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+
 /* gsa_align_many with optional passes run by the worker in front of the callback -- before the prefetch after next can touch the contig's
- * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track) | GSA_WANT_SEGS (gsa_block_segs).  *ex and what it
+ * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track) | GSA_WANT_SEGS (gsa_block_segs) | GSA_WANT_PROJ (gsa_project).  *ex and what it
  * points to are valid during the callback only, like *res. */
 #define GSA_WANT_VARIANTS 1u
 #define GSA_WANT_CIGARS   2u
@@ -497,6 +540,7 @@ int gsa_get_seg_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 #define GSA_WANT_LIFT     16u  /* gsa_lift of every contig; every context of ctx[] must hold positions (gsa_lift_set), else GSA_ERR_STATE before any contig is aligned */
 #define GSA_WANT_TRACK    32u  /* gsa_ref_track of every contig; every context of ctx[] must hold a window (gsa_track_set), else GSA_ERR_STATE before any contig is aligned */
 #define GSA_WANT_SEGS     64u  /* gsa_block_segs; implies GSA_WANT_CIGARS */
+#define GSA_WANT_PROJ     128u /* gsa_project of every contig, behind the other passes; it adds nothing behind gsa_extras; every context of ctx[] must hold an accumulator (gsa_proj_open), else GSA_ERR_STATE before any contig is aligned -- but where NO context of ctx[] holds one the bit is refused like an unknown one, GSA_ERR_ARG, as it was before the pass existed */
 typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;   /* NULL where not asked for */
 /* The contig's cs strings inside the callback of gsa_align_many_ex: the library hands the callback a LARGER object whose head is the gsa_extras
  * (which keeps its two members and its 16 bytes), and this call reaches what lies behind it -- so it is valid for the `ex` the library passed
