@@ -467,5 +467,6 @@ int gsa_get_blocks(gsa_ctx *c, gsa_result *out)
 }
 int gsa_get_counters(gsa_ctx *c, uint64_t counters[8]) { if (!c) return GSA_ERR_ARG; memcpy(counters, c->counters, sizeof(c->counters)); return GSA_OK; }
 int gsa_get_timings(gsa_ctx *c, float ms[8]) { if (!c) return GSA_ERR_ARG; memcpy(ms, c->kernel_ms, sizeof(c->kernel_ms)); if (c->prof_seed && !c->profiling) ms[6] = (float)c->acc_seed_ms; return GSA_OK; }
+int gsa_get_dp_stats(gsa_ctx *c, uint64_t st[4]) { if (!c) return GSA_ERR_ARG; memcpy(st, c->dp_stats, sizeof(c->dp_stats)); return GSA_OK; }
 int gsa_get_seed_stats(gsa_ctx *c, uint64_t st[8]) { if (!c) return GSA_ERR_ARG; memcpy(st, c->dbg, sizeof(c->dbg)); return GSA_OK; }
 } // extern "C"

@@ -508,6 +508,7 @@ int gsa_set_option(gsa_ctx *c, const char *name, int64_t value)
 	else if (k == "seed_lhop") { if (value != 0 && (!in(16, 1 << 16) || (value & (value - 1)))) return gsa_fail(c, GSA_ERR_ARG, "seed_lhop: 0 or a power of two >= 16"); c->opt.seed_lhop = (int)value; }    // (test hook: a smaller long-hop table)
 	else if (k == "pd_bitmap") c->opt.pd_bitmap = value != 0;
 	else if (k == "dp_side") c->opt.dp_side = value != 0;
+	else if (k == "dp_pair") { if (!in(0, 3)) return gsa_fail(c, GSA_ERR_ARG, "dp_pair: 0 never, 1 where it costs fewer wave-steps in a long class, 2 always, 3 where it costs fewer wave-steps"); c->opt.dp_pair = (int)value; }
 	else if (k == "pd_two_level_min") { if (!in(0, BIG)) return gsa_fail(c, GSA_ERR_ARG, "pd_two_level_min: >= 0 blocks"); c->opt.pd_two_level_min = value; }
 	else if (k == "pd_bytes") { if (!in(0, 2)) return gsa_fail(c, GSA_ERR_ARG, "pd_bytes: 0 never, 1 by the hit count, 2 always"); c->opt.pd_bytes = (int)value; }
 	else if (k == "pres_from_kmer") c->opt.pres_from_kmer = value != 0;      // (takes effect at the next gsa_set_params that rebuilds the table)

@@ -82,6 +82,7 @@ struct Options {
 	int pd_bitmap = 1;                 // 0: groups by the PosDiff sort although MaxIndelSize <= 31 would allow the bitmap scan
 	int sweep_shape = -1;              // k_dense_sweep's launch shape: -1 by the number of dense chunks, 0 = four chunks per two-wave workgroup / 160-start segments, 1 = one chunk per four-wave workgroup / 40-start segments
 	int dp_side = 0;                   // 1: the striped DP's lower size class on a stream of its own, beside the upper class (0: behind it)
+	int dp_pair = 1;                   // the striped DP runs two jobs side by side in a wave's 16-bit halves: 0 never (every job in the lagged form), 1 where that costs fewer wave-steps, in size classes of at least DP_PAIR_MIN_JOBS jobs, 2 every two neighbours of a size class, 3 as 1 in a class of any length (2, 3: tests)
 	int64_t walk_chain_min = 100000;   // contigs with more seeds than this walk their window chain in slices (k_walk_chain) instead of one workgroup's LDS (k_walk_windows); tests: 0
 	int64_t pd_two_level_min = 2000000;   // PosDiff bitmaps of more blocks than this (a reference above ~1 Gbp) are scanned in two passes: list the touched blocks, count those (tests: 0)
 	int pd_bytes = 1;                  // the PosDiff bitmap of a contig (bundle) whose hits scatter (-sen: thousands of chance hits per chunk) is filled through a byte per value, plain stores, and packed
@@ -104,7 +105,7 @@ struct gsa_ctx {
 	u64 seed_ticket = 0;                    // value of the seed kernel's ticket counter (d_cnt[16]) before the next launch
 	int n_cus = 0;
 	bool seed_lds_checked = false;       // stage1_seed compared the LDS its launch asks for with the device's per-block limit
-	hipStream_t stream_aux[4] = {nullptr, nullptr, nullptr, nullptr};   // [3]: the striped DP's lower size class beside its upper one (option dp_side); [0] early striped DP, [1] tiny DP + strings + sums, [2] records to the host (four streams in all: one per hardware queue)
+	hipStream_t stream_aux[4] = {nullptr, nullptr, nullptr, nullptr};   // [3]: a striped size class's unpaired jobs beside its pairs (launch_stripes; default path on contigs with a class of DP_PAIR_MIN_JOBS jobs), and the lower size class beside the upper one (option dp_side); [0] early striped DP, [1] tiny DP + strings + sums, [2] records to the host (five streams with the main one: with the runtime's default of four hardware queues two of them share one; bench.py asks for 16)
 	std::string err;
 	Params prm;
 	DevIndex di = {};
@@ -122,6 +123,7 @@ struct gsa_ctx {
 	double wall_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; int64_t wall_n = 0;      // host wall clock spent in [0] the query set-up (upload / wait for the prefetch) and [s] stage s of gsa_run_to, summed over contigs since gsa_set_profiling (gsa_get_wall_sums)
 	double acc_seed_ms = 0.0;                      // seed-search kernel time summed over the contigs since gsa_set_profiling (flag bit 2), see gsa_get_timings
 	u64 counters[8] = {};
+	u64 dp_stats[4] = {};                          // launch_stripes since the context was made: striped jobs, of them side by side, lagged launches, side-by-side launches (gsa_get_dp_stats)
 
 	// index (device)
 	DevBuf d_bwt, d_bwt_ref, d_occ_base, d_sa, d_ref, d_chr_end, d_chr_of_end;

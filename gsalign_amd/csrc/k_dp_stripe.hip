@@ -58,8 +58,10 @@ struct StripeJob { i32 job, m, n, P; i64 diroff, bndoff; i32 ctr, first_block; }
 #define DP_CLASS_M 768          // size classes of a long job list: reference fragments above / up to this (see launch_stripes)
 #define DP_CLASS_TOP 1536       // ... and, round 5, the upper class cut once more: fragments above this keep the 64 KB layout, (768, 1536] run with 26 KB
 #define DP_CLASS_MIN_JOBS 4096
+#define DP_PAIR_MIN_JOBS 4096      // a size class of fewer jobs is not paired (option dp_pair = 1): see launch_stripes
 #ifndef DP_PRIO_BLOCKS
-#define DP_PRIO_BLOCKS 96       // the first workgroups of a launch (its largest jobs: the list is sorted by cells) issue at raised priority
+#define DP_PRIO_BLOCKS 0        // the first so many workgroups of a launch (its largest jobs: the list is sorted by cells) issue at raised priority.  96 until the pairs came:
+                                // two A/Bs (profiles/r06_seed_footprint.txt, profiles/dp_pairs_ab.txt) found no difference between 96 and 0, so nothing is raised
 #endif
 #define DP_LDS_M 3968         // longest reference fragment for which four waves share a workgroup (selectors + 3 boundary columns in 64 KB of LDS)
 
@@ -79,7 +81,17 @@ __device__ __forceinline__ u32 pk_mad(u32 a, u32 b, u32 c) { return U1(V2(a) * V
 __device__ __forceinline__ u32 pk_shl(u32 a, u32 sh) { return U1(V2(a) << V2(sh)); }
 #define DP_OPAQUE(X) asm volatile("" : "+v"(X))
 
-template <int WPB>
+// SBS = 1, the SIDE-BY-SIDE form: the two halves of a wave hold stripe p of two DIFFERENT jobs X (low) and Y (high), in lockstep.  Each half is an
+// ordinary stripe with a 63-step ramp: no lag, no neighbour inside the wave (lane 0 takes both left neighbours from the boundary input), 64 lead-in
+// rows, and a wave runs max(m + width - 1) over the halves it has.  The virtual job (X, Y) is sjobs[b], sjobs[b + 1]: tickets, boundary granules and
+// the forward pass's LDS are the pair's, direction blocks and results each job's own; the last wave of the pair walks back X, then Y.
+// One granule per row carries both jobs' (x, v) of lane 63 under one tag: in the matrix z <= 7 (dp_cell), so v = z - u <= 7 and x = a - (z - 2) <= 2
+// (a <= z): a pair fits a byte, two pairs and the epoch tag the 4-byte granule.  Rows past the shorter job's end carry that half's values cut to the
+// nibble; like every cell outside a matrix they only ever reach other such cells.
+__device__ __forceinline__ u32 dp_pack4(u32 h) { return (h & 0xfu) | ((h >> 4) & 0xf0u) | ((h >> 8) & 0xf00u) | ((h >> 12) & 0xf000u); }          // bytes xX, vX, xY, vY -> nibbles
+__device__ __forceinline__ u32 dp_unpack4(u32 g) { return (g & 0xfu) | ((g & 0xf0u) << 4) | ((g & 0xf00u) << 8) | ((g & 0xf000u) << 12); }      // ... and back
+
+template <int WPB, int SBS>
 __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ blk2job, const StripeJob *__restrict__ sjobs, const uint8_t *__restrict__ pool1, const i64 *__restrict__ off1,
                                                    const uint8_t *__restrict__ pool2, const i64 *__restrict__ off2, uint8_t *dirbase, u32 *bndbase, u32 *ctr,
                                                    uint8_t *revbase, uint8_t *ops, const i64 *__restrict__ ops_off, i32 *ops_len, u32 ep, i32 lds_c1, i32 lds_rows, u32 *err, i32 tick_slot)
@@ -102,26 +114,32 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 	}
 	__syncthreads();
 	const u32 bid = s_bid;
-	if (bid < DP_PRIO_BLOCKS) __builtin_amdgcn_s_setprio(3);
+	if (DP_PRIO_BLOCKS > 0 && bid < (u32)DP_PRIO_BLOCKS) __builtin_amdgcn_s_setprio(3);
 	// which job / pair of stripes am I (uniform).  Both tables are read where the host wrote them (pinned memory): two
 	// dependent reads across the link cost less than a copy operation in front of the launch
 	const StripeJob sj = sjobs[blk2job[bid]];
+	const StripeJob sy = SBS ? sjobs[blk2job[bid] + 1] : sj;            // side by side: job Y of the pair (the high halves)
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const int m = sj.m, n = sj.n, P = sj.P, PP = (P + 1) >> 1;
-	const int pp = ((int)bid - sj.first_block) * WPB + wave;            // stripes 2pp ("A", low halves) and 2pp + 1 ("B", high halves)
+	const int m = sj.m, n = sj.n, P = sj.P, PP = SBS ? (P > sy.P ? P : sy.P) : (P + 1) >> 1;      // PP: waves of the (virtual) job
+	const int mB = SBS ? sy.m : m, nB = SBS ? sy.n : n;                                    // the high halves' job (lagged: the same one)
+	const int mv = SBS ? (m > mB ? m : mB) : m;                         // rows of the virtual job: selectors, boundary columns
+	const int pp = ((int)bid - sj.first_block) * WPB + wave;            // stripes 2pp ("A", low halves) and 2pp + 1 ("B", high halves); side by side: stripe pp of X and of Y
 	const uint8_t *s1 = pool1 + off1[sj.job], *s2 = pool2 + off2[sj.job];
+	const uint8_t *s1B = SBS ? pool1 + off1[sy.job] : s1, *s2B = SBS ? pool2 + off2[sy.job] : s2;
 	const size_t pitch = (size_t)DP_STRIPE_BYTES(m);                    // direction nibbles of one stripe: 256 bytes per eight anti-diagonals
 	const int nblk = (m + 63 + 7) >> 3;                                 // ... in so many blocks
+	const int nblkB = SBS ? (mB + 63 + 7) >> 3 : nblk;
 	uint8_t *dir = dirbase + sj.diroff;
-	u32 *bnd_in = bndbase + sj.bndoff + (size_t)(pp - 1) * m, *bnd_out = bndbase + sj.bndoff + (size_t)pp * m;
-	// C2[128 + j] = v_perm selector of step-row j: byte 0 = code of reference row j (stripe A's table: bytes 0-3 of the pair),
-	// byte 2 = 4 + code of row j - 64 (stripe B lags 64 steps: its table is bytes 4-7), 0x0c ("constant 0") for N and for
-	// the rows in front of and behind the fragment, and in bytes 1, 3.  On step s lane l reads entry s - l.
+	u32 *bnd_in = bndbase + sj.bndoff + (size_t)(pp - 1) * mv, *bnd_out = bndbase + sj.bndoff + (size_t)pp * mv;
+	constexpr int LEAD = SBS ? 64 : 128;                                // "N" rows in front of the fragment's selectors
+	// C2[LEAD + j] = v_perm selector of step-row j: byte 0 = code of the low halves' reference row j (table: bytes 0-3 of the pair), byte 2 = 4 + code of
+	// the high halves' row (table: bytes 4-7) -- lagged: row j - 64 of the same fragment (stripe B lags 64 steps), side by side: row j of Y's fragment --
+	// 0x0c ("constant 0") for N, for the rows in front of and behind a fragment (each job's own end), and in bytes 1, 3.  On step s lane l reads entry s - l.
 	{
-		int fe = (m + DP_C1_PAD + 63) & ~63; fe = fe < (lds_c1 >> 2) ? fe : (lds_c1 >> 2);
+		int fe = (mv + DP_C1_PAD + 63) & ~63; fe = fe < (lds_c1 >> 2) ? fe : (lds_c1 >> 2);
 		for (int t = threadIdx.x; t < fe; t += 64 * WPB) {
-			const int j = t - 128, jb = j - 64;
-			const u32 ca = (j >= 0 && j < m) ? (u32)gsa_nt4(s1[j]) : 4u, cb = (jb >= 0 && jb < m) ? (u32)gsa_nt4(s1[jb]) : 4u;
+			const int j = t - LEAD, jb = j - (SBS ? 0 : 64);
+			const u32 ca = (j >= 0 && j < m) ? (u32)gsa_nt4(s1[j]) : 4u, cb = (jb >= 0 && jb < (SBS ? mB : m)) ? (u32)gsa_nt4((SBS ? s1B : s1)[jb]) : 4u;
 			C2[t] = (ca < 4 ? ca : 0x0cu) | 0x0c000c00u | ((cb < 4 ? 4u + cb : 0x0cu) << 16);
 		}
 	}
@@ -134,11 +152,13 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 	// packed 16-bit instructions (v_pk_add / max / min / sub: one instruction for both cells).  Stripe B lags 64 steps behind A:
 	// on step s lane l holds A's cell (row s - l, column 128 pp + l) and B's cell (row s - 64 - l, column 128 pp + 64 + l), and
 	// B's lane 0 takes its left neighbour -- A's lane 63, one step earlier -- from a readlane.
-	const int tA = pp * 128 + lane, tB = tA + 64;
-	const bool hasB = 2 * pp + 1 < P;
-	const int WpB = !hasB ? 0 : (n - pp * 128 - 64 < 64 ? n - pp * 128 - 64 : 64);
-	const int WpA = n - pp * 128 < 64 ? n - pp * 128 : 64;
-	const int cqA = tA < n ? gsa_nt4(s2[tA]) : 4, cqB = tB < n ? gsa_nt4(s2[tB]) : 4;
+	// Side by side both halves are column 64 pp + l of their own job, row s - l, and either half may be missing (the job has fewer stripes).
+	const int tA = SBS ? pp * 64 + lane : pp * 128 + lane, tB = SBS ? tA : tA + 64;
+	const bool hasA = SBS ? pp < P : true, hasB = SBS ? pp < sy.P : 2 * pp + 1 < P;
+	const int restA = SBS ? n - pp * 64 : n - pp * 128, restB = SBS ? nB - pp * 64 : n - pp * 128 - 64;      // columns from my stripe's first one on
+	const int WpB = !hasB ? 0 : (restB < 64 ? restB : 64);
+	const int WpA = restA < 64 ? restA : 64;
+	const int cqA = tA < n ? gsa_nt4(s2[tA]) : 4, cqB = tB < nB ? gsa_nt4(s2B[tB]) : 4;
 	// z = score + q + e (ksw2_alignment.cpp:74-95: match 1, mismatch -1, N 0 -> 7, 5, 6) as a byte table over the reference
 	// code, stored XOR 6 so that the selector's "constant 0" is the N row: z = v_perm(tables, selector) ^ 6 in both halves
 	u32 tblA = 0, tblB = 0;
@@ -147,24 +167,32 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 		tblA |= (u32)(cqA == 4 ? 0 : (cqA == cc ? 7 ^ 6 : 5 ^ 6)) << (8 * cc);
 		tblB |= (u32)(cqB == 4 ? 0 : (cqB == cc ? 7 ^ 6 : 5 ^ 6)) << (8 * cc);
 	}
-	const u32 uinit2 = (tA ? 2u : 0u) | (2u << 16);
+	const u32 uinit2 = SBS ? (tA ? 0x00020002u : 0u) : (tA ? 2u : 0u) | (2u << 16);
 	u32 u2 = uinit2, y2 = 0;
 	u32 bin = 0, gnext = 0;
 	__syncthreads();
 	if (pp >= PP) return;                               // (a workgroup's spare waves only helped to stage the fragment)
-	const int S_end = hasB ? 64 + m + WpB - 1 : m + WpA - 1;      // steps of this wave
+	const int S_endA = hasA ? m + WpA - 1 : 0, S_endB = hasB ? mB + WpB - 1 : 0;
+	const int S_end = SBS ? (S_endA > S_endB ? S_endA : S_endB) : (hasB ? 64 + m + WpB - 1 : m + WpA - 1);      // steps of this wave
+	// rows of the boundary column this wave takes in and hands on: side by side, the longest job that has the stripe (the stripe in front of an
+	// existing one is full, so the wave in front runs the m + 63 steps those rows need)
+	const int mw = SBS ? ((hasA ? m : 0) > (hasB ? mB : 0) ? (hasA ? m : 0) : (hasB ? mB : 0)) : m;
+	const int mpub = SBS ? ((pp + 1 < P ? m : 0) > (pp + 1 < sy.P ? mB : 0) ? (pp + 1 < P ? m : 0) : (pp + 1 < sy.P ? mB : 0)) : m;
+	// the steady state ends where the first of my stripes runs out of direction blocks
+	const int nblk_lo = SBS ? ((hasA ? nblk : 0x7fffffff) < (hasB ? nblkB : 0x7fffffff) ? (hasA ? nblk : 0x7fffffff) : (hasB ? nblkB : 0x7fffffff)) : nblk;
 	DPT(const unsigned long long T0c = wall_clock64();)
-	u32 *dirA = (u32 *)(dir + (size_t)(2 * pp) * pitch), *dirB = (u32 *)(dir + (size_t)(2 * pp + 1) * pitch);
+	u32 *dirA = (u32 *)(dir + (size_t)(SBS ? pp : 2 * pp) * pitch);
+	u32 *dirB = SBS ? (u32 *)(dirbase + sy.diroff + (size_t)pp * DP_STRIPE_BYTES(mB)) : (u32 *)(dir + (size_t)(2 * pp + 1) * pitch);
 	// boundary granules are fetched ONE BLOCK AHEAD (8 rows per block) so their L2 latency overlaps the block before
 	if (pp > 0) {
-		const int row = (lane & (DP_G - 1)) < m ? (lane & (DP_G - 1)) : m - 1;
+		const int row = (lane & (DP_G - 1)) < mw ? (lane & (DP_G - 1)) : mw - 1;
 		gnext = (WPB > 1 && wave > 0) ? __hip_atomic_load(&lin[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : __hip_atomic_load(&bnd_in[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	}
 	asm volatile("" :: "v"(gnext));                      // the first prefetch is complete before the loop: inside it, waits then only count stores issued after a prefetch
 	const bool pub_stripe = pp < PP - 1;                // (then stripe B is full and its lane 63 owns the boundary column)
 	u32 pk2 = 0;                                        // x | v << 8 of my two columns after the current step: bytes xA, vA, xB, vB
 	u32 hb = 0;                                         // lanes 0-7: stripe B's boundary column (x | v << 8 of its lane 63), the eight rows of the current block
-	const u32 selx = lane ? 0x0c060c04u : 0x0c040c00u, selv = lane ? 0x0c070c05u : 0x0c050c01u;      // x, v of (lane - 1 | boundary, A's lane 63) from (rotated pairs, boundary row)
+	const u32 selx = lane ? 0x0c060c04u : (SBS ? 0x0c020c00u : 0x0c040c00u), selv = lane ? 0x0c070c05u : (SBS ? 0x0c030c01u : 0x0c050c01u);      // x, v of (lane - 1 | boundary, A's lane 63) from (rotated pairs, boundary row); side by side lane 0 takes both from the boundary row (bytes xX, vX, xY, vY)
 	u32 acc = 0, r0 = 0;                   // direction nibbles of the last four steps (per half, oldest on top); those of the four before
 	u32 c1 = 0x00010001u, c2 = 0x00020002u, c4 = 0x00040004u, c7 = 0x00070007u, c16 = 0x00100010u;
 	DP_OPAQUE(c1); DP_OPAQUE(c2); DP_OPAQUE(c4); DP_OPAQUE(c7); DP_OPAQUE(c16);
@@ -180,11 +208,11 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 	{                                                                                                           \
 		const int s_ = s0 + (K2);                                                                               \
 		if (((K2) & (DP_G - 1)) == 0) {                                                                         \
-			if ((MODE) == 0) bin = (s_ == 0 && lane == 0) ? 0u : 0x200u;    /* t = 0 boundary: x1 = 0, v1 = q, except for the very first cell (:157-164) */ \
-			else if (s_ < m) {                                                                                  \
+			if ((MODE) == 0) bin = (s_ == 0 && lane == 0) ? 0u : (SBS ? 0x02000200u : 0x200u);    /* t = 0 boundary: x1 = 0, v1 = q, except for the very first cell (:157-164) */ \
+			else if (s_ < mw) {                                                                                 \
 				/* boundary rows s_ .. s_+DP_G-1 from the pair in front: spin until every granule carries its tag */ \
 				const int row = s_ + (lane & (DP_G - 1));                                                       \
-				const bool need = lane < DP_G && row < m;                                                       \
+				const bool need = lane < DP_G && row < mw;                                                      \
 				u32 g = gnext;                                                                                  \
 				if (!__all(!need || (g >> 16) == ep)) {      /* (first look outside the loop: its wait only covers the prefetch) */ \
 					u32 spins = 0; const unsigned long long t_wait0 = wall_clock64();                          \
@@ -194,9 +222,9 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 						if (need) g = DP_LOADG(MODE, row);                                                      \
 					} while (!__all(!need || (g >> 16) == ep));                                                  \
 				}                                                                                               \
-				bin = g & 0xffffu;                                                                              \
+				bin = SBS ? dp_unpack4(g) : g & 0xffffu;                                                                      \
 				/* every lane loads (clamped row): an unconditional load lands in gnext without a copy that would wait for it */ \
-				const int rown = row + DP_G < m ? row + DP_G : m - 1;                                           \
+				const int rown = row + DP_G < mw ? row + DP_G : mw - 1;                                         \
 				gnext = DP_LOADG(MODE, rown);                                                                   \
 			}                                                                                                   \
 		}                                                                                                       \
@@ -205,7 +233,7 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 		   boundary row for A and A's lane 63 (row s_ - 64, computed one step ago) for B */                          \
 		const u32 bin0 = (u32)__builtin_amdgcn_readlane((int)bin, (K2) & (DP_G - 1));                           \
 		const u32 rot = (u32)__builtin_amdgcn_mov_dpp((int)pk2, 0x13C, 0xf, 0xf, true);                         \
-		WL(hb, (u32)__builtin_amdgcn_readlane((int)pk2, 63) >> 16, (K2) & 7)      /* B's lane 63: boundary row s_ - 128 */ \
+		WL(hb, (u32)__builtin_amdgcn_readlane((int)pk2, 63) >> (SBS ? 0 : 16), (K2) & 7)      /* B's lane 63: boundary row s_ - 128 (side by side: both jobs' lane 63, row s_ - 64) */ \
 		const u32 x1 = __builtin_amdgcn_perm(rot, bin0, selx), v1 = __builtin_amdgcn_perm(rot, bin0, selv);     \
 		const u32 z0 = __builtin_amdgcn_perm(tblB, tblA, (WSEL)) ^ 0x00060006u;                                 \
 		const u32 a = pk_add(x1, v1), b = pk_add(y2, u2);                                                       \
@@ -221,32 +249,32 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 		u2 = un; y2 = yb;                                                                                       \
 		pk2 = __builtin_amdgcn_perm(vn, xa, 0x06020400u);      /* bytes xA, vA, xB, vB (values outside the matrix may not fit a byte: cut, not carried into the neighbour) */ \
 		if (GUARD) {                                                                                            \
-			const u32 keep = (lane <= s_ ? 0xffffu : 0u) | (lane <= s_ - 64 ? 0xffff0000u : 0u);               \
+			const u32 keep = (lane <= s_ ? 0xffffu : 0u) | (lane <= s_ - (SBS ? 0 : 64) ? 0xffff0000u : 0u); \
 			u2 = (u2 & keep) | (uinit2 & ~keep); y2 &= keep;                                                    \
 		}                                                                                                       \
 		if (((K2) & 7) == 3) r0 = acc;                                                                  \
 		if (((K2) & 7) == 7) {                                                                                  \
 			const int blk = s_ >> 3;                                                                            \
-			if (!(GUARD) || blk < nblk) dirA[((size_t)blk << 6) + lane] = __builtin_amdgcn_perm(acc, r0, 0x05040100u); \
-			if (hasB && (!(GUARD) || (blk >= 8 && blk - 8 < nblk))) dirB[((size_t)(blk - 8) << 6) + lane] = __builtin_amdgcn_perm(acc, r0, 0x07060302u); \
+			if (hasA && (!(GUARD) || blk < nblk)) dirA[((size_t)blk << 6) + lane] = __builtin_amdgcn_perm(acc, r0, 0x05040100u); \
+			if (hasB && (!(GUARD) || (blk >= LEAD / 8 - 8 && blk - (LEAD / 8 - 8) < nblkB))) dirB[((size_t)(blk - (LEAD / 8 - 8)) << 6) + lane] = __builtin_amdgcn_perm(acc, r0, 0x07060302u); \
 		}                                                                                                       \
-		if (((K2) & 7) == 7 && pub_stripe && s_ >= 135) {                                                       \
-			/* rows s_-135 .. s_-128 of B's boundary column are complete: one store of eight tagged granules */   \
-			const int row = s_ - 135 + lane;                                                                    \
-			if (lane < 8 && row < m) {                                                                          \
-				if (out_lds) __hip_atomic_store(&lout[row], (ep << 16) | hb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-				else __hip_atomic_store(&bnd_out[row], (ep << 16) | hb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+		if (((K2) & 7) == 7 && pub_stripe && s_ >= LEAD + 7) {                                                  \
+			/* rows s_-135 .. s_-128 of B's boundary column (side by side: s_-71 .. s_-64 of both) are complete: one store of eight tagged granules */ \
+			const int row = s_ - (LEAD + 7) + lane;                                                             \
+			if (lane < 8 && row < mpub) {                                                                       \
+				if (out_lds) __hip_atomic_store(&lout[row], (ep << 16) | (SBS ? dp_pack4(hb) : hb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
+				else __hip_atomic_store(&bnd_out[row], (ep << 16) | (SBS ? dp_pack4(hb) : hb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
 			}                                                                                                   \
 		}                                                                                                       \
 	}
 	// (three copies of the loop: the first pair has no boundary loads in flight, and keeping it apart keeps its waits off the stores)
 #define DP_LOOP(MODE)                                                                                           \
 	for (int s0 = 0; s0 < S_end; s0 += 16) {                                                                    \
-		const u32 *crow = C2 + 128 + s0 - lane;                /* my selectors from step s0 on */                  \
+		const u32 *crow = C2 + LEAD + s0 - lane;               /* my selectors from step s0 on */                  \
 		if (s0 + 16 <= S_end) {                                                                                 \
 			u32 w[16];                                                                                          \
 			_Pragma("unroll") for (int k2 = 0; k2 < 16; k2++) w[k2] = crow[k2];                                   \
-			if (s0 >= 128 && s0 + 16 <= 8 * nblk) {                                                             \
+			if (s0 >= LEAD && s0 + 16 <= 8 * nblk_lo) {                                                         \
 				/* the steady state of a long stripe pair: every lane is under way, every direction block exists */ \
 				DP_STEP(0, MODE, w[0], 0, DP_WL_LIT) DP_STEP(1, MODE, w[1], 0, DP_WL_LIT) DP_STEP(2, MODE, w[2], 0, DP_WL_LIT) DP_STEP(3, MODE, w[3], 0, DP_WL_LIT) DP_STEP(4, MODE, w[4], 0, DP_WL_LIT) DP_STEP(5, MODE, w[5], 0, DP_WL_LIT) DP_STEP(6, MODE, w[6], 0, DP_WL_LIT) DP_STEP(7, MODE, w[7], 0, DP_WL_LIT) \
 				DP_STEP(8, MODE, w[8], 0, DP_WL_LIT) DP_STEP(9, MODE, w[9], 0, DP_WL_LIT) DP_STEP(10, MODE, w[10], 0, DP_WL_LIT) DP_STEP(11, MODE, w[11], 0, DP_WL_LIT) DP_STEP(12, MODE, w[12], 0, DP_WL_LIT) DP_STEP(13, MODE, w[13], 0, DP_WL_LIT) DP_STEP(14, MODE, w[14], 0, DP_WL_LIT) DP_STEP(15, MODE, w[15], 0, DP_WL_LIT) \
@@ -267,16 +295,17 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 		if (S_end & 3) acc = pk_shl(acc, (u32)(4 * (4 - (S_end & 3))) * 0x00010001u);
 		if ((S_end & 7) < 4) r0 = acc;
 		const int blk = S_end >> 3;
-		if (blk < nblk) dirA[((size_t)blk << 6) + lane] = __builtin_amdgcn_perm(acc, r0, 0x05040100u);
-		if (hasB && blk >= 8 && blk - 8 < nblk) dirB[((size_t)(blk - 8) << 6) + lane] = __builtin_amdgcn_perm(acc, r0, 0x07060302u);
+		if (hasA && blk < nblk) dirA[((size_t)blk << 6) + lane] = __builtin_amdgcn_perm(acc, r0, 0x05040100u);
+		if (hasB && blk >= LEAD / 8 - 8 && blk - (LEAD / 8 - 8) < nblkB) dirB[((size_t)(blk - (LEAD / 8 - 8)) << 6) + lane] = __builtin_amdgcn_perm(acc, r0, 0x07060302u);
 	}
 	if (pub_stripe) {
-		// the last (partial) block of boundary rows: row m - 1 is lane 63's value after the last step (S_end = m + 127 here)
-		if (lane == (S_end & 7)) hb = (u32)__builtin_amdgcn_readlane((int)pk2, 63) >> 16;
-		const int row = (S_end & ~7) - 128 + lane;
-		if (lane <= (S_end & 7) && row >= 0 && row < m) {
-			if (out_lds) __hip_atomic_store(&lout[row], (ep << 16) | hb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-			else __hip_atomic_store(&bnd_out[row], (ep << 16) | hb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		// the last (partial) block of boundary rows: row m - 1 is lane 63's value after the last step (S_end = m + 127 here; side by side
+		// S_end >= mpub + 63, and the rows from mpub on are not handed on)
+		if (lane == (S_end & 7)) hb = (u32)__builtin_amdgcn_readlane((int)pk2, 63) >> (SBS ? 0 : 16);
+		const int row = (S_end & ~7) - LEAD + lane;
+		if (lane <= (S_end & 7) && row >= 0 && row < mpub) {
+			if (out_lds) __hip_atomic_store(&lout[row], (ep << 16) | (SBS ? dp_pack4(hb) : hb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+			else __hip_atomic_store(&bnd_out[row], (ep << 16) | (SBS ? dp_pack4(hb) : hb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		}
 	}
 	DPT(if (pp == 0 && lane == 0) ctr[sj.ctr + 40] = (u32)(wall_clock64() - T0c); if (pp == PP - 1 && lane == 0) ctr[sj.ctr + 41] = (u32)(wall_clock64() - T0c);)
@@ -308,102 +337,149 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 	}
 	DPT(const unsigned long long T1c = wall_clock64(); int ntile = 0, nrun = 0;)
-	uint8_t *rev = revbase + ops_off[sj.job], *op = ops + ops_off[sj.job];
-	int i = n - 1, j = m - 1, state = 0, k = 0;
-	// lane l looks at the cell e = l % 21 steps ahead along direction g = l / 21 (0: M, 1: D, 2: I)
-	const int g = lane / DP_LOOK, e = lane - g * DP_LOOK;
-	const int dlc = g == 2 ? 0 : -e, drl = g == 0 ? -2 * e : -e;
-	// The next tile is fetched while the current one is walked: an alignment path runs along the diagonal, so from (i, j)
-	// it will enter the stripe to the left near row j - (lc + 1); those diagonals (+-DP_TILE_SLACK for indels on the way)
-	// are loaded into registers now and only written to LDS when the walker gets there.  A wrong guess costs nothing but
-	// the load: the tile is then fetched the plain way.
-	// (a tile = DP_TILE_ROWS / 8 blocks of eight diagonals = 5 KB; block-aligned)
-	constexpr int TB_BLKS = DP_TILE_ROWS / 8, TB_VEC = TB_BLKS * 16 / 64;
-	static_assert(TB_VEC == 5, "the prefetched tile is five named registers (an array was kept in scratch: 96 bytes per lane)");
-	uint4 pf0 = {0, 0, 0, 0}, pf1 = pf0, pf2 = pf0, pf3 = pf0, pf4 = pf0;
+	// side by side: the pair's last wave walks back X, then Y -- the unchanged walker on each job's own direction blocks and result strings
+	// (a jump back, not a loop statement: the lagged form then compiles to exactly the code it was)
+	int h = 0;
+walk_back:
+	{
+		const int wm = h ? mB : m, wn = h ? nB : n;
+		const i32 wjob = h ? sy.job : sj.job;
+		const uint8_t *wdir = h ? dirbase + sy.diroff : dir;
+		const size_t wpitch = (size_t)DP_STRIPE_BYTES(wm);
+		uint8_t *rev = revbase + ops_off[wjob], *op = ops + ops_off[wjob];
+		int i = wn - 1, j = wm - 1, state = 0, k = 0;
+		// lane l looks at the cell e = l % 21 steps ahead along direction g = l / 21 (0: M, 1: D, 2: I)
+		const int g = lane / DP_LOOK, e = lane - g * DP_LOOK;
+		const int dlc = g == 2 ? 0 : -e, drl = g == 0 ? -2 * e : -e;
+		// The next tile is fetched while the current one is walked: an alignment path runs along the diagonal, so from (i, j)
+		// it will enter the stripe to the left near row j - (lc + 1); those diagonals (+-DP_TILE_SLACK for indels on the way)
+		// are loaded into registers now and only written to LDS when the walker gets there.  A wrong guess costs nothing but
+		// the load: the tile is then fetched the plain way.
+		// (a tile = DP_TILE_ROWS / 8 blocks of eight diagonals = 5 KB; block-aligned)
+		constexpr int TB_BLKS = DP_TILE_ROWS / 8, TB_VEC = TB_BLKS * 16 / 64;
+		static_assert(TB_VEC == 5, "the prefetched tile is five named registers (an array was kept in scratch: 96 bytes per lane)");
+		uint4 pf0 = {0, 0, 0, 0}, pf1 = pf0, pf2 = pf0, pf3 = pf0, pf4 = pf0;
 #define PF_EACH(X) X(0, pf0) X(1, pf1) X(2, pf2) X(3, pf3) X(4, pf4)
-	int pf_sp = -1, pf_lo = 0, pf_hi = -1;
-	const int rl_max = m - 1 + 63;                                      // last local diagonal of a stripe
-	const u32 *tile32 = (const u32 *)tile;
-	while (i >= 0 && j >= 0) {
-		i = __builtin_amdgcn_readfirstlane(i); j = __builtin_amdgcn_readfirstlane(j);
-		// tile: stripe sp, local diagonals rl_lo .. rl_hi
-		DPT(ntile++;)
-		const int sp = i >> 6, rl_hi = j + (i & 63);
-		int rl_lo;
-		uint4 *dst = (uint4 *)tile;
-		if (sp == pf_sp && rl_hi <= pf_hi && rl_hi - pf_lo >= 64) {
-			rl_lo = pf_lo;
-			DPT(nrun += 1 << 16;)
-#define PF_PUT(Q, R) dst[(Q) * 64 + lane] = R;
-			PF_EACH(PF_PUT)
-#undef PF_PUT
-		} else {
-			const int b_hi = rl_hi >> 3, b_lo = b_hi - (TB_BLKS - 1) > 0 ? b_hi - (TB_BLKS - 1) : 0;
-			rl_lo = b_lo << 3;
-			const uint4 *src = (const uint4 *)(dir + (size_t)sp * pitch + ((size_t)b_lo << 8));
-			const int nvec = (b_hi - b_lo + 1) * 16;
-#pragma unroll
-			for (int q2 = 0; q2 < TB_VEC; q2++) { const int id = q2 * 64 + lane; if (id < nvec) dst[id] = src[id]; }
-		}
-		pf_sp = -1;
-		{
-			const int jp = j - ((i & 63) + 1);
-			if (sp > 0 && jp >= 0) {
-				int hi = jp + 63 + DP_TILE_SLACK; hi = hi < rl_max ? hi : rl_max;
-				const int pb_hi = hi >> 3, pb_lo = pb_hi - (TB_BLKS - 1) > 0 ? pb_hi - (TB_BLKS - 1) : 0;
-				const uint4 *src = (const uint4 *)(dir + (size_t)(sp - 1) * pitch + ((size_t)pb_lo << 8));
-				const int nvec = (pb_hi - pb_lo + 1) * 16;
-#define PF_GET(Q, R) { const int id = (Q) * 64 + lane; R = src[id < nvec ? id : 0]; }
-				PF_EACH(PF_GET)
-#undef PF_GET
-				pf_sp = sp - 1; pf_lo = pb_lo << 3; pf_hi = (pb_hi << 3) + 7 < rl_max ? (pb_hi << 3) + 7 : rl_max;
-			}
-		}
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-		for (;;) {
-			// the walker state is wave-uniform: pin it to scalar registers
+		int pf_sp = -1, pf_lo = 0, pf_hi = -1;
+		const int rl_max = wm - 1 + 63;                                      // last local diagonal of a stripe
+		const u32 *tile32 = (const u32 *)tile;
+		while (i >= 0 && j >= 0) {
 			i = __builtin_amdgcn_readfirstlane(i); j = __builtin_amdgcn_readfirstlane(j);
-			state = __builtin_amdgcn_readfirstlane(state); k = __builtin_amdgcn_readfirstlane(k);
-			if (i < 0 || j < 0) break;
-			const int lc = i - (sp << 6), rl = j + lc;
-			if (lc < 0 || rl < rl_lo) break;                       // left the tile: reload
-			const int lc2 = lc + dlc, rl2 = rl + drl;
-			const bool valid = lane < 3 * DP_LOOK && lc2 >= 0 && rl2 >= rl_lo && rl2 - lc2 >= 0;
-			u32 tmp = 0xffu;
-			if (valid) {      // back to ksw2's flag byte (nibble of step k: half k / 4, oldest on top)
-				const u32 nb = (tile32[(((rl2 - rl_lo) >> 3) << 6) + lc2] >> ((((rl2 & 7) >> 2) << 4) + ((3 - (rl2 & 3)) << 2))) & 15u;
-				tmp = ((nb & 2u) ? 2u : (nb & 1u)) | ((nb & 0xCu) << 1);
+			// tile: stripe sp, local diagonals rl_lo .. rl_hi
+			DPT(ntile++;)
+			const int sp = i >> 6, rl_hi = j + (i & 63);
+			int rl_lo;
+			uint4 *dst = (uint4 *)tile;
+			if (sp == pf_sp && rl_hi <= pf_hi && rl_hi - pf_lo >= 64) {
+				rl_lo = pf_lo;
+				DPT(nrun += 1 << 16;)
+#define PF_PUT(Q, R) dst[(Q) * 64 + lane] = R;
+				PF_EACH(PF_PUT)
+#undef PF_PUT
+			} else {
+				const int b_hi = rl_hi >> 3, b_lo = b_hi - (TB_BLKS - 1) > 0 ? b_hi - (TB_BLKS - 1) : 0;
+				rl_lo = b_lo << 3;
+				const uint4 *src = (const uint4 *)(wdir + (size_t)sp * wpitch + ((size_t)b_lo << 8));
+				const int nvec = (b_hi - b_lo + 1) * 16;
+#pragma unroll
+				for (int q2 = 0; q2 < TB_VEC; q2++) { const int id = q2 * 64 + lane; if (id < nvec) dst[id] = src[id]; }
 			}
-			const u32 cur = (u32)__builtin_amdgcn_readfirstlane((int)tmp);
-			// the automaton of ksw_backtrack (:38-52) for the current cell ...
-			const int S = dp_bt_next(state, cur);
-			const int isM = S == 0 ? 1 : 0, isD = (S == 1 || S == 3) ? 1 : 0;
-			const int gS = isM ? 0 : (isD ? 1 : 2);
-			// ... and for the cells behind it while they keep the same state
-			const bool cont = valid && g == gS && (isM ? (tmp & 7) == 0 : (((tmp >> (S + 2)) & 1) != 0 || (int)(tmp & 7) == S));
-			const unsigned long long bal = __ballot(cont) >> (gS * DP_LOOK + 1);
-			int run = __builtin_ctzll(~bal);
-			run = run < DP_LOOK - 1 ? run : DP_LOOK - 1;
-			const int L = 1 + run;
-			if (lane < L) rev[k + lane] = (uint8_t)(isM ? 'M' : (isD ? 'D' : 'I'));
-			k += L; state = S; DPT(nrun++;)
-			i -= (isM | isD) ? L : 0; j -= (isM | (1 - isD)) ? L : 0;
+			pf_sp = -1;
+			{
+				const int jp = j - ((i & 63) + 1);
+				if (sp > 0 && jp >= 0) {
+					int hi = jp + 63 + DP_TILE_SLACK; hi = hi < rl_max ? hi : rl_max;
+					const int pb_hi = hi >> 3, pb_lo = pb_hi - (TB_BLKS - 1) > 0 ? pb_hi - (TB_BLKS - 1) : 0;
+					const uint4 *src = (const uint4 *)(wdir + (size_t)(sp - 1) * wpitch + ((size_t)pb_lo << 8));
+					const int nvec = (pb_hi - pb_lo + 1) * 16;
+#define PF_GET(Q, R) { const int id = (Q) * 64 + lane; R = src[id < nvec ? id : 0]; }
+					PF_EACH(PF_GET)
+#undef PF_GET
+					pf_sp = sp - 1; pf_lo = pb_lo << 3; pf_hi = (pb_hi << 3) + 7 < rl_max ? (pb_hi << 3) + 7 : rl_max;
+				}
+			}
+			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+			__builtin_amdgcn_wave_barrier();
+			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+			for (;;) {
+				// the walker state is wave-uniform: pin it to scalar registers
+				i = __builtin_amdgcn_readfirstlane(i); j = __builtin_amdgcn_readfirstlane(j);
+				state = __builtin_amdgcn_readfirstlane(state); k = __builtin_amdgcn_readfirstlane(k);
+				if (i < 0 || j < 0) break;
+				const int lc = i - (sp << 6), rl = j + lc;
+				if (lc < 0 || rl < rl_lo) break;                       // left the tile: reload
+				const int lc2 = lc + dlc, rl2 = rl + drl;
+				const bool valid = lane < 3 * DP_LOOK && lc2 >= 0 && rl2 >= rl_lo && rl2 - lc2 >= 0;
+				u32 tmp = 0xffu;
+				if (valid) {      // back to ksw2's flag byte (nibble of step k: half k / 4, oldest on top)
+					const u32 nb = (tile32[(((rl2 - rl_lo) >> 3) << 6) + lc2] >> ((((rl2 & 7) >> 2) << 4) + ((3 - (rl2 & 3)) << 2))) & 15u;
+					tmp = ((nb & 2u) ? 2u : (nb & 1u)) | ((nb & 0xCu) << 1);
+				}
+				const u32 cur = (u32)__builtin_amdgcn_readfirstlane((int)tmp);
+				// the automaton of ksw_backtrack (:38-52) for the current cell ...
+				const int S = dp_bt_next(state, cur);
+				const int isM = S == 0 ? 1 : 0, isD = (S == 1 || S == 3) ? 1 : 0;
+				const int gS = isM ? 0 : (isD ? 1 : 2);
+				// ... and for the cells behind it while they keep the same state
+				const bool cont = valid && g == gS && (isM ? (tmp & 7) == 0 : (((tmp >> (S + 2)) & 1) != 0 || (int)(tmp & 7) == S));
+				const unsigned long long bal = __ballot(cont) >> (gS * DP_LOOK + 1);
+				int run = __builtin_ctzll(~bal);
+				run = run < DP_LOOK - 1 ? run : DP_LOOK - 1;
+				const int L = 1 + run;
+				if (lane < L) rev[k + lane] = (uint8_t)(isM ? 'M' : (isD ? 'D' : 'I'));
+				k += L; state = S; DPT(nrun++;)
+				i -= (isM | isD) ? L : 0; j -= (isM | (1 - isD)) ? L : 0;
+			}
 		}
+		DPT(if (lane == 0) { ctr[sj.ctr + 42] = (u32)(wall_clock64() - T1c); ctr[sj.ctr + 43] = ntile; ctr[sj.ctr + 44] = nrun; ctr[sj.ctr + 45] = (u32)(wall_clock64() - T0c); })
+		if (lane == 0) {
+			for (; i >= 0; --i) rev[k++] = 'D';
+			for (; j >= 0; --j) rev[k++] = 'I';
+			ops_len[wjob] = k;
+		}
+		k = __builtin_amdgcn_readfirstlane(k);
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+		for (int q2 = lane; q2 < k; q2 += 64) op[q2] = rev[k - 1 - q2];
 	}
-	DPT(if (lane == 0) { ctr[sj.ctr + 42] = (u32)(wall_clock64() - T1c); ctr[sj.ctr + 43] = ntile; ctr[sj.ctr + 44] = nrun; ctr[sj.ctr + 45] = (u32)(wall_clock64() - T0c); })
-	if (lane == 0) {
-		for (; i >= 0; --i) rev[k++] = 'D';
-		for (; j >= 0; --j) rev[k++] = 'I';
-		ops_len[sj.job] = k;
+	if (SBS && h == 0) { h = 1; goto walk_back; }
+}
+
+// Forward wave-steps of a job in the lagged form and of two jobs side by side (S_end of every wave, as the kernel computes it).
+static i64 dp_steps_lagged(int m, int n)
+{
+	const int P = (n + 63) / 64; i64 s = 0;
+	for (int pp = 0; 2 * pp < P; pp++) s += 2 * pp + 1 < P ? 64 + m + std::min(n - pp * 128 - 64, 64) - 1 : m + std::min(n - pp * 128, 64) - 1;
+	return s;
+}
+static i64 dp_steps_pair(int mx, int nx, int my, int ny)
+{
+	const int PX = (nx + 63) / 64, PY = (ny + 63) / 64; i64 s = 0;
+	for (int p = 0; p < std::max(PX, PY); p++) s += std::max(p < PX ? mx + std::min(nx - p * 64, 64) - 1 : 0, p < PY ? my + std::min(ny - p * 64, 64) - 1 : 0);
+	return s;
+}
+// One workgroup list of launch_stripes: a job in the lagged form (y < 0) or two jobs side by side; x, y index the job list.
+struct DpUnit { i64 cells; size_t x; long long y; };
+// The units of one size-class segment [b, e) of `large`.  mode 0: every job alone, in the order of the list.  Otherwise the segment is put in
+// (stripe count, m) order, largest first, and neighbours are paired -- mode 1: where the pair costs fewer wave-steps than the two lagged forms
+// together; mode 2: always (tests) -- and the head of the unit list is ordered by cells again, as the job list was.
+static void dp_make_units(std::vector<LgJob> &large, size_t b, size_t e, int mode, std::vector<DpUnit> &units)
+{
+	units.clear();
+	auto cells = [&](size_t k) { return (i64)large[k].m * large[k].n; };
+	if (mode == 0 || e - b < 2) { for (size_t k = b; k < e; k++) units.push_back({ cells(k), k, -1 }); return; }
+	std::sort(large.begin() + b, large.begin() + e, [](const LgJob &p, const LgJob &q) {
+		const int Pp = (p.n + 63) / 64, Pq = (q.n + 63) / 64;
+		return Pp != Pq ? Pp > Pq : (p.m != q.m ? p.m > q.m : p.job < q.job); });
+	for (size_t k = b; k < e; ) {
+		const bool pair = k + 1 < e && (mode == 2 || dp_steps_pair(large[k].m, large[k].n, large[k + 1].m, large[k + 1].n) < dp_steps_lagged(large[k].m, large[k].n) + dp_steps_lagged(large[k + 1].m, large[k + 1].n));
+		if (pair) { units.push_back({ cells(k) + cells(k + 1), k, (long long)(k + 1) }); k += 2; }
+		else { units.push_back({ cells(k), k, -1 }); k++; }
 	}
-	k = __builtin_amdgcn_readfirstlane(k);
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-	for (int q2 = lane; q2 < k; q2 += 64) op[q2] = rev[k - 1 - q2];
+	auto by_cells = [&](const DpUnit &p, const DpUnit &q) { return p.cells != q.cells ? p.cells > q.cells : large[p.x].job < large[q.x].job; };
+	if (units.size() > 512) std::partial_sort(units.begin(), units.begin() + 256, units.end(), by_cells);
+	else std::sort(units.begin(), units.end(), by_cells);
 }
 
 // Striped kernel for a list of large jobs on stream `ss` (batches so that the direction bytes of one batch fit the
@@ -452,7 +528,8 @@ int launch_stripes(gsa_ctx *c, hipStream_t st, std::vector<LgJob> &large, const 
 		// the segments of this batch: [first, s0) above DP_LDS_M, [s0, st) above DP_CLASS_TOP, [st, s1) above DP_CLASS_M, [s1, first + cnt) below
 		const size_t s0 = std::min(std::max(n_xl, first), first + cnt), stp = std::min(std::max(n_top, first), first + cnt), s1 = std::min(std::max(n_hi, first), first + cnt);
 		constexpr int NSEG = 4;
-		struct Seg { size_t b, e; int mmax, wpb, mpad, lds_rows; size_t dyn_lds; i32 *b2j; i32 nblocks; } seg[NSEG] = { { first, s0 }, { s0, stp }, { stp, s1 }, { s1, first + cnt } };
+		// (a segment is up to two launches: [0] its jobs in the lagged form, [1] its pairs side by side)
+		struct Seg { size_t b, e; int mmax, wpb, mpad, lds_rows; size_t dyn_lds; i32 *b2j[2]; i32 nblocks[2]; std::vector<DpUnit> units; } seg[NSEG] = { { first, s0 }, { s0, stp }, { stp, s1 }, { s1, first + cnt } };
 		size_t nb_ub = 0;
 		for (Seg &sg : seg) {
 			sg.mmax = 1;
@@ -462,25 +539,45 @@ int launch_stripes(gsa_ctx *c, hipStream_t st, std::vector<LgJob> &large, const 
 			sg.lds_rows = (sg.mmax + 15) & ~15;
 			sg.dyn_lds = (size_t)sg.mpad * 4 + (sg.wpb > 1 ? (size_t)(sg.wpb - 1) * sg.lds_rows * 4 : 0);      // (one selector dword per row)
 			if (sg.dyn_lds < (size_t)DP_TILE_ROWS * 32) sg.dyn_lds = (size_t)DP_TILE_ROWS * 32;      // (the traceback tile -- nibbles -- lives in the same bytes)
-			for (size_t k = sg.b; k < sg.e; k++) nb_ub += (size_t)((((large[k].n + 63) / 64 + 1) / 2 + sg.wpb - 1) / sg.wpb);      // (a wave takes two stripes)
+			for (size_t k = sg.b; k < sg.e; k++) nb_ub += (size_t)(((large[k].n + 63) / 64 + sg.wpb - 1) / sg.wpb);      // (a wave takes two stripes, or one of each job of a pair)
+			// pairs only where four waves share a workgroup: the one-wave class stays as it is (dp_safe: one job per launch, nothing to pair)
+			// ... and, by default, only in a class long enough to keep the chip's workgroup slots full (about 1 300 four-wave workgroups): a shorter list is
+			// bound by its longest chain of waves, not by instructions, and a pair halves its workgroups and walks back two jobs on one wave -- with every
+			// class paired yeast's lists of a few hundred jobs ran 12 % slower per step (3.12 -> 3.50 ms; profiles/dp_pairs_ab.txt section 4).
+			// Such a class takes the parent's path untouched: its order, one launch, no second stream.  dp_pair 3 (tests): the rule without this condition
+			int mode = sg.wpb == 4 ? c->opt.dp_pair : 0;
+			if (mode == 1 && sg.e - sg.b < DP_PAIR_MIN_JOBS) mode = 0;
+			dp_make_units(large, sg.b, sg.e, mode == 3 ? 1 : mode, sg.units);
+			for (const DpUnit &u : sg.units) { c->dp_stats[0] += u.y >= 0 ? 2 : 1; c->dp_stats[1] += u.y >= 0 ? 2 : 0; }
 		}
 		if (!pin_ensure<char>(c, psj, (cnt + 1) * sizeof(StripeJob) + (nb_ub + 2) * 4)) return GSA_ERR_NOMEM;
 		StripeJob *sj = psj.as<StripeJob>();
 		i32 *b2j_all = (i32 *)(sj + cnt + 1);
-		i64 dbytes = 128, bwords = 0; i32 nctr = NSEG; size_t b2j_used = 0;      // (ctr[0 .. NSEG-1]: launch tickets of the size classes)
+		i64 dbytes = 128, bwords = 0; i32 nctr = 2 * NSEG; size_t b2j_used = 0, nsj = 0;      // (ctr[0 .. 2 NSEG - 1]: launch tickets of the size classes' two forms)
 		for (Seg &sg : seg) {
-			sg.b2j = b2j_all + b2j_used; sg.nblocks = 0;
-			for (size_t k = sg.b; k < sg.e; k++) {
-				const LgJob &g = large[k];
-				const i64 cells = (((i64)g.n + 63) / 64) * (i64)DP_STRIPE_BYTES(g.m);   // stripe-local direction nibbles
-				StripeJob s; s.job = g.job; s.m = g.m; s.n = g.n; s.P = (g.n + 63) / 64;
-				s.diroff = dbytes; dbytes += cells + 128;
-				s.bndoff = bwords; bwords += (i64)(s.P - 1) * g.m;
-				s.ctr = nctr++; s.first_block = sg.nblocks;
-				for (int b = 0; b < ((s.P + 1) / 2 + sg.wpb - 1) / sg.wpb; b++) sg.b2j[sg.nblocks++] = (i32)(k - first);
-				sj[k - first] = s;
+			for (int form = 0; form < 2; form++) {
+				sg.b2j[form] = b2j_all + b2j_used; sg.nblocks[form] = 0;
+				for (const DpUnit &u : sg.units) {
+					if ((u.y >= 0) != (form == 1)) continue;
+					// the table entry of the job / of X and, behind it, of Y
+					const int nj = form ? 2 : 1;
+					StripeJob s[2];
+					for (int q = 0; q < nj; q++) {
+						const LgJob &g = large[q ? (size_t)u.y : u.x];
+						const i64 cells = (((i64)g.n + 63) / 64) * (i64)DP_STRIPE_BYTES(g.m);   // stripe-local direction nibbles
+						s[q].job = g.job; s[q].m = g.m; s[q].n = g.n; s[q].P = (g.n + 63) / 64;
+						s[q].diroff = dbytes; dbytes += cells + 128;
+						s[q].bndoff = 0; s[q].ctr = 0; s[q].first_block = sg.nblocks[form];
+					}
+					// boundary columns and the ticket are the (virtual) job's
+					const int waves = form ? std::max(s[0].P, s[1].P) : (s[0].P + 1) / 2, rows = form ? std::max(s[0].m, s[1].m) : s[0].m;
+					s[0].bndoff = bwords; bwords += (i64)((form ? waves : s[0].P) - 1) * rows;
+					s[0].ctr = nctr++;
+					for (int b = 0; b < (waves + sg.wpb - 1) / sg.wpb; b++) sg.b2j[form][sg.nblocks[form]++] = (i32)nsj;
+					for (int q = 0; q < nj; q++) sj[nsj++] = s[q];
+				}
+				b2j_used += (size_t)sg.nblocks[form];
 			}
-			b2j_used += (size_t)sg.nblocks;
 		}
 		const size_t last = first + cnt;
 		uint8_t *dir = dev_ensure<uint8_t>(c, c->d_scan2, (size_t)dbytes + 512);
@@ -498,17 +595,27 @@ int launch_stripes(gsa_ctx *c, hipStream_t st, std::vector<LgJob> &large, const 
 		//  was measured at 250 Mb: same step time, the refinement passes beside them starve instead: the chip is busy either way)
 		// (option dp_side: the lower class on a stream of its own -- it then starts with the upper one instead of behind it; the classes share
 		//  nothing but the error word: tickets per class, direction / boundary bytes per job)
-		const bool side = c->opt.dp_side && c->stream_aux[3] && seg[NSEG - 1].nblocks > 0 && (seg[0].nblocks > 0 || seg[1].nblocks > 0 || seg[2].nblocks > 0);
-		if (side) { GSA_CHECK(c, hipEventRecord(c->ev[24], st)); GSA_CHECK(c, hipStreamWaitEvent(c->stream_aux[3], c->ev[24], 0)); }
+		auto blocks_of = [&](int si) { return seg[si].nblocks[0] + seg[si].nblocks[1]; };
+		const bool side = c->opt.dp_side && c->stream_aux[3] && blocks_of(NSEG - 1) > 0 && (blocks_of(0) > 0 || blocks_of(1) > 0 || blocks_of(2) > 0);
+		// A class's unpaired jobs -- what found no partner in (stripe count, m) order: the odd sizes, the largest among them -- run BESIDE its pairs, on
+		// stream_aux[3]: behind each other on one stream, a 250 Mb contig alone waited 2 ms for a few dozen long lagged jobs before its pairs started
+		// (one context, every class paired: 11.47 -> 13.32 ms per contig behind each other, 12.68 ms beside; profiles/dp_pairs_ab.txt section 4).  The two launches share nothing but the error word.
+		bool beside = false;
+		for (const Seg &sg : seg) if (sg.nblocks[0] > 0 && sg.nblocks[1] > 0 && c->stream_aux[3]) beside = true;
+		if (side || beside) { GSA_CHECK(c, hipEventRecord(c->ev[24], st)); GSA_CHECK(c, hipStreamWaitEvent(c->stream_aux[3], c->ev[24], 0)); }
 		hipStream_t st_main = st;
 		for (int si = 0; si < NSEG; si++) {
 			const Seg &sg = seg[si];
-			if (sg.nblocks == 0) continue;
-			hipStream_t st = (side && si == NSEG - 1) ? c->stream_aux[3] : st_main;
-			if (sg.wpb == 4) hipLaunchKernelGGL(k_dp_stripe<4>, dim3((unsigned)sg.nblocks), dim3(256), sg.dyn_lds, st, (const i32 *)sg.b2j, (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), si);
-			else hipLaunchKernelGGL(k_dp_stripe<1>, dim3((unsigned)sg.nblocks), dim3(64), sg.dyn_lds, st, (const i32 *)sg.b2j, (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), si);
+			hipStream_t st_seg = (side && si == NSEG - 1) ? c->stream_aux[3] : st_main;
+			hipStream_t st = (beside && sg.nblocks[1] > 0) ? c->stream_aux[3] : st_seg;      // (of the lagged launch)
+			c->dp_stats[2] += sg.nblocks[0] > 0; c->dp_stats[3] += sg.nblocks[1] > 0;
+			if (sg.nblocks[0] > 0) {
+				if (sg.wpb == 4) hipLaunchKernelGGL((k_dp_stripe<4, 0>), dim3((unsigned)sg.nblocks[0]), dim3(256), sg.dyn_lds, st, (const i32 *)sg.b2j[0], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si);
+				else hipLaunchKernelGGL((k_dp_stripe<1, 0>), dim3((unsigned)sg.nblocks[0]), dim3(64), sg.dyn_lds, st, (const i32 *)sg.b2j[0], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si);
+			}
+			if (sg.nblocks[1] > 0) hipLaunchKernelGGL((k_dp_stripe<4, 1>), dim3((unsigned)sg.nblocks[1]), dim3(256), sg.dyn_lds, st_seg, (const i32 *)sg.b2j[1], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si + 1);
 		}
-		if (side) { GSA_CHECK(c, hipEventRecord(c->ev[25], c->stream_aux[3])); GSA_CHECK(c, hipStreamWaitEvent(st, c->ev[25], 0)); }
+		if (side || beside) { GSA_CHECK(c, hipEventRecord(c->ev[25], c->stream_aux[3])); GSA_CHECK(c, hipStreamWaitEvent(st, c->ev[25], 0)); }
 		GSA_CHECK(c, hipGetLastError());
 		DPT(GSA_CHECK(c, hipStreamSynchronize(st)); if (cnt == 1) { u32 hh[6]; hipMemcpy(hh, ctr + sj[0].ctr + 40, 24, hipMemcpyDeviceToHost); fprintf(stderr, "[dp] %d x %d: fwd0 %.1f us  fwdlast %.1f us  traceback %.1f us (tiles %u runs %u)  total %.1f us\n", sj[0].m, sj[0].n, hh[0] * 0.01, hh[1] * 0.01, hh[2] * 0.01, hh[3], hh[4], hh[5] * 0.01); })
 		if (last < large.size()) {

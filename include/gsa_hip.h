@@ -179,6 +179,9 @@ void gsa_release_reserved(int device);
  *                    workgroup and 160-start segments (many chunks), 1 = one chunk per workgroup and 40-start segments (few).  Results do not depend on it
  *   "dp_side"        1 = the striped DP launches its lower size class on a stream of its own, beside the upper class, instead of behind it (measured: the DP
  *                    span of a 250 Mb contig 4.9 -> 1.9 ms, but the refinement passes beside it starve: contig latency 13.7 -> 14.3 ms, throughput -4 % / +4 %); default 0
+ *   "dp_pair"        the striped DP puts two jobs of a size class side by side into the 16-bit halves of a wavefront: 1 (default) = where that costs fewer
+ *                    wave-steps than the two jobs one after the other and the class holds at least 4096 jobs (shorter lists are bound by their longest
+ *                    job, not by instructions), 0 = never, 2 = every two neighbours, 3 = by the step count alone (2, 3: tests).  Results do not depend on it
  *   "walk_chain_min" seeds; a contig with more seeds than this walks its window chain (chaining, GSAlign.cpp:326-338) in slices of the candidate list,
  *                    one launch (default 100 000; below that one workgroup holds the chain in LDS).  Results do not depend on it (tests: 0)
  *   "pd_two_level_min" blocks; PosDiff bitmaps larger than this are scanned in two passes (touched blocks listed, then counted); default 2 000 000
@@ -670,6 +673,9 @@ int gsa_set_profiling(gsa_ctx *ctx, int flags);
  * `freq > MaxSeedFreq` reject-and-restart regime of bwt_search.cpp:177-182, or -sen), [2] most wave-iterations of a chunk,
  * [3..5] slowest chunk: round 1 / resolver / up to the marks, in 10 ns ticks; [6..7] reserved. */
 int gsa_get_seed_stats(gsa_ctx *ctx, uint64_t stats[8]);
+/* What the striped gap DP launched since the context was made (sums; a clone starts at zero): [0] jobs, [1] of them side by side with a partner
+ * (option "dp_pair"), [2] launches of the lagged form, [3] launches of the side-by-side form. */
+int gsa_get_dp_stats(gsa_ctx *ctx, uint64_t stats[4]);
 
 #ifdef __cplusplus
 }
