@@ -30,6 +30,7 @@ EXPORTS = [
     "gsa_proj_open", "gsa_proj_close", "gsa_proj_clear", "gsa_project", "gsa_proj_fetch", "gsa_proj_merge", "gsa_get_proj_timing",
     "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
     "gsa_create_from_pac", "gsa_export_index_table",
+    "gsa_build_index_opts", "gsa_get_index_build_stats2", "gsa_set_index_build_caps", "gsa_plan_index_batches",
 ]
 
 
@@ -318,18 +319,25 @@ def index_sizes(G: int):
 BUILD_INDEX_ARGTYPES = [C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
 
 
-def build_index_arrays(pac, G: int, device: int = 0):
-    """gsa_build_index: the .pac bytes of G forward bases -> (hdr uint64[5] = [primary, L2[1..4]], bwt uint32[], sa uint64[]), the arrays of
-    indexio.BwaIndex, suffix-sorted on the GPU.  Raises GsaError (.code = the library's error code) when the library refuses."""
+BUILD_INDEX_OPTS_ARGTYPES = [C.c_int, C.c_void_p, C.c_int64, C.c_uint32, C.c_int64, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+BUILD_AUTO, BUILD_WIDE = 0, 1      # GSA_BUILD_* (include/gsa_hip.h)
+CREATE_SORT_WIDE = 2               # GSA_CREATE_SORT_WIDE
+
+
+def build_index_arrays(pac, G: int, device: int = 0, wide: bool = False, batch_cap: int = 0, occ_segment: int = 0):
+    """gsa_build_index_opts: the .pac bytes of G forward bases -> (hdr uint64[5] = [primary, L2[1..4]], bwt uint32[], sa uint64[]), the arrays of
+    indexio.BwaIndex, suffix-sorted on the GPU.  wide: the batched 64-bit sorter at any size (GSA_BUILD_WIDE; otherwise it runs over 1 073 741 822 bases only),
+    batch_cap / occ_segment: its batch size and Occ scan segment (0: the defaults).  Raises GsaError (.code = the library's error code) when the library refuses."""
     lib = load_library()
-    lib.gsa_build_index.argtypes = BUILD_INDEX_ARGTYPES
+    lib.gsa_build_index_opts.argtypes = BUILD_INDEX_OPTS_ARGTYPES
     pac = np.ascontiguousarray(pac, dtype=np.uint8)
     if G <= 0 or pac.size < (G + 3) // 4:
         raise ValueError("pac holds fewer than G bases")
     bw, ns = index_sizes(G)
     bwt = np.zeros(bw, np.uint32); sa = np.zeros(ns, np.uint64)
     primary = C.c_uint64(); L2 = (C.c_uint64 * 5)()
-    rc = lib.gsa_build_index(int(device), C.c_void_p(pac.ctypes.data), int(G), C.byref(primary), L2, C.c_void_p(bwt.ctypes.data), C.c_void_p(sa.ctypes.data))
+    rc = lib.gsa_build_index_opts(int(device), C.c_void_p(pac.ctypes.data), int(G), BUILD_WIDE if wide else BUILD_AUTO, int(batch_cap), int(occ_segment),
+                                  C.byref(primary), L2, C.c_void_p(bwt.ctypes.data), C.c_void_p(sa.ctypes.data))
     if rc != 0:
         e = GsaError(f"gsa_build_index -> {rc}: {lib.gsa_last_error(None).decode()}"); e.code = rc
         raise e
@@ -343,6 +351,38 @@ def index_build_stats():
     lib.gsa_get_index_build_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     lib.gsa_get_index_build_stats(C.byref(ms), C.byref(rounds))
     return float(ms.value), int(rounds.value)
+
+
+def index_build_stats2():
+    """gsa_get_index_build_stats2: (batches that held a suffix, peak device bytes, suffixes still tied after the first pass) of the calling thread's last build;
+    (0, 0, 0) after the narrow sorter."""
+    lib = load_library()
+    batches, peak, active = C.c_int64(), C.c_uint64(), C.c_int64()
+    lib.gsa_get_index_build_stats2.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]
+    lib.gsa_get_index_build_stats2(C.byref(batches), C.byref(peak), C.byref(active))
+    return int(batches.value), int(peak.value), int(active.value)
+
+
+def set_index_build_caps(batch_cap: int = 0, occ_segment: int = 0, active_cap: int = 0) -> None:
+    """gsa_set_index_build_caps (test support, process-wide; 0: the defaults): the wide builder's batch cap and Occ segment inside
+    Aligner.from_reference(sort_wide=True), and a limit on the entries of its list of tied suffixes in every wide build."""
+    lib = load_library()
+    lib.gsa_set_index_build_caps.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+    if lib.gsa_set_index_build_caps(int(batch_cap), int(occ_segment), int(active_cap)) != 0:
+        raise GsaError(f"gsa_set_index_build_caps: {lib.gsa_last_error(None).decode()}")
+
+
+def plan_index_batches(hist, batch_cap: int):
+    """gsa_plan_index_batches: (first[n_batches + 1], base[n_batches + 1]) of the wide builder's batches for the class counts `hist`; GsaError (.code) when refused."""
+    lib = load_library()
+    lib.gsa_plan_index_batches.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    hist = np.ascontiguousarray(hist, dtype=np.uint64)
+    first = np.zeros(hist.size + 1, np.int64); base = np.zeros(hist.size + 1, np.uint64); nb = C.c_int64()
+    rc = lib.gsa_plan_index_batches(C.c_void_p(hist.ctypes.data), hist.size, int(batch_cap), hist.size, C.c_void_p(first.ctypes.data), C.c_void_p(base.ctypes.data), C.byref(nb))
+    if rc != 0:
+        e = GsaError(f"gsa_plan_index_batches -> {rc}: {lib.gsa_last_error(None).decode()}"); e.code = rc
+        raise e
+    return first[:nb.value + 1].copy(), base[:nb.value + 1].copy()
 
 
 def bind_host_thread(device: int = 0) -> None:
@@ -544,7 +584,7 @@ class Aligner:
         self._options_from_env()
 
     @classmethod
-    def from_reference(cls, pac, G: int, chr_len, device: int = 0, wide: bool = False, kmer_k: int = 0, **params) -> "Aligner":
+    def from_reference(cls, pac, G: int, chr_len, device: int = 0, wide: bool = False, kmer_k: int = 0, sort_wide: bool = False, **params) -> "Aligner":
         """gsa_create_from_pac: a context from the .pac bytes of the G forward bases and the sequence lengths (hostlib.reference_from_fasta gives them) -- the index is
         built in device memory, no index file and no host index array exists (self.idx is None).  Raises GsaError (.code = the library's error code)."""
         self = cls.__new__(cls)
@@ -557,7 +597,7 @@ class Aligner:
         wide = wide or os.environ.get("GSA_FORCE_WIDE", "0") not in ("", "0")
         kmer_k = kmer_k or int(os.environ.get("GSA_KMER_K", "0") or 0)
         prio = int(os.environ.get("GSA_PRIO", "0") or 0)
-        flags = (1 if wide else 0) | ((kmer_k & 15) << 8) | ((prio & 3) << 16)
+        flags = (1 if wide else 0) | ((kmer_k & 15) << 8) | ((prio & 3) << 16) | (CREATE_SORT_WIDE if sort_wide else 0)      # (sort_wide: GSA_CREATE_SORT_WIDE, the batched 64-bit sorter; implies wide)
         self.ctx = C.c_void_p()
         p = self._params(**params)
         rc = self.lib.gsa_create_from_pac(int(device), C.c_void_p(pac.ctypes.data), int(G), C.c_void_p(chr_len.ctypes.data), int(chr_len.size), C.byref(p), flags, C.byref(self.ctx))

@@ -1,6 +1,7 @@
 // gsalign_amd/csrc/gsa_create.hip -- the life cycle of a context behind the C ABI (include/gsa_hip.h): constructors and gsa_destroy, the index reservation, parameters
 // and options, memory helpers, the index builder's wrapper.  The text of gsa_last_error(NULL) is private to this file: gsa_fail(nullptr, ...) sets it.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <pthread.h>
 #include <sched.h>
@@ -29,9 +30,9 @@ static int create_device_ok(const char *who, int device)
 	if (device < 0 || device >= ndev) return gsa_fail(nullptr, GSA_ERR_ARG, std::string(who) + ": bad device ordinal");
 	return GSA_OK;
 }
-static int create_flags_ok(const char *who, uint32_t flags)
+static int create_flags_ok(const char *who, uint32_t flags, uint32_t extra = 0u)
 {
-	if (flags & ~(uint32_t)(GSA_CREATE_WIDE | GSA_CREATE_KMER_K(15) | GSA_CREATE_PRIO(3) | GSA_CREATE_REF_PAC)) return gsa_fail(nullptr, GSA_ERR_ARG, std::string(who) + ": unknown flag");
+	if (flags & ~(uint32_t)(GSA_CREATE_WIDE | GSA_CREATE_KMER_K(15) | GSA_CREATE_PRIO(3) | GSA_CREATE_REF_PAC | extra)) return gsa_fail(nullptr, GSA_ERR_ARG, std::string(who) + ": unknown flag");
 	if (((flags >> 8) & 15u) == 1) return gsa_fail(nullptr, GSA_ERR_ARG, std::string(who) + ": GSA_CREATE_KMER_K takes 2 .. 15 (0: chosen by text length and free memory)");
 	return GSA_OK;
 }
@@ -122,6 +123,10 @@ void *dev_take_reserved(int device, size_t bytes, size_t *got)
 	for (int k = 0; k < 2; k++) { ReservedBuf &r = g_res[device & 63][k]; if (r.p && r.bytes >= bytes && r.bytes <= bytes + bytes / 8 + 4096) { void *p = r.p; *got = r.bytes; r.p = nullptr; r.bytes = 0; return p; } }
 	return nullptr;
 }
+
+// the wide index builder (k_index_wide.hip): its bound, and the caps gsa_create_from_pac hands it (gsa_set_index_build_caps)
+static const int64_t IX_WIDE_MAX_G = 4294967295ll;
+static std::atomic<int64_t> g_ix_batch_cap{ 0 }, g_ix_occ_segment{ 0 }, g_ix_active_cap{ 0 };
 
 // ChrLocMap (bwt_index.cpp:240-253) as a sorted table of last coordinates, host and device; the error text goes to gsa_last_error(NULL) (the caller destroys c)
 static int ctx_chr_tables(gsa_ctx *c, const int32_t *chr_len, int32_t n_chr, i64 G, const char *who)
@@ -228,9 +233,12 @@ int gsa_create_from_pac(int device, const uint8_t *pac, int64_t G, const int32_t
 {
 	if (!pac || !chr_len || !out || G <= 0 || n_chr <= 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_create_from_pac: bad argument");
 	{ int64_t tot = 0; for (int i = 0; i < n_chr; i++) { if (chr_len[i] <= 0) { tot = -1; break; } tot += chr_len[i]; } if (tot != G) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_create_from_pac: sum(chr_len) != G"); }
-	if (int rc = create_flags_ok("gsa_create_from_pac", flags)) return rc;
-	// the bound of the device builder (gsa_build_index): 32-bit suffix indices
-	if (2 * G + 1 > (1ll << 31) - 2) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_create_from_pac: the reference is longer than 1 073 741 822 bases (the device builder sorts 32-bit suffix indices)");
+	if (int rc = create_flags_ok("gsa_create_from_pac", flags, GSA_CREATE_SORT_WIDE)) return rc;
+	const bool sort_wide = (flags & GSA_CREATE_SORT_WIDE) != 0;
+	if (sort_wide) flags |= GSA_CREATE_WIDE;      // (the 64-bit SA array is adopted as it is)
+	// the bound of the device builder (gsa_build_index): 32-bit suffix indices; of the wide one (gsa_build_index_opts): a 33-bit rank in a sort key
+	if (sort_wide && G > IX_WIDE_MAX_G) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_create_from_pac: the reference is longer than 4 294 967 295 bases (the wide device builder's sort key holds a 33-bit rank)");
+	if (!sort_wide && 2 * G + 1 > (1ll << 31) - 2) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_create_from_pac: the reference is longer than 1 073 741 822 bases (the device builder sorts 32-bit suffix indices)");
 	if (int rc = create_device_ok("gsa_create_from_pac", device)) return rc;
 	gsa_ctx *c = ctx_new(device, flags);
 	if (!c->err.empty()) return ctx_abandon(c, GSA_ERR_HIP, "gsa_create_from_pac: hipSetDevice");
@@ -240,7 +248,7 @@ int gsa_create_from_pac(int device, const uint8_t *pac, int64_t G, const int32_t
 	c->d_ref.cap = (size_t)2 * G + 64;
 	if (int rc = ctx_chr_tables(c, chr_len, n_chr, G, "gsa_create_from_pac")) return ctx_abandon(c, rc);
 	c->di.ref = c->d_ref.as<uint8_t>(); c->di.G = G;      // (the other tables: the builders below)
-	if (int rc = build_tables_from_pac(c, pac, G)) return ctx_abandon(c, rc);
+	if (int rc = sort_wide ? build_tables_from_pac_wide(c, pac, G, g_ix_batch_cap.load(), g_ix_occ_segment.load(), g_ix_active_cap.load()) : build_tables_from_pac(c, pac, G)) return ctx_abandon(c, rc);
 	if (int rc = build_ref2(c)) return ctx_abandon(c, rc);
 	if (int rc = build_kmer_table(c)) return ctx_abandon(c, rc);
 	gsa_params dp; gsa_default_params(&dp);
@@ -545,26 +553,62 @@ int gsa_index_sizes(int64_t G, uint64_t *bwt_words, uint64_t *n_sa)
 	*n_sa = (S + 32) / 32;
 	return GSA_OK;
 }
-static thread_local double g_ix_ms = 0; static thread_local int32_t g_ix_rounds = 0;
-int gsa_build_index(int device, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
+static thread_local double g_ix_ms = 0; static thread_local int32_t g_ix_rounds = 0; static thread_local int64_t g_ix_batches = 0, g_ix_active = 0; static thread_local uint64_t g_ix_peak = 0;
+// A context with no index: the device, one stream, the mailbox the fused passes draw their tickets from; the sort's scratch (tmp) and the look-back status words
+// grow on first use.  No uploader thread, no events, no auxiliary streams.  gsa_destroy frees it like any other context.
+static int ix_bare_ctx(const char *who, int device, gsa_ctx **out)
 {
-	if (!pac || !primary || !L2 || !bwt || !sa || G <= 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_build_index: bad argument");
-	// 32-bit suffix indices, ranks and scatter positions: the text with its '$' has at most 2^31 - 2 suffixes (the bound of the host builder's 32-bit instance)
-	if (2 * G + 1 > (1ll << 31) - 2) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_build_index: the reference is longer than 1 073 741 822 bases (the device builder sorts 32-bit suffix indices)");
-	if (int rc = create_device_ok("gsa_build_index", device)) return rc;
-	// A context with no index: the device, one stream, the mailbox the fused passes draw their tickets from; the sort's scratch (tmp) and the look-back status words
-	// grow on first use.  No uploader thread, no events, no auxiliary streams.  gsa_destroy frees it like any other context.
 	gsa_ctx *c = new gsa_ctx();
 	c->device = device;
 	hipError_t e = hipSetDevice(device);
 	if (e == hipSuccess) e = hipStreamCreate(&c->stream);
 	if (e == hipSuccess) e = hipMalloc(&c->d_mail.p, MAIL_N * sizeof(i32));
 	if (e == hipSuccess) { c->d_mail.cap = MAIL_N * sizeof(i32); e = hipMemset(c->d_mail.p, 0, MAIL_N * sizeof(i32)); }
-	if (e != hipSuccess) { (void)hipGetLastError(); return ctx_abandon(c, GSA_ERR_HIP, std::string("gsa_build_index: device set-up: ") + hipGetErrorString(e)); }
+	if (e != hipSuccess) { (void)hipGetLastError(); return ctx_abandon(c, GSA_ERR_HIP, std::string(who) + ": device set-up: " + hipGetErrorString(e)); }
+	*out = c;
+	return GSA_OK;
+}
+int gsa_build_index(int device, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
+{
+	if (!pac || !primary || !L2 || !bwt || !sa || G <= 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_build_index: bad argument");
+	// 32-bit suffix indices, ranks and scatter positions: the text with its '$' has at most 2^31 - 2 suffixes (the bound of the host builder's 32-bit instance)
+	if (2 * G + 1 > (1ll << 31) - 2) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_build_index: the reference is longer than 1 073 741 822 bases (the device builder sorts 32-bit suffix indices)");
+	if (int rc = create_device_ok("gsa_build_index", device)) return rc;
+	gsa_ctx *c = nullptr;
+	if (int rc = ix_bare_ctx("gsa_build_index", device, &c)) return rc;
 	double ms = 0; int32_t rounds = 0;
 	if (int rc = build_index_device(c, pac, G, primary, L2, bwt, sa, &ms, &rounds)) { g_create_error = c->err; return ctx_abandon(c, rc); }
-	g_ix_ms = ms; g_ix_rounds = rounds;
+	g_ix_ms = ms; g_ix_rounds = rounds; g_ix_batches = 0; g_ix_peak = 0; g_ix_active = 0;
 	gsa_destroy(c);
+	return GSA_OK;
+}
+int gsa_build_index_opts(int device, const uint8_t *pac, int64_t G, uint32_t flags, int64_t batch_cap, int64_t occ_segment, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
+{
+	if (!pac || !primary || !L2 || !bwt || !sa || G <= 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_build_index_opts: bad argument");
+	if (flags & ~(uint32_t)GSA_BUILD_WIDE) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_build_index_opts: unknown flag");
+	if (batch_cap < 0 || occ_segment < 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_build_index_opts: batch_cap and occ_segment are 0 (the default) or positive");
+	if (G > IX_WIDE_MAX_G) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_build_index_opts: the reference is longer than 4 294 967 295 bases (the wide device builder's sort key holds a 33-bit rank)");
+	const bool wide = (flags & GSA_BUILD_WIDE) != 0 || 2 * G + 1 > (1ll << 31) - 2;
+	if (!wide) return gsa_build_index(device, pac, G, primary, L2, bwt, sa);
+	if (int rc = create_device_ok("gsa_build_index_opts", device)) return rc;
+	gsa_ctx *c = nullptr;
+	if (int rc = ix_bare_ctx("gsa_build_index_opts", device, &c)) return rc;
+	double ms = 0; int32_t rounds = 0; i64 batches = 0, active = 0; u64 peak = 0;
+	if (int rc = build_index_device_wide(c, pac, G, batch_cap, occ_segment, g_ix_active_cap.load(), primary, L2, bwt, sa, &ms, &rounds, &batches, &peak, &active)) { g_create_error = c->err; return ctx_abandon(c, rc); }
+	g_ix_ms = ms; g_ix_rounds = rounds; g_ix_batches = batches; g_ix_peak = peak; g_ix_active = active;
+	gsa_destroy(c);
+	return GSA_OK;
+}
+int gsa_get_index_build_stats2(int64_t *batches, uint64_t *peak_bytes, int64_t *active_suffixes)
+{
+	if (!batches || !peak_bytes || !active_suffixes) return GSA_ERR_ARG;
+	*batches = g_ix_batches; *peak_bytes = g_ix_peak; *active_suffixes = g_ix_active;
+	return GSA_OK;
+}
+int gsa_set_index_build_caps(int64_t batch_cap, int64_t occ_segment, int64_t active_cap)
+{
+	if (batch_cap < 0 || occ_segment < 0 || active_cap < 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_set_index_build_caps: 0 (the default) or positive");
+	g_ix_batch_cap.store(batch_cap); g_ix_occ_segment.store(occ_segment); g_ix_active_cap.store(active_cap);
 	return GSA_OK;
 }
 int gsa_get_index_build_stats(double *ms, int32_t *rounds)

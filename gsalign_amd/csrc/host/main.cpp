@@ -5,7 +5,7 @@
 // pthread stages.  Extra flags: -gpu LIST (device ordinals, comma separated: the query contigs shard over them with the
 // index replicated), -ctx N (contexts per GPU: gsa_clone, contigs overlap on one device) and -timing
 // (one JSON line on stderr: where the wall time of the run went).  -gpuindex: an index that has to be built (`index`, or -r) gets its BWT/SA half from the
-// GPU (gsa_build_index) instead of the host's suffix sorters; the files are the same bytes.  -memindex (with -r): no index file at all -- the reference FASTA is
+// GPU (gsa_build_index_opts) instead of the host's suffix sorters; the files are the same bytes.  -memindex (with -r): no index file at all -- the reference FASTA is
 // parsed (gsah_reference_from_fasta) and the first GPU's context is made from its .pac bytes in device memory (gsa_create_from_pac).  -lift FILE: the reference positions
 // listed in FILE (name, 1-based position; a VCF works as it is) are carried through every contig's alignment on the GPU (gsa_lift) and written to <prefix>.lift.tsv.
 // -track W: the reference sequences in windows of W bases -- covered, matching, mismatching, deleted and inserted bases per window and query contig, computed on the GPU
@@ -61,17 +61,20 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -track INT     per window of INT reference bases and query sequence: covered / matching / mismatching / deleted / inserted bases, computed on the GPU (gsa_ref_track): <prefix>.track.tsv\n");
 	fprintf(stderr, "         -chain         write every alignment as a UCSC chain (liftOver, CrossMap), its segments computed on the GPU (gsa_block_segs): <prefix>.chain [false]\n");
 	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
-	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index), references up to 1.07 Gbp [false]\n", prog);
-	fprintf(stderr, "         -memindex      with -r: build the index in GPU memory (gsa_create_from_pac) and align against it; no index file is written or read, references up to 1.07 Gbp [false]\n\n");
+	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index_opts; over 1.07 Gbp its batched 64-bit sorter) [false]\n", prog);
+	fprintf(stderr, "         -memindex      with -r: build the index in GPU memory (gsa_create_from_pac) and align against it; no index file is written or read (over 1.07 Gbp: the batched 64-bit sorter) [false]\n\n");
 }
 
-// the index of `fasta` under `prefix`; on_gpu: the BWT/SA half from gsa_build_index on `device` (a reference over its bound: one line, then the host builder).
-// Returns 0, 1 (the builder's error: printed) or 2 (the GPU's error: printed).
+// GSA_INDEX_64BIT=1: the wide device builder on any input (as it forces the wide host sorter); GSA_INDEX_BATCH=N: its batch cap (how the tests reach several batches with a small fixture)
+static bool env_index_wide() { const char *e = getenv("GSA_INDEX_64BIT"); return e && *e && *e != '0'; }
+static int64_t env_index_batch() { const char *e = getenv("GSA_INDEX_BATCH"); const long long v = e ? atoll(e) : 0; return v > 0 ? v : 0; }
+// the index of `fasta` under `prefix`; on_gpu: the BWT/SA half from gsa_build_index_opts on `device` (GSA_BUILD_AUTO: the wide sorter over 1 073 741 822 bases; a reference
+// over ITS bound: one line, then the host builder).  Returns 0, 1 (the builder's error: printed) or 2 (the GPU's error: printed).
 struct GpuIndexCall { int device, rc; };
 static int gpu_bwt_fn(void *user, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
 {
 	GpuIndexCall *g = (GpuIndexCall *)user;
-	return g->rc = gsa_build_index(g->device, pac, G, primary, L2, bwt, sa);
+	return g->rc = gsa_build_index_opts(g->device, pac, G, env_index_wide() ? GSA_BUILD_WIDE : GSA_BUILD_AUTO, env_index_batch(), 0, primary, L2, bwt, sa);
 }
 static int build_index(const char *fasta, const std::string &prefix, bool on_gpu, int device)
 {
@@ -279,9 +282,12 @@ int main(int argc, char *argv[])
 			// (the first GPU gets the index from the host -- upload + table builds; every further GPU gets a device-to-device copy of the finished tables:
 			//  gsa_clone_to_device, no second pass over PCIe, nothing rebuilt)
 			const uint32_t wide = (fw && *fw && *fw != '0') ? GSA_CREATE_WIDE : 0u;
+			// (-memindex: the wide sorter over the narrow one's bound of 1 073 741 822 bases, or when GSA_INDEX_64BIT asks for it)
+			const uint32_t sort_wide = memindex && (env_index_wide() || idx.G > 1073741822ll) ? GSA_CREATE_SORT_WIDE : 0u;
+			if (sort_wide) (void)gsa_set_index_build_caps(env_index_batch(), 0, 0);
 			const double tc = now_s();
 			const int rc_c = g > 0 ? gsa_clone_to_device(ctxs[0], gpus[g], &owner)
-			               : memindex ? gsa_create_from_pac(gpus[g], idx.pac.data(), idx.G, idx.chr_len.data(), (int32_t)idx.chr_len.size(), &prm, wide, &owner)
+			               : memindex ? gsa_create_from_pac(gpus[g], idx.pac.data(), idx.G, idx.chr_len.data(), (int32_t)idx.chr_len.size(), &prm, wide | sort_wide, &owner)
 			                          : gsa_create_opts(gpus[g], &view, &prm, wide | GSA_CREATE_REF_PAC, &owner);
 			if (g == 0 && memindex) t_from_pac = now_s() - tc;
 			// (a reference over the device builder's bound: the library's message, and no fall-back to a path that writes the files the user asked not to have)

@@ -15,38 +15,7 @@
 // gsa_create_from_pac (build_tables_from_pac, at the end) runs the same sort and the same passes for a context: nothing is copied home, the SA array itself becomes the
 // context's dense SA (k_ix_widen for the 64-bit layout) and the file layout of the BWT words lives only until build_occ (k_tables.hip) has regrouped it.
 #include <chrono>
-#include "gsa_scan.h"
-
-#define IX_H0 29
-#define IX_T 256
-
-static inline unsigned ix_grid(i64 n) { const i64 g = (n + IX_T - 1) / IX_T; return (unsigned)(g < 1 ? 1 : (g > 16384 ? 16384 : g)); }      // (grid-stride kernels: at most 2^22 work-items per launch)
-
-__device__ __forceinline__ u32 ix_pacsym(const uint8_t *__restrict__ pac, i64 q) { return (u32)(pac[q >> 2] >> ((~q & 3) << 1)) & 3u; }
-// the 32 bases from p on, first base in the top bits; the words behind the text are zero
-__device__ __forceinline__ u64 ix_get32(const u64 *__restrict__ tw, i64 p)
-{
-	const i64 wi = p >> 5; const int sh = (int)(p & 31) * 2;
-	const u64 a = tw[wi], b = tw[wi + 1];
-	return sh ? (a << sh) | (b >> (64 - sh)) : a;
-}
-__device__ __forceinline__ u32 ix_sym(const u64 *__restrict__ tw, i64 p) { return (u32)(tw[p >> 5] >> (62 - 2 * (int)(p & 31))) & 3u; }
-
-// T, 2 bits per base, 32 bases per word: the forward strand from .pac, behind it its reverse complement (the text gsah_build_index forms), zeros behind that
-__global__ void __launch_bounds__(IX_T) k_ix_pack(const uint8_t *__restrict__ pac, i64 G, i64 S, u64 *__restrict__ tw, i64 n_tw)
-{
-	for (i64 w = (i64)blockIdx.x * IX_T + threadIdx.x; w < n_tw; w += (i64)gridDim.x * IX_T) {
-		u64 v = 0; const i64 p0 = w * 32;
-#pragma unroll 8
-		for (int k = 0; k < 32; k++) {
-			const i64 p = p0 + k;
-			u32 s = 0;
-			if (p < G) s = ix_pacsym(pac, p); else if (p < S) s = 3u - ix_pacsym(pac, S - 1 - p);
-			v |= (u64)s << (62 - 2 * k);
-		}
-		tw[w] = v;
-	}
-}
+#include "gsa_index.h"
 
 // first-pass keys, two suffixes per thread (S is even): 16-byte key stores, 8-byte value stores
 __global__ void __launch_bounds__(IX_T) k_ix_keys0(const u64 *__restrict__ tw, i64 S, u64 *__restrict__ key, u32 *__restrict__ val)
@@ -179,14 +148,6 @@ __global__ void __launch_bounds__(IX_T) k_ix_widen(i64 n, const u32 *__restrict_
 }
 
 namespace {
-// the builder's device arrays: all freed when the call returns, whichever way (gsa_create_from_pac takes SA out first: release)
-struct IxBufs {
-	hipStream_t st; std::vector<void *> p;
-	~IxBufs() { free_all(); }
-	void free_all() { if (p.empty()) return; (void)hipStreamSynchronize(st); for (void *q : p) (void)hipFree(q); p.clear(); (void)hipGetLastError(); }
-	void release(void *q) { for (size_t k = 0; k < p.size(); k++) if (p[k] == q) { p.erase(p.begin() + (long)k); return; } }
-	template <class T> bool get(T **out, size_t n) { void *q = nullptr; if (hipMalloc(&q, (n ? n : 1) * sizeof(T) + 256) != hipSuccess) { (void)hipGetLastError(); return false; } p.push_back(q); *out = (T *)q; return true; }
-};
 // what the sort leaves on the device: SA (n + 32 entries: the size of the 32-bit dense SA of a context, build_dense_sa), the packed text, the .pac bytes, the status
 // words {-, primary}; d_bwt is zeroed for the BWT / Occ passes (whole 64-byte blocks of the file layout and one more: what build_occ reads), d_sa is there when asked for
 struct IxSort {

@@ -72,9 +72,10 @@ def build_index_with(fasta: str, prefix: str, fn) -> None:
         raise e
 
 
-def build_index_gpu(fasta: str, prefix: str, device: int = 0) -> None:
-    """The index files of `fasta` with the BWT/SA half built on the GPU (capi.build_index_arrays): the same five files as build_index."""
-    build_index_with(fasta, prefix, lambda pac, G: capi.build_index_arrays(pac, G, device))
+def build_index_gpu(fasta: str, prefix: str, device: int = 0, wide: bool = False, batch_cap: int = 0, occ_segment: int = 0) -> None:
+    """The index files of `fasta` with the BWT/SA half built on the GPU (capi.build_index_arrays): the same five files as build_index.  wide: the batched
+    64-bit sorter whatever the length (it runs by itself over 1 073 741 822 bases)."""
+    build_index_with(fasta, prefix, lambda pac, G: capi.build_index_arrays(pac, G, device, wide=wide, batch_cap=batch_cap, occ_segment=occ_segment))
 
 
 def reference_from_fasta(fasta: str):

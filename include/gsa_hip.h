@@ -144,6 +144,10 @@ int  gsa_create(int device, const gsa_index_view *idx, const gsa_params *prm, gs
  * The reference unpacks .pac into 2G ASCII bytes on the host (RestoreReferenceInfo, bwt_index.cpp:229-264) before anything else can start; with this flag the device does
  * that loop itself -- G / 4 bytes cross PCIe instead of 2G, and a host program can unpack its own copy (for its emitters) WHILE gsa_create builds the device tables. */
 #define GSA_CREATE_REF_PAC 4u
+/* GSA_CREATE_SORT_WIDE (gsa_create_from_pac only): the suffixes are sorted by the wide device builder (gsa_build_index_opts, GSA_BUILD_WIDE) whatever the
+ * text length, and its 64-bit suffix array becomes the wide dense SA -- GSA_CREATE_WIDE is implied.  This is how a reference over 1 073 741 822 bases gets a
+ * context from its sequence; under that length it lets the tests drive the wide builder (its batch cap and Occ segment: gsa_set_index_build_caps). */
+#define GSA_CREATE_SORT_WIDE 2u
 int  gsa_create_opts(int device, const gsa_index_view *idx, const gsa_params *prm, uint32_t flags, gsa_ctx **out);
 /* A context from the reference SEQUENCE instead of from its index files: what bwa_idx_build (BWT_Index/bwtindex.c:77-149) followed by bwa_idx_load +
  * RestoreReferenceInfo (bwt_index.cpp:147-264) amount to, with no file and no host array in between.  pac = ceil(G / 4) host bytes as gsa_build_index takes them;
@@ -152,7 +156,7 @@ int  gsa_create_opts(int device, const gsa_index_view *idx, const gsa_params *pr
  * the device.  The context is the one gsa_create_opts makes from the index files of the same sequence -- the same device tables bit for bit -- and is cloned
  * (gsa_clone, gsa_clone_to_device) and destroyed like it.  A reservation of gsa_reserve_index on `device` is released, not adopted.
  * Errors in this order: NULL pointers, G <= 0, n_chr <= 0, sum(chr_len) != G, an unknown flag GSA_ERR_ARG; G > 1 073 741 822 GSA_ERR_LIMIT (before anything is
- * allocated and before pac is read); no device GSA_ERR_HIP; ~52 bytes of device memory per suffix that are not there GSA_ERR_NOMEM.  gsa_last_error(NULL) has the text. */
+ * allocated and before pac is read; with GSA_CREATE_SORT_WIDE the bound is gsa_build_index_opts's, 4 294 967 295); no device GSA_ERR_HIP; ~52 bytes of device memory per suffix that are not there GSA_ERR_NOMEM.  gsa_last_error(NULL) has the text. */
 int  gsa_create_from_pac(int device, const uint8_t *pac, int64_t G, const int32_t *chr_len, int32_t n_chr, const gsa_params *prm, uint32_t flags, gsa_ctx **out);
 /* Test support: device table `which` of a context (its own, or the one it borrows) copied to dst[cap]; *bytes = its size, dst == NULL only reports it; an absent
  * table reports 0.  Only the DEFINED extent of a table is exported: the dense SA seq_len + 1 entries, the Occ blocks the 2 x n_blocks uint4 that were written,
@@ -570,8 +574,36 @@ int gsa_index_sizes(int64_t G, uint64_t *bwt_words, uint64_t *n_sa);
  * they are not there).  Errors in this order: NULL pointers or G <= 0 GSA_ERR_ARG, G over the bound GSA_ERR_LIMIT, no device GSA_ERR_HIP;
  * gsa_last_error(NULL) has the text. */
 int gsa_build_index(int device, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa);
-/* measurement: device ms and doubling rounds of the last gsa_build_index of the calling thread */
+/* measurement: device ms and doubling rounds of the last gsa_build_index / gsa_build_index_opts of the calling thread */
 int gsa_get_index_build_stats(double *ms, int32_t *rounds);
+/* gsa_build_index with a choice of sorter.  flags: GSA_BUILD_AUTO -- the sorter of gsa_build_index up to its bound of 1 073 741 822 bases, the wide one above it;
+ * GSA_BUILD_WIDE -- the wide one at any size.  The wide sorter keeps suffix numbers, ranks and SA slots in 64 bits and works in BATCHES: ranges of classes of
+ * the first 8 bases that hold at most batch_cap suffixes each (0: 2^30; a class larger than the cap is a batch of its own, and a class of more than
+ * 2 147 483 646 suffixes GSA_ERR_LIMIT with the class in the message), sorted one after the other with the 32-bit radix sort.  The running symbol counts of
+ * the .bwt layout are scanned in segments of occ_segment 128-symbol blocks (0, or more than 2^23: 2^23) with a 64-bit carry.  The arrays are the same bytes
+ * whichever sorter made them.  Device memory: 16 bytes per suffix, 52 per suffix of the largest batch, 24 per suffix that still ties with another after 29
+ * bases (GSA_ERR_NOMEM, with the sizes, when that list does not fit).
+ * The bound: G <= 4 294 967 295 -- a sort key holds a rank inside a batch (31 bits) and a rank in the text (33 bits); the file layout and gsa_index_sizes (64-bit
+ * counts and samples) would allow more.  Errors in this order: NULL pointers or G <= 0, an unknown flag, a negative batch_cap or occ_segment GSA_ERR_ARG;
+ * G over the bound GSA_ERR_LIMIT; no device GSA_ERR_HIP. */
+#define GSA_BUILD_AUTO 0u
+#define GSA_BUILD_WIDE 1u
+int gsa_build_index_opts(int device, const uint8_t *pac, int64_t G, uint32_t flags, int64_t batch_cap, int64_t occ_segment,
+                         uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa);
+/* measurement, beside gsa_get_index_build_stats: the batches that held a suffix (0: the narrow sorter ran), the peak of device memory in use during the last
+ * gsa_build_index_opts of the calling thread (the low-water mark of hipMemGetInfo below its value at the start; the list of tied suffixes is given the free
+ * memory up to 24 bytes per suffix, so this says that the build fits, not what it needs) and the suffixes that still tied with another after the first pass (29
+ * bases): the longest that list ever is.  0, 0, 0 for the narrow sorter. */
+int gsa_get_index_build_stats2(int64_t *batches, uint64_t *peak_bytes, int64_t *active_suffixes);
+/* Test support, process-wide: batch_cap / occ_segment of the wide builder inside gsa_create_from_pac (GSA_CREATE_SORT_WIDE), and active_cap -- an upper limit on
+ * the entries of the wide builder's list of tied suffixes, in gsa_create_from_pac and gsa_build_index_opts alike (how a test reaches the GSA_ERR_NOMEM of a list that
+ * does not fit).  0: the defaults; negative: GSA_ERR_ARG */
+int gsa_set_index_build_caps(int64_t batch_cap, int64_t occ_segment, int64_t active_cap);
+/* The wide builder's batch planner, a host function: hist[n_classes] suffix counts -> consecutive class ranges of at most batch_cap suffixes.  first[b] = the
+ * first class of batch b, first[*n_batches] = n_classes; base[b] = 1 + the suffixes in front of batch b (its first SA slot: '$' keeps slot 0), base[*n_batches]
+ * = 1 + all suffixes.  A class over the cap is a batch of its own (empty classes between two such classes form a batch of no suffix, which
+ * the builder skips).  first / base hold max_batches + 1 entries.  A class of more than 2 147 483 646 suffixes: GSA_ERR_LIMIT. */
+int gsa_plan_index_batches(const uint64_t *hist, int64_t n_classes, int64_t batch_cap, int64_t max_batches, int64_t *first, uint64_t *base, int64_t *n_batches);
 
 /* ---- one long contig on several GPUs ---------------------------------------
  * IdentifyLocalMEM hands 10 000-bp chunks of the contig to whichever thread is free (GSAlign.cpp:61-94) and seeds never
