@@ -248,7 +248,7 @@ int gsa_create_from_pac(int device, const uint8_t *pac, int64_t G, const int32_t
 	c->d_ref.cap = (size_t)2 * G + 64;
 	if (int rc = ctx_chr_tables(c, chr_len, n_chr, G, "gsa_create_from_pac")) return ctx_abandon(c, rc);
 	c->di.ref = c->d_ref.as<uint8_t>(); c->di.G = G;      // (the other tables: the builders below)
-	if (int rc = sort_wide ? build_tables_from_pac_wide(c, pac, G, g_ix_batch_cap.load(), g_ix_occ_segment.load(), g_ix_active_cap.load()) : build_tables_from_pac(c, pac, G)) return ctx_abandon(c, rc);
+	if (int rc = build_tables_from_pac(c, pac, G, IxOpts{ sort_wide, g_ix_batch_cap.load(), g_ix_occ_segment.load(), g_ix_active_cap.load() })) return ctx_abandon(c, rc);
 	if (int rc = build_ref2(c)) return ctx_abandon(c, rc);
 	if (int rc = build_kmer_table(c)) return ctx_abandon(c, rc);
 	gsa_params dp; gsa_default_params(&dp);
@@ -553,7 +553,7 @@ int gsa_index_sizes(int64_t G, uint64_t *bwt_words, uint64_t *n_sa)
 	*n_sa = (S + 32) / 32;
 	return GSA_OK;
 }
-static thread_local double g_ix_ms = 0; static thread_local int32_t g_ix_rounds = 0; static thread_local int64_t g_ix_batches = 0, g_ix_active = 0; static thread_local uint64_t g_ix_peak = 0;
+static thread_local IxStats g_ix;      // the calling thread's last build
 // A context with no index: the device, one stream, the mailbox the fused passes draw their tickets from; the sort's scratch (tmp) and the look-back status words
 // grow on first use.  No uploader thread, no events, no auxiliary streams.  gsa_destroy frees it like any other context.
 static int ix_bare_ctx(const char *who, int device, gsa_ctx **out)
@@ -568,19 +568,24 @@ static int ix_bare_ctx(const char *who, int device, gsa_ctx **out)
 	*out = c;
 	return GSA_OK;
 }
+// both entry points behind their argument checks: a bare context, the build, its figures, the context gone
+static int ix_build(const char *who, int device, const uint8_t *pac, int64_t G, const IxOpts &o, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
+{
+	if (int rc = create_device_ok(who, device)) return rc;
+	gsa_ctx *c = nullptr;
+	if (int rc = ix_bare_ctx(who, device, &c)) return rc;
+	IxStats s;
+	if (int rc = build_index_device(c, pac, G, o, who, primary, L2, bwt, sa, &s)) { g_create_error = c->err; return ctx_abandon(c, rc); }
+	g_ix = s;
+	gsa_destroy(c);
+	return GSA_OK;
+}
 int gsa_build_index(int device, const uint8_t *pac, int64_t G, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
 {
 	if (!pac || !primary || !L2 || !bwt || !sa || G <= 0) return gsa_fail(nullptr, GSA_ERR_ARG, "gsa_build_index: bad argument");
 	// 32-bit suffix indices, ranks and scatter positions: the text with its '$' has at most 2^31 - 2 suffixes (the bound of the host builder's 32-bit instance)
 	if (2 * G + 1 > (1ll << 31) - 2) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_build_index: the reference is longer than 1 073 741 822 bases (the device builder sorts 32-bit suffix indices)");
-	if (int rc = create_device_ok("gsa_build_index", device)) return rc;
-	gsa_ctx *c = nullptr;
-	if (int rc = ix_bare_ctx("gsa_build_index", device, &c)) return rc;
-	double ms = 0; int32_t rounds = 0;
-	if (int rc = build_index_device(c, pac, G, primary, L2, bwt, sa, &ms, &rounds)) { g_create_error = c->err; return ctx_abandon(c, rc); }
-	g_ix_ms = ms; g_ix_rounds = rounds; g_ix_batches = 0; g_ix_peak = 0; g_ix_active = 0;
-	gsa_destroy(c);
-	return GSA_OK;
+	return ix_build("gsa_build_index", device, pac, G, IxOpts{ false, 0, 0, 0 }, primary, L2, bwt, sa);
 }
 int gsa_build_index_opts(int device, const uint8_t *pac, int64_t G, uint32_t flags, int64_t batch_cap, int64_t occ_segment, uint64_t *primary, uint64_t L2[5], uint32_t *bwt, uint64_t *sa)
 {
@@ -590,19 +595,12 @@ int gsa_build_index_opts(int device, const uint8_t *pac, int64_t G, uint32_t fla
 	if (G > IX_WIDE_MAX_G) return gsa_fail(nullptr, GSA_ERR_LIMIT, "gsa_build_index_opts: the reference is longer than 4 294 967 295 bases (the wide device builder's sort key holds a 33-bit rank)");
 	const bool wide = (flags & GSA_BUILD_WIDE) != 0 || 2 * G + 1 > (1ll << 31) - 2;
 	if (!wide) return gsa_build_index(device, pac, G, primary, L2, bwt, sa);
-	if (int rc = create_device_ok("gsa_build_index_opts", device)) return rc;
-	gsa_ctx *c = nullptr;
-	if (int rc = ix_bare_ctx("gsa_build_index_opts", device, &c)) return rc;
-	double ms = 0; int32_t rounds = 0; i64 batches = 0, active = 0; u64 peak = 0;
-	if (int rc = build_index_device_wide(c, pac, G, batch_cap, occ_segment, g_ix_active_cap.load(), primary, L2, bwt, sa, &ms, &rounds, &batches, &peak, &active)) { g_create_error = c->err; return ctx_abandon(c, rc); }
-	g_ix_ms = ms; g_ix_rounds = rounds; g_ix_batches = batches; g_ix_peak = peak; g_ix_active = active;
-	gsa_destroy(c);
-	return GSA_OK;
+	return ix_build("gsa_build_index_opts", device, pac, G, IxOpts{ true, batch_cap, occ_segment, g_ix_active_cap.load() }, primary, L2, bwt, sa);
 }
 int gsa_get_index_build_stats2(int64_t *batches, uint64_t *peak_bytes, int64_t *active_suffixes)
 {
 	if (!batches || !peak_bytes || !active_suffixes) return GSA_ERR_ARG;
-	*batches = g_ix_batches; *peak_bytes = g_ix_peak; *active_suffixes = g_ix_active;
+	*batches = g_ix.batches; *peak_bytes = g_ix.peak; *active_suffixes = g_ix.active;
 	return GSA_OK;
 }
 int gsa_set_index_build_caps(int64_t batch_cap, int64_t occ_segment, int64_t active_cap)
@@ -614,7 +612,7 @@ int gsa_set_index_build_caps(int64_t batch_cap, int64_t occ_segment, int64_t act
 int gsa_get_index_build_stats(double *ms, int32_t *rounds)
 {
 	if (!ms || !rounds) return GSA_ERR_ARG;
-	*ms = g_ix_ms; *rounds = g_ix_rounds;
+	*ms = g_ix.ms; *rounds = g_ix.rounds;
 	return GSA_OK;
 }
 } // extern "C"

@@ -346,8 +346,9 @@ int build_kmer_table(gsa_ctx *c);           // k_tables.hip  (needs the Occ bloc
 int unpack_pac(gsa_ctx *c, const uint8_t *d_pac, i64 G, uint8_t *d_ref);   // k_tables.hip  (GSA_CREATE_REF_PAC: RefSequence from the .pac bytes, on the device)
 int build_occ(gsa_ctx *c, const void *ref_layout, u64 n_blocks128);   // k_tables.hip: the device's Occ blocks from the reference's layout
 int build_presence(gsa_ctx *c);             // k_tables.hip  (after MinSeedLength changed)
-int build_tables_from_pac(gsa_ctx *c, const uint8_t *pac, i64 G);   // k_index.hip  (gsa_create_from_pac: Occ blocks, both SAs and RefSequence from the suffix sort, nothing copied home)
-int build_tables_from_pac_wide(gsa_ctx *c, const uint8_t *pac, i64 G, i64 batch_cap, i64 occ_segment, i64 active_cap);   // k_index_wide.hip  (the same from the batched 64-bit sort: GSA_CREATE_SORT_WIDE)
+struct IxOpts { bool wide; i64 batch_cap, occ_segment, active_cap; };      // which sorter of the device index builder; the wide one's caps (0: the default)
+struct IxStats { double ms = 0; i32 rounds = 0; i64 batches = 0, active = 0; u64 peak = 0; };
+int build_tables_from_pac(gsa_ctx *c, const uint8_t *pac, i64 G, const IxOpts &o);   // k_index.hip  (gsa_create_from_pac: Occ blocks, both SAs and RefSequence from the suffix sort -- narrow, or the batched 64-bit one: GSA_CREATE_SORT_WIDE -- nothing copied home)
 int stage1_seed(gsa_ctx *c);          // k_seed.hip
 int stage1_dense(gsa_ctx *c, hipStream_t st, const uint8_t *d_q, i32 qlen, i64 n_chunks, u64 n_heavy, bool dense_all, bool sweep_all, size_t ccap, u64 &hits, u64 &maxcand, u64 &occ_all);   // k_seed_dense.hip  (stage1_seed's dense kernels: launch, wait, counters)
 int prepare_pd_bitmap(gsa_ctx *c, i64 n_hits, i64 n_chunks = 0);   // k_seed_select.hip  (whether this contig keeps the bitmap of occupied PosDiff values, cleared)
@@ -379,8 +380,7 @@ int proj_release(gsa_ctx *c);                               // k_proj.hip  (gsa_
 int proj_clear(gsa_ctx *c);
 int proj_fetch(gsa_ctx *c, i64 p0, i64 n, char *text, u32 *words);
 int proj_merge(gsa_ctx *c, i64 p0, i64 n, const u32 *words);
-int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds);   // k_index.hip  (suffix sort + BWT / Occ / SA samples of forward + reverse complement)
-int build_index_device_wide(gsa_ctx *c, const uint8_t *pac, i64 G, i64 batch_cap, i64 occ_segment, i64 active_cap, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds, i64 *batches, u64 *peak, i64 *active);   // k_index_wide.hip  (the same above 2^31 - 2 suffixes: batches, 64-bit suffix numbers)
+int build_index_device(gsa_ctx *c, const uint8_t *pac, i64 G, const IxOpts &o, const char *who, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, IxStats *out);   // k_index.hip  (suffix sort -- narrow, or k_index_wide.hip's above 2^31 - 2 suffixes -- + BWT / Occ / SA samples of forward + reverse complement)
 int host_stage4_5_6(gsa_ctx *c, int stage);    // gsa_blocks.cpp
 int host_stage8_finish(gsa_ctx *c);            // gsa_blocks.cpp
 int build_block_view(gsa_ctx *c);              // gsa_blocks.cpp

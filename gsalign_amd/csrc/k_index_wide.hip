@@ -10,8 +10,8 @@
 //                {rank[i] - base_b, rank[i + h]} (31 + 33 bits at most), gathered, split (OpIxwRound) and applied (k_ixw_apply).  A later batch of the round may read
 //                rank[i + h] of a suffix an earlier batch has refined in this very round: that rank is finer and order-consistent, which is all the key needs
 //                (the argument is in DESIGN.md section 8d.1).  Slots travel relative to the batch base, in 32 bits.
-//   derivation   k_index.hip's passes on the 64-bit SA; the Occ running counts are scanned in segments of occ_segment blocks whose totals fit the scan's i32, with a
-//                64-bit carry from segment to segment.
+// This file is the sorter only (ix_sort_wide, between ix_begin and the derivation half: both in k_index.hip, the latter instantiated for the 64-bit SA, its Occ running
+// counts scanned in segments of occ_segment blocks whose totals fit the scan's i32) and the batch planner.
 #include <chrono>
 #include "gsa_index.h"
 
@@ -59,12 +59,6 @@ __global__ void __launch_bounds__(IX_T) k_ixw_keys0(i64 m, const u64 *__restrict
 __global__ void __launch_bounds__(IX_T) k_ixw_gather(i64 m, const u64 *__restrict__ src, const u32 *__restrict__ idx, u64 *__restrict__ dst)
 {
 	for (i64 t = (i64)blockIdx.x * IX_T + threadIdx.x; t < m; t += (i64)gridDim.x * IX_T) dst[t] = src[idx[t]];
-}
-
-// st: [0] unused, [1] primary
-__global__ void k_ixw_init(u64 *rank, u64 *SA, u64 *st, i64 S)
-{
-	if (threadIdx.x == 0 && blockIdx.x == 0) { rank[S] = 0; SA[0] = (u64)S; st[0] = 0; st[1] = 0; }
 }
 
 // OpIxRound (k_index.hip) for one batch: slots are relative to the batch base (slot = nullptr: entry t sits in slot t, the first pass), suffixes 64-bit.  The next
@@ -115,68 +109,6 @@ __global__ void __launch_bounds__(IX_T) k_ixw_keys(i64 m, const u64 *__restrict_
 	}
 }
 
-// k_ix_bwt on the 64-bit SA
-__global__ void __launch_bounds__(IX_T) k_ixw_bwt(i64 S, const u64 *__restrict__ SA, const u64 *__restrict__ tw, const u64 *__restrict__ st, u32 *__restrict__ out)
-{
-	const i64 primary = (i64)st[1];
-	for (i64 base = (i64)blockIdx.x * IX_T; base < S; base += (i64)gridDim.x * IX_T) {      // (base is the same in all lanes of a wave: the shuffles below see full waves)
-		const i64 k = base + threadIdx.x;
-		u32 v = 0;
-		if (k < S) {
-			const i64 i = k + (k >= primary ? 1 : 0);
-			const i64 p = (i64)SA[i] - 1;
-			v = ix_sym(tw, p < 0 ? 0 : p) << ((~(u32)k & 15u) << 1);
-		}
-		v |= __shfl_xor(v, 1); v |= __shfl_xor(v, 2); v |= __shfl_xor(v, 4); v |= __shfl_xor(v, 8);
-		if (k < S && (k & 15) == 0) out[(k >> 7) * 16 + 8 + ((k >> 4) & 7)] = v;
-	}
-}
-
-// OpIxOcc (k_index.hip) over the blocks g0 .. g0 + n - 1 of one segment: the scan's i32 sums count the segment's symbols only, the counts in front of the segment
-// come in as 64-bit words (carry_in[sym]) and the segment's closing counts go out the same way (carry_out: another array, other tiles still read carry_in)
-struct OpIxwOcc {
-	u32 *out; i64 S, n_words, g0; int sym0; const u64 *carry_in; u64 *carry_out;
-	struct Item { i32 c0, c1; };
-	__device__ Item load(i64 gl) const
-	{
-		const i64 g = g0 + gl;
-		const uint4 *w4 = (const uint4 *)(out + g * 16 + 8);
-		const uint4 a = w4[0], b = w4[1];
-		const u32 w[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
-		const i64 nw = n_words - g * 8, left = S - g * 128;
-		i32 cC = 0, cG = 0, cT = 0;
-#pragma unroll
-		for (int k = 0; k < 8; k++) {
-			const u32 x = k < nw ? w[k] : 0u;      // (behind the last word of the last block lie the closing counts)
-			const u32 lo = x & 0x55555555u, hi = (x >> 1) & 0x55555555u;
-			cT += __popc(lo & hi); cG += __popc(hi & ~lo); cC += __popc(lo & ~hi);
-		}
-		const i32 cA = (i32)(left < 128 ? left : 128) - cC - cG - cT;      // (the padding of the last word is zeros, not A's)
-		Item it;
-		if (sym0 == 0) { it.c0 = cA; it.c1 = cC; } else { it.c0 = cG; it.c1 = cT; }
-		return it;
-	}
-	__device__ i32 value(const Item &it, i64, int c) const { return c ? it.c1 : it.c0; }
-	__device__ void emit(const Item &, i64 gl, const i32 *, const i32 *ex) const
-	{
-		const u64 x0 = carry_in[sym0] + (u64)(u32)ex[0], x1 = carry_in[sym0 + 1] + (u64)(u32)ex[1];
-		uint4 o; o.x = (u32)x0; o.y = (u32)(x0 >> 32); o.z = (u32)x1; o.w = (u32)(x1 >> 32);
-		*(uint4 *)(out + (g0 + gl) * 16 + 2 * sym0) = o;
-	}
-	__device__ void done(const i32 *tt) const { carry_out[sym0] = carry_in[sym0] + (u64)(u32)tt[0]; carry_out[sym0 + 1] = carry_in[sym0 + 1] + (u64)(u32)tt[1]; }
-};
-// the closing counts behind the last block
-__global__ void k_ixw_close(const u64 *carry, u32 *out, i64 k_end)
-{
-	const int k = threadIdx.x;
-	if (blockIdx.x == 0 && k < 4) { out[k_end + 2 * k] = (u32)carry[k]; out[k_end + 2 * k + 1] = (u32)(carry[k] >> 32); }
-}
-
-__global__ void __launch_bounds__(IX_T) k_ixw_samples(i64 n_sa, const u64 *__restrict__ SA, u64 *__restrict__ sa)
-{
-	for (i64 j = (i64)blockIdx.x * IX_T + threadIdx.x; j < n_sa; j += (i64)gridDim.x * IX_T) sa[j] = j ? SA[32 * j] : ~0ull;
-}
-
 // ---- the batch planner (host) --------------------------------------------------------------------------------------------------------------------------------
 // hist[n_classes] -> consecutive class ranges of at most batch_cap suffixes each.  first[b] = the first class of batch b, first[*n_batches] = n_classes;
 // base[b] = 1 + the suffixes in front of batch b ('$' keeps slot 0), base[*n_batches] = 1 + all of them.  A class larger than the cap is a batch of its own: empty
@@ -207,47 +139,26 @@ extern "C" int gsa_plan_index_batches(const uint64_t *hist, int64_t n_classes, i
 	return GSA_OK;
 }
 
-namespace {
-struct IxWide {
-	IxBufs B;
-	i64 G = 0, S = 0, n = 0, n_tw = 0, n_words = 0, n_blk = 0, n_bwt = 0, n_sa = 0, k_end = 0; i32 rounds = 0; i64 batches = 0, active = 0;      // active: the suffixes that still tie after the first pass (the longest list)
-	uint8_t *d_pac = nullptr; u64 *tw = nullptr, *d_sa = nullptr, *SA = nullptr, *d_st = nullptr, *carry = nullptr; u32 *d_bwt = nullptr;
-	size_t free0 = 0, free_min = 0;      // hipMemGetInfo when the builder started / its low-water mark
-	std::vector<void *> dead;            // what only the sort needed (ixw_release_sort)
-	void mark() { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) { if (fr < free_min) free_min = fr; } else (void)hipGetLastError(); }
-};
-}
+static i64 ixw_cap(i64 batch_cap) { return batch_cap <= 0 ? (i64)1 << 30 : (batch_cap > IXW_LIMIT ? IXW_LIMIT : batch_cap); }
 
+// From ix_begin's state (k_index.hip) to the finished 64-bit SA; X.batches: those that hold a suffix, X.dead: everything only the rounds needed.
 // Device bytes: 16 per suffix (rank, SA), 52 per entry of the largest batch (unsorted positions 8, keys 2 x 8, values 2 x 4, sorted positions 8, the sort's scratch 12 and
 // its histograms; the group numbers and head slots of a round live where the sort's input keys were), 24 per entry of the active list (relative slot 4, suffix 8, twice), under
 // 1 per suffix for the packed text, the BWT words and the samples.
-static int ixw_sort(gsa_ctx *c, IxWide &X, const uint8_t *pac, i64 G, i64 batch_cap, i64 active_cap, bool samples, hipEvent_t ev0, const char *who)
+int ix_sort_wide(gsa_ctx *c, IxBuilt &X, i64 batch_cap, i64 active_cap, const char *who)
 {
-	const i64 S = 2 * G, n = S + 1;
-	X.G = G; X.S = S; X.n = n;
-	X.n_tw = S / 32 + 3; X.n_words = (S + 15) / 16; X.n_blk = (S + 127) / 128; X.n_bwt = X.n_words + (X.n_blk + 1) * 8; X.n_sa = (S + 32) / 32; X.k_end = X.n_blk * 8 + X.n_words;
-	const i64 n_tw = X.n_tw;
-	const size_t pac_bytes = (size_t)((G + 3) / 4), bwt_alloc = (size_t)((X.n_bwt + 15) / 16) * 16 + 16;
+	const i64 S = X.S;
 	const int b = ceil_log2_u64((u64)S + 1);      // bits of a rank (0 .. S)
+	batch_cap = ixw_cap(batch_cap);
 	hipStream_t st = c->stream;
-	IxBufs &B = X.B; B.st = st;
-	{ size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = 0; } X.free0 = X.free_min = fr; }
-	const std::string nomem = std::string(who) + ": hipMalloc (wide builder: 16 bytes per suffix, " + std::to_string((long long)S) + " suffixes";
-	uint8_t *d_pac; u64 *tw, *rank, *SA, *d_st; unsigned long long *d_hist;
-	if (!B.get(&d_pac, pac_bytes) || !B.get(&tw, (size_t)n_tw) || !B.get(&rank, (size_t)n + 1) || !B.get(&SA, (size_t)n + 32) || !B.get(&d_st, (size_t)4) || !B.get(&X.carry, (size_t)8) ||
-	    !B.get(&d_hist, (size_t)IXW_NCLS) || !B.get(&X.d_bwt, bwt_alloc) || (samples && !B.get(&X.d_sa, (size_t)X.n_sa)))
-		return gsa_fail(c, GSA_ERR_NOMEM, nomem + ")");
-	X.d_pac = d_pac; X.tw = tw; X.SA = SA; X.d_st = d_st;
-	GSA_CHECK(c, hipMemcpyAsync(d_pac, pac, pac_bytes, hipMemcpyHostToDevice, st));
-	if (ev0) GSA_CHECK(c, hipEventRecord(ev0, st));
-	GSA_CHECK(c, hipMemsetAsync(X.d_bwt, 0, bwt_alloc * 4, st));
+	IxBufs &B = X.B;
+	const std::string nomem = X.nomem(who);
+	const u64 *tw = X.tw; u64 *rank, *SA = (u64 *)X.SA, *d_st = X.d_st; unsigned long long *d_hist;
+	if (!B.get(&rank, (size_t)X.n + 1) || !B.get(&d_hist, (size_t)IXW_NCLS)) return gsa_fail(c, GSA_ERR_NOMEM, nomem + ")");
 	GSA_CHECK(c, hipMemsetAsync(d_hist, 0, (size_t)IXW_NCLS * 8, st));
-	GSA_CHECK(c, hipMemsetAsync(X.carry, 0, 64, st));
-	hipLaunchKernelGGL(k_ixw_init, dim3(1), dim3(64), 0, st, rank, SA, d_st, S);
+	hipLaunchKernelGGL(k_ix_init<u64>, dim3(1), dim3(64), 0, st, rank, SA, d_st, S);
 	GSA_CHECK(c, hipGetLastError());
-	hipLaunchKernelGGL(k_ix_pack, dim3(ix_grid(n_tw)), dim3(IX_T), 0, st, (const uint8_t *)d_pac, G, S, tw, n_tw);
-	GSA_CHECK(c, hipGetLastError());
-	hipLaunchKernelGGL(k_ixw_hist, dim3(ix_grid((S + 31) / 32)), dim3(IX_T), 0, st, (const u64 *)tw, S, d_hist);
+	hipLaunchKernelGGL(k_ixw_hist, dim3(ix_grid((S + 31) / 32)), dim3(IX_T), 0, st, tw, S, d_hist);
 	GSA_CHECK(c, hipGetLastError());
 	std::vector<uint64_t> hist((size_t)IXW_NCLS), base((size_t)IXW_NCLS + 1); std::vector<int64_t> first((size_t)IXW_NCLS + 1);
 	GSA_CHECK(c, hipMemcpyAsync(hist.data(), d_hist, (size_t)IXW_NCLS * 8, hipMemcpyDeviceToHost, st));
@@ -339,106 +250,5 @@ static int ixw_sort(gsa_ctx *c, IxWide &X, const uint8_t *pac, i64 G, i64 batch_
 	X.mark();
 	X.rounds = nr;
 	X.dead = { (void *)rank, (void *)d_hist, (void *)pos, (void *)keyA, (void *)keyB, (void *)sufS, (void *)valA, (void *)valB, (void *)slotL[0], (void *)slotL[1], (void *)sufL[0], (void *)sufL[1], (void *)d_off };
-	return GSA_OK;
-}
-
-// Everything the rounds used is dead once ixw_sort returns -- ranks, batch arrays, active lists, the sort scratch that grew inside the context: the derivation reads SA,
-// the packed text and the .pac bytes only.  gsa_create_from_pac frees them here, BEFORE the context's Occ blocks and samples are allocated (a list that was cut to the
-// free memory leaves no room for them otherwise); gsa_build_index_opts lets them go with the rest when it returns, outside its timed region.
-static int ixw_release_sort(gsa_ctx *c, IxWide &X)
-{
-	GSA_CHECK(c, hipStreamSynchronize(c->stream));
-	for (void *q : X.dead) { X.B.release(q); (void)hipFree(q); }
-	(void)hipGetLastError();
-	X.dead.clear();
-	if (c->tmp.p) { ctx_quiesce(c); (void)hipFree(c->tmp.p); c->tmp.p = nullptr; c->tmp.cap = 0; c->tmp.len = 0; }
-	return GSA_OK;
-}
-
-// the file layout of the .bwt words into X.d_bwt: the symbols, then the running counts in front of every block, segment by segment, and the closing counts
-static int ixw_bwt_occ(gsa_ctx *c, IxWide &X, i64 occ_segment)
-{
-	hipStream_t st = c->stream;
-	hipLaunchKernelGGL(k_ixw_bwt, dim3(ix_grid(X.S)), dim3(IX_T), 0, st, X.S, (const u64 *)X.SA, (const u64 *)X.tw, (const u64 *)X.d_st, X.d_bwt);
-	GSA_CHECK(c, hipGetLastError());
-	int par = 0;
-	for (i64 g0 = 0; g0 < X.n_blk; g0 += occ_segment, par ^= 1) {
-		const i64 ng = X.n_blk - g0 < occ_segment ? X.n_blk - g0 : occ_segment;
-		for (int sym0 = 0; sym0 < 4; sym0 += 2) { OpIxwOcc op = { X.d_bwt, X.S, X.n_words, g0, sym0, X.carry + 4 * par, X.carry + 4 * (par ^ 1) }; if (int rc = lb_launch<2>(c, ng, op, st)) return rc; }
-	}
-	hipLaunchKernelGGL(k_ixw_close, dim3(1), dim3(64), 0, st, (const u64 *)(X.carry + 4 * par), X.d_bwt, X.k_end);
-	GSA_CHECK(c, hipGetLastError());
-	return GSA_OK;
-}
-
-static i64 ixw_cap(i64 batch_cap) { return batch_cap <= 0 ? (i64)1 << 30 : (batch_cap > IXW_LIMIT ? IXW_LIMIT : batch_cap); }
-static i64 ixw_seg(i64 occ_segment) { return occ_segment <= 0 || occ_segment > ((i64)1 << 23) ? (i64)1 << 23 : occ_segment; }      // (2^23 blocks of 128 symbols: totals of 2^30)
-
-// build_index_device (k_index.hip) with the wide sorter; batches: those that hold a suffix; peak: device bytes in use at the low-water mark of hipMemGetInfo, less what was in use at the start
-int build_index_device_wide(gsa_ctx *c, const uint8_t *pac, i64 G, i64 batch_cap, i64 occ_segment, i64 active_cap, u64 *primary, u64 L2[5], u32 *bwt, u64 *sa, double *ms, i32 *rounds, i64 *batches, u64 *peak, i64 *active)
-{
-	hipStream_t st = c->stream;
-	hipEvent_t ev[2] = { nullptr, nullptr };
-	struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int k = 0; k < 2; k++) if (e[k]) (void)hipEventDestroy(e[k]); } } evg{ ev };
-	IxWide X;      // (behind the events: its arrays are freed, after a wait for the stream, before they are destroyed)
-	GSA_CHECK(c, hipEventCreate(&ev[0])); GSA_CHECK(c, hipEventCreate(&ev[1]));
-	if (int rc = ixw_sort(c, X, pac, G, ixw_cap(batch_cap), active_cap, true, ev[0], "gsa_build_index_opts")) return rc;
-	if (int rc = ixw_bwt_occ(c, X, ixw_seg(occ_segment))) return rc;
-	const i64 S = X.S, n_bwt = X.n_bwt, n_sa = X.n_sa, k_end = X.k_end;
-	hipLaunchKernelGGL(k_ixw_samples, dim3(ix_grid(n_sa)), dim3(IX_T), 0, st, n_sa, (const u64 *)X.SA, X.d_sa);
-	GSA_CHECK(c, hipGetLastError());
-	GSA_CHECK(c, hipEventRecord(ev[1], st));
-	u64 h_st[2] = { 0, 0 }; i32 lberr = 0;
-	GSA_CHECK(c, hipMemcpyAsync(h_st, X.d_st, 16, hipMemcpyDeviceToHost, st));
-	GSA_CHECK(c, hipMemcpyAsync(&lberr, c->d_mail.as<i32>() + M_LBERR, 4, hipMemcpyDeviceToHost, st));
-	GSA_CHECK(c, hipMemcpyAsync(bwt, X.d_bwt, (size_t)n_bwt * 4, hipMemcpyDeviceToHost, st));
-	GSA_CHECK(c, hipMemcpyAsync(sa, X.d_sa, (size_t)n_sa * 8, hipMemcpyDeviceToHost, st));
-	GSA_CHECK(c, hipStreamSynchronize(st));
-	if (lberr) return gsa_fail(c, GSA_ERR_STATE, "internal: look-back scan timed out");
-	X.mark();
-	float fms = 0; if (hipEventElapsedTime(&fms, ev[0], ev[1]) != hipSuccess) { fms = 0; (void)hipGetLastError(); }
-	*primary = h_st[1];
-	L2[0] = 0;
-	for (int k = 0; k < 4; k++) L2[k + 1] = L2[k] + ((u64)bwt[k_end + 2 * k] | ((u64)bwt[k_end + 2 * k + 1] << 32));
-	if (L2[4] != (u64)S) return gsa_fail(c, GSA_ERR_STATE, "internal: gsa_build_index_opts: the symbol counts do not add up");
-	*ms = (double)fms; *rounds = X.rounds; *batches = X.batches; *peak = (u64)(X.free0 - X.free_min); *active = X.active;
-	return GSA_OK;
-}
-
-// build_tables_from_pac (k_index.hip) with the wide sorter: the 64-bit SA array itself becomes the wide dense SA (GSA_CREATE_WIDE is implied: the caller has set force_wide)
-int build_tables_from_pac_wide(gsa_ctx *c, const uint8_t *pac, i64 G, i64 batch_cap, i64 occ_segment, i64 active_cap)
-{
-	hipStream_t st = c->stream;
-	IxWide X;
-	auto drop_scratch = [&]() { if (c->tmp.p) { ctx_quiesce(c); (void)hipFree(c->tmp.p); c->tmp.p = nullptr; c->tmp.cap = 0; c->tmp.len = 0; } };
-	struct ScratchGuard { decltype(drop_scratch) &f; ~ScratchGuard() { f(); } } sg{ drop_scratch };
-	if (int rc = ixw_sort(c, X, pac, G, ixw_cap(batch_cap), active_cap, false, nullptr, "gsa_create_from_pac")) return rc;
-	if (int rc = ixw_release_sort(c, X)) return rc;
-	if (int rc = ixw_bwt_occ(c, X, ixw_seg(occ_segment))) return rc;
-	const i64 S = X.S, n = X.n, n_sa = X.n_sa;
-	u64 h_st[2] = { 0, 0 }; u32 h_end[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; i32 lberr = 0;
-	GSA_CHECK(c, hipMemcpyAsync(h_st, X.d_st, 16, hipMemcpyDeviceToHost, st));
-	GSA_CHECK(c, hipMemcpyAsync(h_end, X.d_bwt + X.k_end, 32, hipMemcpyDeviceToHost, st));
-	GSA_CHECK(c, hipMemcpyAsync(&lberr, c->d_mail.as<i32>() + M_LBERR, 4, hipMemcpyDeviceToHost, st));      // (no fused pass runs below this point)
-	GSA_CHECK(c, hipStreamSynchronize(st));
-	if (lberr) return gsa_fail(c, GSA_ERR_STATE, "internal: look-back scan timed out");
-	c->di.primary = h_st[1]; c->di.L2[0] = 0;
-	for (int k = 0; k < 4; k++) c->di.L2[k + 1] = c->di.L2[k] + ((u64)h_end[2 * k] | ((u64)h_end[2 * k + 1] << 32));
-	if (c->di.L2[4] != (u64)S) return gsa_fail(c, GSA_ERR_STATE, "internal: gsa_create_from_pac: the symbol counts do not add up");
-	c->di.seq_len = (u64)S;
-	if (int rc = build_occ(c, X.d_bwt, (u64)((X.n_bwt + 15) / 16))) return rc;
-	if (hipMalloc(&c->d_sa.p, (size_t)n_sa * 8) != hipSuccess) { (void)hipGetLastError(); return gsa_fail(c, GSA_ERR_NOMEM, "hipMalloc (sampled SA)"); }
-	c->d_sa.cap = (size_t)n_sa * 8;
-	hipLaunchKernelGGL(k_ixw_samples, dim3(ix_grid(n_sa)), dim3(IX_T), 0, st, n_sa, (const u64 *)X.SA, c->d_sa.as<u64>());
-	GSA_CHECK(c, hipGetLastError());
-	c->di.sa = c->d_sa.as<u64>();
-	if (int rc = unpack_pac(c, X.d_pac, G, c->d_ref.as<uint8_t>())) return rc;
-	GSA_CHECK(c, hipMemsetAsync(X.SA, 0xFF, 8, st));      // row 0: SA[0] = S here, the sa[0] = -1 sentinel there
-	GSA_CHECK(c, hipStreamSynchronize(st));
-	X.B.release(X.SA);
-	c->d_sa_dense.p = X.SA; c->d_sa_dense.len = ((size_t)n + 32) * 8; c->d_sa_dense.cap = c->d_sa_dense.len + 256;      // (IxBufs::get's size is dev_ensure's exact size)
-	c->di.sa64 = c->d_sa_dense.as<u64>(); c->di.sa32 = nullptr;
-	X.B.free_all();
-	drop_scratch();
 	return GSA_OK;
 }

@@ -1,6 +1,6 @@
 """The wide device index builder (gsa_build_index_opts with GSA_BUILD_WIDE, GSA_CREATE_SORT_WIDE; k_index_wide.hip): the batched 64-bit suffix sorter and its
 derivation passes, forced onto small inputs, against the index files the reference wrote (tests/golden) and against the host builder run serially (SA-IS) on the
-shapes of test_gpu_index_build.py (restated here) and on shapes aimed at the batch seams.  Every comparison is exact equality."""
+shapes of test_gpu_index_build.py (tests/index_shapes.py) and on shapes aimed at the batch seams.  Every comparison is exact equality."""
 import ctypes as C
 import os
 import shutil
@@ -10,19 +10,13 @@ import numpy as np
 import pytest
 
 from gsalign_amd import capi, hostlib, indexio, synth
+from index_shapes import SHAPES, _ascii, _load
 
 pytestmark = pytest.mark.gpu
 EXTS = ("bwt", "sa", "pac", "ann", "amb")
 TABLES = list(capi.Aligner.TABLES)
 GSA_ERR_NOMEM = -3
 P = 8                                                             # bases of a prefix class (k_index_wide.hip)
-
-
-def _load(prefix):
-    """(pac bytes, G, hdr, bwt, sa) of index files"""
-    G = int(open(prefix + ".ann").readline().split()[0])
-    idx = indexio.load_index(prefix)
-    return np.fromfile(prefix + ".pac", dtype=np.uint8)[:(G + 3) // 4], G, idx.hdr, idx.bwt, idx.sa
 
 
 def _check(prefix, **kw):
@@ -82,31 +76,6 @@ def test_golden_index_files_in_many_batches_and_segments(golden_dir, name):
 
 
 # ---- the shapes of test_gpu_index_build.py, forced wide, batch_cap = 1024 ---------------------------------------------------------------------------------------
-def _ascii(codes):
-    return np.frombuffer(b"ACGT", dtype=np.uint8)[np.asarray(codes, dtype=np.int64)]
-
-
-def _shapes():
-    rng = np.random.default_rng(20261018)
-    R = lambda n: synth.random_genome(n, rng)
-    out = {}
-    for G in (1, 2, 3, 5, 31, 32, 33):                      # shorter than one key, on the key's edge, every G % 4
-        out[f"G{G}"] = [R(G)]
-    out["G2049"] = [R(2049)]
-    out["allA4099"] = [_ascii(np.zeros(4099))]               # one prefix class far over the cap
-    out["AC3000"] = [_ascii(np.tile([0, 1], 3000))]
-    out["unit997x64"] = [np.tile(R(997), 64)]
-    out["tails"] = [np.concatenate([_ascii(np.full(40, 3)), R(3000), _ascii(np.zeros(40))])]      # padded tail keys tie on both strands
-    c = R(20000)
-    out["twice20k"] = [c, c.copy()]                          # two identical contigs
-    h = R(2500)
-    out["selfrc5k"] = [np.concatenate([h, synth.revcomp(h)])]   # equal to its own reverse complement
-    return out
-
-
-SHAPES = _shapes()
-
-
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_shapes_against_the_serial_host_builder(tmp_path, shape):
     pac, G = _check(_host_index(tmp_path, SHAPES[shape]), batch_cap=1024, occ_segment=4)
