@@ -1,4 +1,5 @@
 // gsalign_amd/csrc/gsa_api.hip -- the C-ABI entry points (include/gsa_hip.h) that RUN a query and read its result; block lists: gsa_blocks.cpp
+#include <algorithm>
 #include <cstring>
 #include "gsa_ctx.h"
 
@@ -35,9 +36,9 @@ static int rewind_to_hits(gsa_ctx *c)
 	return stage1_restore_pdbm(c);
 }
 
-// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip, k_proj.hip) ask of the context before they run; `who`: the export, for the messages;
-// need_positions: the pass reads the positions of gsa_lift_set; need_window: the window of gsa_track_set; need_acc: it paints into the accumulator of gsa_proj_open
-static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false, bool need_window = false, bool need_acc = false)
+// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip, k_proj.hip, k_regions.hip) ask of the context before they run; `who`: the export, for the messages;
+// need_positions: the pass reads the positions of gsa_lift_set; need_window: the window of gsa_track_set; need_acc: it paints into the accumulator of gsa_proj_open; need_regions: it reads the regions of gsa_regions_set
+static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false, bool need_window = false, bool need_acc = false, bool need_regions = false)
 {
 	const std::string w(who);
 	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, w + ": the context holds no finished (stage 8) result");
@@ -47,6 +48,7 @@ static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_p
 	if (need_positions && c->lift_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no positions (gsa_lift_set first)");
 	if (need_window && c->track_w <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no window (gsa_track_set first)");
 	if (need_acc && !c->proj) return gsa_fail(c, GSA_ERR_STATE, w + ": no accumulator (gsa_proj_open first)");
+	if (need_regions && c->reg_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no regions (gsa_regions_set first)");
 	GSA_CHECK(c, hipSetDevice(c->device));
 	return GSA_OK;
 }
@@ -81,6 +83,19 @@ int lift_call(gsa_ctx *c, int32_t k, gsa_lifts *out)
 	const auto t0 = std::chrono::steady_clock::now();
 	rc = lift_positions(c, k, out);
 	c->lift_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->lift_calls++;
+	return rc;
+}
+
+// the regions of gsa_regions_set through the stage-8 result the context holds: k_regions.hip
+int regions_call(gsa_ctx *c, int32_t k, gsa_region_lifts *out)
+{
+	if (!c || !out) return GSA_ERR_ARG;
+	out->n_hits = 0; out->hits = nullptr;
+	int rc = result_pass_ready(c, k, "gsa_lift_regions", false, false, false, true);
+	if (rc) return rc;
+	const auto t0 = std::chrono::steady_clock::now();
+	rc = lift_regions(c, k, out);
+	c->reg_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->reg_calls++;
 	return rc;
 }
 
@@ -325,6 +340,32 @@ int gsa_lift_set(gsa_ctx *c, const int64_t *pos, int64_t n)
 }
 int gsa_lift(gsa_ctx *c, int32_t k, gsa_lifts *out) { return lift_call(c, k, out); }
 int gsa_get_lift_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::lift_ms_sum, &gsa_ctx::lift_calls, ms_sum, n_calls); }
+
+int gsa_regions_set(gsa_ctx *c, const int64_t *beg, const int64_t *end, int64_t n)
+{
+	if (!c || n < 0 || (n > 0 && (!beg || !end))) return GSA_ERR_ARG;
+	if (n >= (1ll << 31) - 256) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_regions_set: too many regions");
+	for (int64_t i = 0; i < n; i++) {
+		const std::string who = "gsa_regions_set: region [" + std::to_string((long long)beg[i]) + ", " + std::to_string((long long)end[i]) + ") (entry " + std::to_string((long long)i) + ")";
+		if (beg[i] < 0 || end[i] > c->G || beg[i] >= c->G) return gsa_fail(c, GSA_ERR_ARG, who + " lies outside the reference [0, " + std::to_string((long long)c->G) + ")");
+		if (beg[i] >= end[i]) return gsa_fail(c, GSA_ERR_ARG, who + (beg[i] == end[i] ? " is empty" : " is reversed"));
+		// (the sequence that holds beg: the last one that starts at or before it)
+		const size_t s = (size_t)(std::upper_bound(c->h_chr_fwd.begin(), c->h_chr_fwd.end(), (i64)beg[i]) - c->h_chr_fwd.begin()) - 1;
+		if (s >= c->h_chr_len.size() || end[i] > c->h_chr_fwd[s] + (i64)c->h_chr_len[s]) return gsa_fail(c, GSA_ERR_ARG, who + " crosses a sequence boundary");
+	}
+	if (n == 0) { c->reg_n = 0; return GSA_OK; }
+	GSA_CHECK(c, hipSetDevice(c->device));
+	// (the API is synchronous: no pass of this context reads the old regions any more)
+	c->reg_n = 0;      // (a failed allocation or copy leaves the context without regions, never with half of them)
+	ENS(i64, d_rgpos, 2 * (size_t)n);
+	hipError_t e = hipMemcpy(c->d_rgpos.p, beg, (size_t)n * sizeof(i64), hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = hipMemcpy(c->d_rgpos.as<i64>() + n, end, (size_t)n * sizeof(i64), hipMemcpyHostToDevice);
+	if (e != hipSuccess) { return gsa_fail(c, GSA_ERR_HIP, std::string("gsa_regions_set (hipMemcpy H2D): ") + hipGetErrorString(e)); }
+	c->reg_n = n;
+	return GSA_OK;
+}
+int gsa_lift_regions(gsa_ctx *c, int32_t k, gsa_region_lifts *out) { return regions_call(c, k, out); }
+int gsa_get_region_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::reg_ms_sum, &gsa_ctx::reg_calls, ms_sum, n_calls); }
 
 int gsa_track_set(gsa_ctx *c, int32_t window)
 {

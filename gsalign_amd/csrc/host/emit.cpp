@@ -95,6 +95,7 @@ template struct RawArr<gsa_block_cigar>;
 template struct RawArr<gsa_cs_block>;
 template struct RawArr<uint32_t>;
 template struct RawArr<gsa_lift_hit>;
+template struct RawArr<gsa_region_hit>;
 template struct RawArr<gsa_track_win>;
 template struct RawArr<gsa_seg_block>;
 template struct RawArr<gsa_seg>;
@@ -658,6 +659,133 @@ void Emitter::lift_text(bool first, const QueryContig &q, const ContigResult &r,
 		w = put_int(w, (long long)h.qpos + 1); *w++ = '\t';
 		*w++ = h.rev ? '-' : '+'; *w++ = '\t';
 		*w++ = h.cls == GSA_CIGAR_EQ ? '=' : (h.cls == GSA_CIGAR_X ? 'X' : 'D'); *w++ = '\t';
+		w = put_int(w, score[(size_t)h.block]); *w++ = '\t';
+		w = put_int(w, h.n_cover); *w++ = '\n';
+		o.n = (size_t)(w - o.p);
+		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
+	}
+	if (o.n) sink(std::move(o));
+}
+
+// ---- lifted reference intervals ----------------------------------------------------------------------------------------------------------
+void gsah_lift_regions(const HostIndex &ix, const ContigResult &r, const int64_t *beg, const int64_t *end, int64_t n, std::vector<gsa_region_hit> &hits)
+{
+	hits.clear();
+	if (r.summary || n <= 0) return;      // (a summary result holds neither records nor strings)
+	// the blocks with records in the order of their first text position, the running maximum of their trimmed ends beside them (as gsah_lift)
+	struct Blk { int64_t start, end, maxend; int32_t block; };
+	std::vector<Blk> tab;
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		if (b.n_frag <= 0) continue;
+		const gsa_frag first = r.frag(b.frag_off), last = r.frag(b.frag_off + b.n_frag - 1);
+		Blk v; v.start = first.rpos; v.end = last.rpos + last.rlen - extension(ix, b, last); v.maxend = 0; v.block = (int32_t)bi;
+		if (v.end > v.start) tab.push_back(v);
+	}
+	if (tab.empty()) return;
+	std::sort(tab.begin(), tab.end(), [](const Blk &x, const Blk &y) { return x.start != y.start ? x.start < y.start : x.block < y.block; });
+	for (size_t j = 0; j < tab.size(); j++) tab[j].maxend = j ? std::max(tab[j - 1].maxend, tab[j].end) : tab[j].end;
+	struct Best { int32_t block = -1; int64_t ov = 0, start = 0, end = 0; };
+	auto better = [&](int32_t x, int64_t ox, const Best &y) {
+		const gsa_block &a = r.blocks[(size_t)x], &b = r.blocks[(size_t)y.block];
+		if ((a.bdup != 0) != (b.bdup != 0)) return a.bdup == 0;
+		if (ox != y.ov) return ox > y.ov;
+		if (a.score != b.score) return a.score > b.score;
+		return x < y.block;
+	};
+	auto cover = [&](int64_t lo, int64_t hi, Best &best, uint32_t &cnt) {      // the blocks whose coverage overlaps the text interval [lo, hi)
+		size_t j = (size_t)(std::lower_bound(tab.begin(), tab.end(), hi, [](const Blk &b, int64_t v) { return b.start < v; }) - tab.begin());
+		while (j > 0 && tab[j - 1].maxend > lo) {
+			j--;
+			if (tab[j].end <= lo) continue;
+			const int64_t ov = std::min(tab[j].end, hi) - std::max(tab[j].start, lo);
+			cnt++;
+			if (best.block < 0 || better(tab[j].block, ov, best)) { best.block = tab[j].block; best.ov = ov; best.start = tab[j].start; best.end = tab[j].end; }
+		}
+	};
+	std::vector<gsa_region_hit> all((size_t)n);      // block = -1: no block overlaps the region
+	auto one = [&](size_t ib, size_t ie) {
+		for (size_t i = ib; i < ie; i++) {
+			gsa_region_hit &h = all[i];
+			memset(&h, 0, sizeof(h)); h.block = -1;
+			const int64_t p0 = beg[i], p1 = end[i];
+			if (p0 < 0 || p0 >= p1 || p1 > ix.G) continue;
+			{      // (a region that crosses a sequence boundary is no region: gsa_regions_set refuses it)
+				size_t c = 0; while (c + 1 < ix.chr_fwd.size() && ix.chr_fwd[c + 1] <= p0) c++;
+				if (p1 > ix.chr_fwd[c] + ix.chr_len[c]) continue;
+			}
+			Best best; uint32_t cnt = 0;
+			cover(p0, p1, best, cnt); cover(2 * ix.G - p1, 2 * ix.G - p0, best, cnt);
+			if (best.block < 0) continue;
+			const gsa_block &b = r.blocks[(size_t)best.block];
+			const int64_t lo = b.bdir ? p0 : 2 * ix.G - p1, hi = b.bdir ? p1 : 2 * ix.G - p0;
+			const int64_t t_lo = std::max(lo, best.start), t_hi = std::min(hi, best.end);
+			h.idx = (int32_t)i; h.block = best.block; h.rev = b.bdir ? 0 : 1; h.n_cover = (uint16_t)(cnt > 65535u ? 65535u : cnt);
+			h.off_lo = (int32_t)(b.bdir ? t_lo - lo : hi - t_hi); h.off_hi = (int32_t)(b.bdir ? t_hi - lo : hi - t_lo);
+			int64_t a = b.frag_off, z = b.frag_off + b.n_frag;      // the last record that starts at or before t_lo
+			while (z - a > 1) { const int64_t m = (a + z) >> 1; if (r.frag(m).rpos <= t_lo) a = m; else z = m; }
+			// the columns in walk order from the one that holds t_lo through the one that holds t_hi - 1
+			bool in = false, done = false; int32_t q_lo = -1;
+			for (int64_t k = a; k < b.frag_off + b.n_frag && !done; k++) {
+				const gsa_frag f = r.frag(k);
+				if (f.bseed) {
+					const int64_t s = std::max<int64_t>(f.rpos, t_lo), e = std::min<int64_t>(f.rpos + f.rlen, t_hi);
+					if (e <= s) continue;
+					if (!in) { in = true; q_lo = f.qpos + (int32_t)(s - f.rpos); }
+					h.n_eq += (uint32_t)(e - s);
+					if (e == t_hi) done = true;
+					continue;
+				}
+				const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+				int64_t rp = f.rpos; int32_t qp = f.qpos;
+				for (int c = 0; c < f.aln_len; c++) {
+					const bool rb = x1[c] != '-', qb = x2[c] != '-';
+					if (!in && rb && rp == t_lo) { in = true; q_lo = qp; }
+					if (in) {
+						if (!rb) h.n_ins++;
+						else if (!qb) h.n_del++;
+						else if (column_class(x1[c], x2[c]) == (int)GSA_CIGAR_EQ) h.n_eq++;
+						else h.n_x++;
+						if (rb && rp == t_hi - 1) { done = true; break; }
+					}
+					if (rb) rp++;
+					if (qb) qp++;
+				}
+			}
+			h.q_lo = q_lo; h.q_hi = q_lo + (int32_t)(h.n_eq + h.n_x + h.n_ins);
+		}
+	};
+	if ((size_t)n * sizeof(gsa_region_hit) >= par_min_bytes()) par_ranges((size_t)n, (size_t)1 << 12, one); else one(0, (size_t)n);
+	for (size_t i = 0; i < (size_t)n; i++) if (all[i].block >= 0) hits.push_back(all[i]);
+}
+
+// <prefix>.regions.tsv: one line per hit -- reference name, the region (0-based, half-open, inside the sequence), its name, the covered part, query name, the query
+// interval (0-based, half-open, in the contig as stored), strand, the four counts, the block's score as the MAF prints it (trimmed; 1 for a duplicate), n_cover
+void Emitter::regions_text(bool first, const QueryContig &q, const ContigResult &r, const gsa_region_hit *hits, int64_t n_hits, const int32_t *ref_chr, const int32_t *ref_beg,
+                           const int32_t *ref_end, const std::string *name, const std::function<void(OutBuf &&)> &sink) const
+{
+	OutBuf o;
+	if (first) o.append("#ref\tstart\tend\tname\tcstart\tcend\tquery\tqstart\tqend\tstrand\tmatch\tmismatch\tdeleted\tinserted\tscore\tn_cover\n");
+	std::vector<int> score(r.blocks.size(), 0);
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		score[bi] = b.bdup ? 1 : b.score;
+		if (!b.bdup && b.n_frag > 0 && !r.summary) score[bi] -= extension(*idx, b, r.frag(b.frag_off + b.n_frag - 1));
+	}
+	for (int64_t i = 0; i < n_hits; i++) {
+		const gsa_region_hit &h = hits[i];
+		if (h.block < 0 || (size_t)h.block >= r.blocks.size()) continue;
+		const std::string &rname = idx->chr_name[(size_t)ref_chr[h.idx]], &nm = name[h.idx];
+		o.reserve(o.n + rname.size() + nm.size() + q.name.size() + 256);
+		char *w = o.p + o.n;
+		memcpy(w, rname.data(), rname.size()); w += rname.size(); *w++ = '\t';
+		w = put_int(w, ref_beg[h.idx]); *w++ = '\t'; w = put_int(w, ref_end[h.idx]); *w++ = '\t';
+		memcpy(w, nm.data(), nm.size()); w += nm.size(); *w++ = '\t';
+		w = put_int(w, (long long)ref_beg[h.idx] + h.off_lo); *w++ = '\t'; w = put_int(w, (long long)ref_beg[h.idx] + h.off_hi); *w++ = '\t';
+		memcpy(w, q.name.data(), q.name.size()); w += q.name.size(); *w++ = '\t';
+		w = put_int(w, h.q_lo); *w++ = '\t'; w = put_int(w, h.q_hi); *w++ = '\t';
+		*w++ = h.rev ? '-' : '+'; *w++ = '\t';
+		w = put_int(w, h.n_eq); *w++ = '\t'; w = put_int(w, h.n_x); *w++ = '\t'; w = put_int(w, h.n_del); *w++ = '\t'; w = put_int(w, h.n_ins); *w++ = '\t';
 		w = put_int(w, score[(size_t)h.block]); *w++ = '\t';
 		w = put_int(w, h.n_cover); *w++ = '\n';
 		o.n = (size_t)(w - o.p);

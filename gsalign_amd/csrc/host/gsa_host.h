@@ -129,6 +129,12 @@ void gsah_segs_trim(const gsa_seg *segs, int64_t n, int bdir, int64_t ext, std::
 // gsa_lift, and the lift of a host that holds a gsa_result and no GPU context.  hits: ascending in idx, positions no block covers (or outside [0, G)) absent.
 void gsah_lift(const HostIndex &ix, const ContigResult &r, const int64_t *pos, int64_t n, std::vector<gsa_lift_hit> &hits);
 
+// The regions [beg[i], end[i]) (0-based forward global reference coordinates, half-open) lifted through a finished contig, by the contract of gsa_lift_regions (gsa_hip.h):
+// trimmed coverage, the choice among overlapping blocks (overlap before score), the span's four class counts and its query interval -- from the records and the two gapped
+// strings, column by column.  The comparator of gsa_lift_regions, and the interval lift of a host that holds a gsa_result and no GPU context.  hits: ascending in idx,
+// regions no block overlaps (or that are empty, outside [0, G) or across a sequence boundary) absent.
+void gsah_lift_regions(const HostIndex &ix, const ContigResult &r, const int64_t *beg, const int64_t *end, int64_t n, std::vector<gsa_region_hit> &hits);
+
 // The per-window track of a finished contig over the reference sequences at window length W, by the contract of gsa_ref_track (gsa_hip.h): counted blocks, trimmed
 // coverage, column classes, the insertion rule -- from the records and the two gapped strings.  The comparator of gsa_ref_track, and the track of a host that holds a
 // gsa_result and no GPU context.  win: one record per window with n_cov > 0, ascending by (chr, start); empty for a summary result or W <= 0.
@@ -167,6 +173,12 @@ struct Emitter {
 	// and 1-based position of every input position (gsa_lift_hit::idx indexes them)
 	void lift_text(bool first, const QueryContig &q, const ContigResult &r, const gsa_lift_hit *hits, int64_t n_hits, const int32_t *ref_chr, const int32_t *ref_pos,
 	               const std::function<void(OutBuf &&)> &sink) const;
+	// <prefix>.regions.tsv (-liftbed): one line per hit of gsa_lift_regions / gsah_lift_regions, in the order given -- reference name, the region's start and end (BED-style:
+	// 0-based, half-open, inside the sequence), its name, the covered part's start and end, query name, the query interval (0-based, half-open, in the contig as stored),
+	// + / -, match, mismatch, deleted, inserted, the block's score as the MAF prints it (1 for a duplicate), n_cover; first: the header line in front.  ref_chr / ref_beg /
+	// ref_end / name: sequence, local interval and name of every input region (gsa_region_hit::idx indexes them)
+	void regions_text(bool first, const QueryContig &q, const ContigResult &r, const gsa_region_hit *hits, int64_t n_hits, const int32_t *ref_chr, const int32_t *ref_beg,
+	                  const int32_t *ref_end, const std::string *name, const std::function<void(OutBuf &&)> &sink) const;
 	// <prefix>.track.tsv (-track W): one line per window of gsa_ref_track / gsah_track, in the order given -- reference name, start and end (BED-style: 0-based, half-open,
 	// inside the sequence), query name, covered, match, mismatch, deleted, inserted; first: the header line in front
 	void track_text(bool first, const QueryContig &q, const gsa_track_win *win, int64_t n_win, const std::function<void(OutBuf &&)> &sink) const;

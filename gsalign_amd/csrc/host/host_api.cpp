@@ -328,6 +328,26 @@ long long gsah_c_lift(const char *index_prefix, const gsa_result *res, const int
 	return (long long)h.size();
 }
 
+// gsah_lift_regions through the C API: the regions [beg[i], end[i]) lifted through one finished contig, on the host -- what gsa_lift_regions gives.  out[cap]; returns the
+// number of hits (call with cap = 0 to size `out`), < 0 on error.  The index of the last prefix stays loaded, behind a lock, as in gsah_c_lift (only its sequence table is read).
+long long gsah_c_lift_regions(const char *index_prefix, const gsa_result *res, const int64_t *beg, const int64_t *end, long long n, gsa_region_hit *out, long long cap)
+{
+	static std::mutex mu; static std::string have; static HostIndex *idx = nullptr;
+	std::lock_guard<std::mutex> lock(mu);
+	if (!index_prefix || !res || n < 0 || (n > 0 && (!beg || !end)) || (cap > 0 && !out)) return -1;
+	if (!idx || have != index_prefix) {
+		delete idx; idx = new HostIndex; have.clear(); std::string e;
+		if (!gsah_load_index(index_prefix, *idx, e)) { delete idx; idx = nullptr; return -2; }
+		have = index_prefix;
+	}
+	ContigResult cr; cr.assign(*res);
+	std::vector<gsa_region_hit> h;
+	gsah_lift_regions(*idx, cr, beg, end, n, h);
+	const size_t m = std::min<size_t>(h.size(), cap > 0 ? (size_t)cap : 0);
+	if (m) memcpy(out, h.data(), m * sizeof(gsa_region_hit));
+	return (long long)h.size();
+}
+
 // gsah_track through the C API: the per-window track of one finished contig at window length W, on the host -- what gsa_ref_track gives.  out[cap]; returns the number
 // of windows (call with cap = 0 to size `out`), < 0 on error.  The index of the last prefix stays loaded, behind a lock, as in gsah_c_lift (only its sequence table is read).
 long long gsah_c_track(const char *index_prefix, const gsa_result *res, int32_t W, gsa_track_win *out, long long cap)

@@ -7,7 +7,8 @@
 // (one JSON line on stderr: where the wall time of the run went).  -gpuindex: an index that has to be built (`index`, or -r) gets its BWT/SA half from the
 // GPU (gsa_build_index_opts) instead of the host's suffix sorters; the files are the same bytes.  -memindex (with -r): no index file at all -- the reference FASTA is
 // parsed (gsah_reference_from_fasta) and the first GPU's context is made from its .pac bytes in device memory (gsa_create_from_pac).  -lift FILE: the reference positions
-// listed in FILE (name, 1-based position; a VCF works as it is) are carried through every contig's alignment on the GPU (gsa_lift) and written to <prefix>.lift.tsv.
+// listed in FILE (name, 1-based position; a VCF works as it is) are carried through every contig's alignment on the GPU (gsa_lift) and written to <prefix>.lift.tsv.  -liftbed FILE: the reference
+// intervals of FILE (BED) are carried through every contig's alignment on the GPU (gsa_lift_regions) and written with their class counts to <prefix>.regions.tsv.
 // -track W: the reference sequences in windows of W bases -- covered, matching, mismatching, deleted and inserted bases per window and query contig, computed on the GPU
 // (gsa_ref_track) and written to <prefix>.track.tsv.  -proj: the query in reference coordinates -- one character per reference base over all
 // query contigs, painted on the GPU into one accumulator per device (gsa_project) and written to <prefix>.proj.fa.  -chain: every alignment as a UCSC chain (for liftOver, CrossMap, bcftools +liftover), its size / dt / dq lines
@@ -59,6 +60,7 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -lift  FILE    lift the reference positions of FILE (tab-separated: sequence name, 1-based position; '#' lines skipped, a VCF works) to the query on the GPU (gsa_lift): <prefix>.lift.tsv\n");
 	fprintf(stderr, "         -proj          project the query onto the reference on the GPU (gsa_project): one character per reference base over all query sequences -- the aligned query base, '-' deleted, 'n' not aligned: <prefix>.proj.fa\n");
 	fprintf(stderr, "         -track INT     per window of INT reference bases and query sequence: covered / matching / mismatching / deleted / inserted bases, computed on the GPU (gsa_ref_track): <prefix>.track.tsv\n");
+	fprintf(stderr, "         -liftbed FILE  lift the reference intervals of FILE (BED: sequence name, 0-based start, end, optional name) to the query on the GPU (gsa_lift_regions), with match / mismatch / deleted / inserted counts: <prefix>.regions.tsv\n");
 	fprintf(stderr, "         -chain         write every alignment as a UCSC chain (liftOver, CrossMap), its segments computed on the GPU (gsa_block_segs): <prefix>.chain [false]\n");
 	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
 	fprintf(stderr, "         -gpuindex      build the index (-r, or `%s index [-gpuindex] [-gpu N] ref.fa prefix`) on the GPU (gsa_build_index_opts; over 1.07 Gbp its batched 64-bit sorter) [false]\n", prog);
@@ -134,6 +136,40 @@ static bool load_lift_file(const char *path, const HostIndex &idx, std::vector<i
 	return ok;
 }
 
+// -liftbed FILE: BED -- name <tab> 0-based start <tab> end [<tab> region name [<tab> anything]]; '#', "track", "browser" and empty lines are skipped.  beg / end: 0-based
+// forward global coordinates, chr / lo / hi: sequence and local interval of every entry, name: its 4th column ("." when absent).  false: one line on stderr (the file,
+// a malformed line, an unknown name, start >= end, an end beyond its sequence)
+static bool load_bed_file(const char *path, const HostIndex &idx, std::vector<int64_t> &beg, std::vector<int64_t> &end, std::vector<int32_t> &chr, std::vector<int32_t> &lo,
+                          std::vector<int32_t> &hi, std::vector<std::string> &name)
+{
+	FILE *fp = fopen(path, "r");
+	if (!fp) { fprintf(stderr, "-liftbed: cannot open %s\n", path); return false; }
+	std::string line; long long ln = 0; bool ok = true;
+	for (int ch = 0; ok && ch != EOF;) {
+		line.clear();
+		while ((ch = fgetc(fp)) != EOF && ch != '\n') line.push_back((char)ch);
+		ln++;
+		if (!line.empty() && line[line.size() - 1] == '\r') line.resize(line.size() - 1);
+		if (line.empty() || line[0] == '#' || line.compare(0, 5, "track") == 0 || line.compare(0, 7, "browser") == 0) continue;
+		const size_t t1 = line.find('\t'), t2 = t1 == std::string::npos ? t1 : line.find('\t', t1 + 1);
+		char *e1 = nullptr, *e2 = nullptr;
+		const long long p0 = t2 == std::string::npos ? 0 : strtoll(line.c_str() + t1 + 1, &e1, 10), p1 = t2 == std::string::npos ? 0 : strtoll(line.c_str() + t2 + 1, &e2, 10);
+		if (t2 == std::string::npos || e1 != line.c_str() + t2 || e1 == line.c_str() + t1 + 1 || e2 == line.c_str() + t2 + 1 || (*e2 != 0 && *e2 != '\t')) {
+			fprintf(stderr, "-liftbed: %s line %lld: expected a sequence name, a start and an end, tab-separated\n", path, ln); ok = false; break;
+		}
+		const std::string sname = line.substr(0, t1);
+		size_t c = 0; while (c < idx.chr_name.size() && idx.chr_name[c] != sname) c++;
+		if (c == idx.chr_name.size()) { fprintf(stderr, "-liftbed: %s line %lld: unknown reference sequence %s\n", path, ln, sname.c_str()); ok = false; break; }
+		if (p0 < 0 || p0 >= p1) { fprintf(stderr, "-liftbed: %s line %lld: start %lld is not below end %lld\n", path, ln, p0, p1); ok = false; break; }
+		if (p1 > idx.chr_len[c]) { fprintf(stderr, "-liftbed: %s line %lld: end %lld lies beyond %s (%d bases)\n", path, ln, p1, sname.c_str(), idx.chr_len[c]); ok = false; break; }
+		std::string nm = ".";
+		if (*e2 == '\t') { const size_t a = (size_t)(e2 - line.c_str()) + 1, z = line.find('\t', a); if (z != a && a < line.size()) nm = line.substr(a, z == std::string::npos ? z : z - a); }
+		beg.push_back(idx.chr_fwd[c] + p0); end.push_back(idx.chr_fwd[c] + p1); chr.push_back((int32_t)c); lo.push_back((int32_t)p0); hi.push_back((int32_t)p1); name.push_back(nm);
+	}
+	fclose(fp);
+	return ok;
+}
+
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int main(int argc, char *argv[])
@@ -146,7 +182,7 @@ int main(int argc, char *argv[])
 	gsa_params prm; gsa_default_params(&prm);
 	int threads = HostPool::default_threads(), fmt = 1, n_ctx_per_gpu = 2; bool vcf = true, allow_dup = true, dotplot = false, gpuvar = false, want_cs = false, want_chain = false, want_proj = false, gpuindex = false, memindex = false, timing = getenv("GSA_TIMING") != NULL;
 	std::vector<int> gpus;
-	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL, *lift_file = NULL;
+	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL, *lift_file = NULL, *bed_file = NULL;
 	int track_w = 0;      // -track W (0: no track)
 	if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(argv[0], threads, prm, fmt); return 0; }
 	if (strcmp(argv[1], "index") == 0) {
@@ -181,6 +217,7 @@ int main(int argc, char *argv[])
 		else if (a == "-chain") want_chain = true;
 		else if (a == "-proj") want_proj = true;
 		else if (a == "-lift" && i + 1 < argc) lift_file = argv[++i];
+		else if (a == "-liftbed" && i + 1 < argc) bed_file = argv[++i];
 		else if (a == "-track" && i + 1 < argc) {
 			char *end = NULL; const long long w = strtoll(argv[++i], &end, 10);
 			if (end == argv[i] || *end || w < 1 || w > 0x7fffffffll) { fprintf(stderr, "-track: the window must be a number of bases from 1 to 2147483647 (got %s)\n", argv[i]); return 1; }
@@ -228,7 +265,7 @@ int main(int argc, char *argv[])
 	double t_reserve = 0, t_reserve_wait = 0, t_unpack_wait = 0, t_at_align = 0;
 	std::thread reserver([&] {
 		if (memindex) return;      // (no .bwt header to read the text length from, and gsa_create_from_pac adopts no reservation)
-		if (lift_file) return;     // (-lift: no GPU work before the position file has been checked against the reference's sequence table, which needs the index files)
+		if (lift_file || bed_file) return;     // (-lift, -liftbed: no GPU work before the position file has been checked against the reference's sequence table, which needs the index files)
 		const double t = now_s();
 		uint64_t hdr[5] = { 0, 0, 0, 0, 0 };
 		FILE *fb = fopen((prefix + ".bwt").c_str(), "rb");
@@ -247,6 +284,12 @@ int main(int argc, char *argv[])
 	if (lift_file && !load_lift_file(lift_file, idx, lift_pos, lift_chr, lift_at)) return 1;
 	const bool want_lift = lift_file != NULL && !lift_pos.empty();
 	if (lift_file && !want_lift) fprintf(stderr, "Warning! -lift: %s holds no position\n", lift_file);
+
+	// -liftbed: the same for the regions
+	std::vector<int64_t> bed_beg, bed_end; std::vector<int32_t> bed_chr, bed_lo, bed_hi; std::vector<std::string> bed_name;
+	if (bed_file && !load_bed_file(bed_file, idx, bed_beg, bed_end, bed_chr, bed_lo, bed_hi, bed_name)) return 1;
+	const bool want_regions = bed_file != NULL && !bed_beg.empty();
+	if (bed_file && !want_regions) fprintf(stderr, "Warning! -liftbed: %s holds no region\n", bed_file);
 
 	// FindGnuPlotPath (main.cpp:169-191): -dp needs a gnuplot binary -- the one -gp names, else the first one on PATH; without one the
 	// reference plots nothing either
@@ -329,6 +372,9 @@ int main(int argc, char *argv[])
 	}
 	if (want_lift) for (gsa_ctx *c : ctxs) if (gsa_lift_set(c, lift_pos.data(), (int64_t)lift_pos.size()) != GSA_OK) { fprintf(stderr, "-lift: %s\n", gsa_last_error(c)); return 2; }
 
+	if (want_regions) for (gsa_ctx *c : ctxs) if (gsa_regions_set(c, bed_beg.data(), bed_end.data(), (int64_t)bed_beg.size()) != GSA_OK) { fprintf(stderr, "-liftbed: %s\n", gsa_last_error(c)); return 2; }
+
+	const std::string regn = std::string(out_prefix) + ".regions.tsv";
 	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv", trackn = std::string(out_prefix) + ".track.tsv", chainn = std::string(out_prefix) + ".chain", projn = std::string(out_prefix) + ".proj.fa";
 	Emitter em; em.idx = &idx; em.allow_dup = allow_dup;
 	long long n_aln = 0, tot_len = 0, tot_match = 0, n_dup = 0;
@@ -345,11 +391,12 @@ int main(int argc, char *argv[])
 		bool want_cig = false; std::vector<RawArr<gsa_block_cigar> > cblk; std::vector<RawArr<uint32_t> > cops;      // -fmt 3: the contig's CIGARs as gsa_block_cigars left them
 		std::vector<RawArr<gsa_cs_block> > sblk; std::vector<RawArr<char> > sbytes; bool want_cs = false;      // -cs: the contig's cs strings as gsa_block_cs left them
 		std::vector<RawArr<gsa_lift_hit> > lift; bool want_lift = false;      // -lift: the contig's hits as gsa_lift left them
+		std::vector<RawArr<gsa_region_hit> > regions; bool want_regions = false;      // -liftbed: the contig's hits as gsa_lift_regions left them
 		std::vector<RawArr<gsa_track_win> > track; bool want_track = false;   // -track: the contig's windows as gsa_ref_track left them
 		std::vector<RawArr<gsa_seg_block> > gblk; std::vector<RawArr<gsa_seg> > gseg; bool want_segs = false;   // -chain: the contig's triples as gsa_block_segs left them
 	} sink;
 	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size()); sink.sblk.resize(qs.size()); sink.sbytes.resize(qs.size()); sink.want_cs = want_cs; sink.want_cig = fmt == 3; sink.lift.resize(qs.size()); sink.want_lift = want_lift; sink.track.resize(qs.size()); sink.want_track = track_w != 0;
-	sink.gblk.resize(qs.size()); sink.gseg.resize(qs.size()); sink.want_segs = want_chain;
+	sink.gblk.resize(qs.size()); sink.gseg.resize(qs.size()); sink.want_segs = want_chain; sink.regions.resize(qs.size()); sink.want_regions = want_regions;
 	const bool var_on_gpu = gpuvar && vcf;          // (-no_vcf: nobody reads the variants)
 	// the MAF file: created by the first contig that has alignments ("w" for contig 0, "a" afterwards: tools.cpp:158-163 -- a run whose
 	// first contig aligns nowhere appends to whatever the file held, as the reference does)
@@ -358,6 +405,8 @@ int main(int argc, char *argv[])
 	size_t written = 0;
 	FILE *lift_fp = NULL;
 	if (want_lift && !(lift_fp = fopen(liftn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", liftn.c_str(), strerror(errno)); }
+	FILE *reg_fp = NULL;
+	if (want_regions && !(reg_fp = fopen(regn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", regn.c_str(), strerror(errno)); }
 	FILE *track_fp = NULL;
 	if (track_w && !(track_fp = fopen(trackn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", trackn.c_str(), strerror(errno)); }
 	FILE *chain_fp = NULL; int64_t chain_id = 0;
@@ -378,6 +427,10 @@ int main(int argc, char *argv[])
 		if (lift_fp) {      // (query contigs in file order, a contig's hits in input order; a contig without alignments has none)
 			em.lift_text(ci == 0, qs[ci], cr, sink.lift[ci].data(), (int64_t)sink.lift[ci].size(), lift_chr.data(), lift_at.data(), [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, lift_fp) != o.n) out_failed = true; });
 			sink.lift[ci].reset();
+		}
+		if (reg_fp) {      // (query contigs in file order, a contig's hits in input order; a contig without alignments has none)
+			em.regions_text(ci == 0, qs[ci], cr, sink.regions[ci].data(), (int64_t)sink.regions[ci].size(), bed_chr.data(), bed_lo.data(), bed_hi.data(), bed_name.data(), [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, reg_fp) != o.n) out_failed = true; });
+			sink.regions[ci].reset();
 		}
 		if (cr.blocks.empty()) return;
 		long long len = 0, score = 0;
@@ -472,6 +525,11 @@ int main(int argc, char *argv[])
 			if (gsa_extras_lift(ex, &lf) != GSA_OK) return 1;
 			sk.lift[(size_t)ci].assign(lf.hits, (size_t)lf.n_hits);
 		}
+		if (sk.want_regions) {
+			gsa_region_lifts rg;
+			if (gsa_extras_regions(ex, &rg) != GSA_OK) return 1;
+			sk.regions[(size_t)ci].assign(rg.hits, (size_t)rg.n_hits);
+		}
 		if (sk.want_segs) {
 			gsa_segs sg;
 			if (gsa_extras_segs(ex, &sg) != GSA_OK) return 1;
@@ -489,7 +547,7 @@ int main(int argc, char *argv[])
 	};
 	if (timing && var_on_gpu) for (gsa_ctx *c : ctxs) (void)gsa_set_profiling(c, 8);      // (the variant passes' device time, for the GSA_VARIANT_PASS line)
 	const double ta = now_s(); t_at_align = ta - T0;
-	const int rc_many = (fmt == 3 || want_lift || track_w || want_chain || want_proj) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u) | (want_chain ? GSA_WANT_SEGS : 0u) | (want_proj ? GSA_WANT_PROJ : 0u), on_result_ex, &sink)
+	const int rc_many = (fmt == 3 || want_lift || track_w || want_chain || want_proj || want_regions) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u) | (want_chain ? GSA_WANT_SEGS : 0u) | (want_proj ? GSA_WANT_PROJ : 0u) | (want_regions ? GSA_WANT_REGIONS : 0u), on_result_ex, &sink)
 	                  : var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
 	                               : gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
 	t_align = now_s() - ta;
@@ -498,6 +556,7 @@ int main(int argc, char *argv[])
 	double cigar_ms = 0;      // -fmt 3: wall time the workers spent inside gsa_block_cigars, all contexts
 	double cs_ms = 0;         // -cs: the same of gsa_block_cs (which runs the CIGAR walk itself: cigar_s is 0 then)
 	double lift_ms = 0;       // -lift: the same of gsa_lift
+	double regions_ms = 0;    // -liftbed: the same of gsa_lift_regions
 	double track_ms = 0;      // -track: the same of gsa_ref_track
 	double chain_ms = 0;      // -chain: the same of gsa_block_segs (its CIGAR walk included unless -cs ran it)
 	double proj_ms = 0;       // -proj: the same of gsa_project, plus the fetch, merge and write below
@@ -508,6 +567,7 @@ int main(int argc, char *argv[])
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_cigar_timing(c, &cm, &cn) == GSA_OK) cigar_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_cs_timing(c, &cm, &cn) == GSA_OK) cs_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_lift_timing(c, &cm, &cn) == GSA_OK) lift_ms += cm; }
+		{ double cm = 0; int64_t cn = 0; if (gsa_get_region_timing(c, &cm, &cn) == GSA_OK) regions_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_track_timing(c, &cm, &cn) == GSA_OK) track_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_seg_timing(c, &cm, &cn) == GSA_OK) chain_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_proj_timing(c, &cm, &cn) == GSA_OK) proj_ms += cm; }
@@ -545,6 +605,7 @@ int main(int argc, char *argv[])
 	std::thread destroyer([&] { if (rc_many != GSA_OK) return; const double t = now_s(); for (size_t k = ctxs.size(); k-- > 0;) gsa_destroy(ctxs[k]); t_destroy = now_s() - t; });      // clones before the owners of their index (after an error the contexts stay: their messages are printed below)
 	formatter.join();
 	if (lift_fp) { if (ferror(lift_fp) | fclose(lift_fp)) out_failed = true; lift_fp = NULL; }
+	if (reg_fp) { if (ferror(reg_fp) | fclose(reg_fp)) out_failed = true; reg_fp = NULL; }
 	if (track_fp) { if (ferror(track_fp) | fclose(track_fp)) out_failed = true; track_fp = NULL; }
 	if (chain_fp) { if (ferror(chain_fp) | fclose(chain_fp)) out_failed = true; chain_fp = NULL; }
 	double maf_write_s = 0; unsigned long long maf_bytes = 0;
@@ -585,10 +646,10 @@ int main(int argc, char *argv[])
 		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, \"cigar_s\": %.3f, "
 		        "\"result_copy_s_sum\": %.3f, \"maf_format_s\": %.3f, \"variants_s\": %.3f, \"output_drain_after_align_s\": %.3f, \"maf_write_s\": %.3f, \"maf_bytes\": %llu, "
 		        "\"vcf_s\": %.3f, \"vcf_write_s\": %.3f, \"vcf_bytes\": %llu, \"destroy_s\": %.3f, \"host_threads\": %d, \"contexts\": %d, \"query_bp\": %lld, \"contigs\": %d, \"gbp_per_s_excl_index_build\": %.4f, "
-		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"proj_s\": %.3f, \"chain_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
+		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"regions_s\": %.3f, \"proj_s\": %.3f, \"chain_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
 		        total, t_build, t_index, t_create, t_query, t_pin, t_align, cigar_ms / 1e3, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
-		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, proj_ms / 1e3, chain_ms / 1e3, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
+		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, regions_ms / 1e3, proj_ms / 1e3, chain_ms / 1e3, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
 	}
 	if (timing && var_on_gpu) fprintf(stderr, "GSA_VARIANT_PASS {\"device_ms_sum\": %.3f, \"passes\": %lld, \"query_bp\": %lld}\n", var_dev_ms, var_dev_n, [&] { long long b = 0; for (const QueryContig &q : qs) b += (long long)q.seq.size(); return b; }());
 	// (everything is on disk and the GPU is released: the process ends here -- unwinding 20 GB of host buffers and the HIP runtime's own

@@ -291,6 +291,27 @@ def lift(index_prefix, seq, result, positions):
     return H[:int(n)].copy()
 
 
+def lift_regions(index_prefix, seq, result, beg, end):
+    """gsah_c_lift_regions: the reference regions [beg[i], end[i]) (0-based forward global coordinates, half-open) lifted through one finished contig on the host, from
+    the records and the gapped strings -- what Aligner.lift_regions computes on the GPU, by the contract of gsa_lift_regions (include/gsa_hip.h).  result: a capi.Result,
+    a dump dict (oracle layout) or a result dict of capi.Aligner.  The index under index_prefix supplies the reference sequences' lengths (the trim); seq is not needed
+    by the walk and may be None.  Returns a REGION_HIT_DT array, ascending in idx; regions no block overlaps are absent."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    b = np.ascontiguousarray(beg, dtype=np.int64); e = np.ascontiguousarray(end, dtype=np.int64)
+    if b.shape != e.shape or b.ndim != 1:
+        raise ValueError("lift_regions: beg and end must be one-dimensional and of one length")
+    lib = load()
+    lib.gsah_c_lift_regions.restype = C.c_longlong
+    lib.gsah_c_lift_regions.argtypes = [C.c_char_p, C.POINTER(capi.Result), C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
+    H = np.zeros(int(b.size), capi.REGION_HIT_DT)
+    n = lib.gsah_c_lift_regions(index_prefix.encode(), C.byref(result), C.c_void_p(b.ctypes.data), C.c_void_p(e.ctypes.data), int(b.size), C.c_void_p(H.ctypes.data), int(H.size))
+    if n < 0:
+        raise RuntimeError(f"gsah_c_lift_regions -> {n}")
+    return H[:int(n)].copy()
+
+
 def track(index_prefix, seq, result, W: int):
     """gsah_c_track: the per-window track of one finished contig over the reference sequences at window length W, on the host, from the records and the gapped
     strings -- what Aligner.track computes on the GPU, by the contract of gsa_ref_track (include/gsa_hip.h).  result: a capi.Result, a dump dict (oracle layout) or a

@@ -538,8 +538,46 @@ int gsa_proj_merge(gsa_ctx *ctx, int64_t p0, int64_t n, const uint32_t *words);
 /* measurement: host wall time the calling threads spent inside gsa_project on this context since it was created, and the number of calls.  Always on. */
 int gsa_get_proj_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 
+/* ---- lifting reference intervals through the alignment ------------------------------------------------------
+ * Where does an annotated interval of the reference (a gene, an exon, a BED line) lie on the query contig, and how well is it conserved?  A REGION is a half-open
+ * interval [beg, end) of 0-based FORWARD global reference coordinates, 0 <= beg < end <= G, inside ONE reference sequence.  It is the text interval [beg, end) for
+ * forward-strand blocks and [2G - end, 2G - beg) for reverse-strand blocks (t = p and t = 2G - 1 - p, as for gsa_lift).
+ *   coverage  gsa_lift's, TRIMMED: a block covers the text positions first.rpos <= t < min(last.rpos + last.rlen, end of the block's chromosome copy)
+ *   choice    among the blocks of contig k whose coverage overlaps the region in either orientation: bdup == 0 before bdup != 0, then the greater OVERLAP (the region
+ *             bases under the block's coverage), then the greater gsa_block::score, then the smaller block index.  gsa_lift has no overlap to compare; for a region
+ *             of length 1 every overlap is 1 and the choice is exactly gsa_lift's.  n_cover counts ALL overlapping blocks, duplicates included, and saturates at 65535
+ *   span      [t_lo, t_hi): the part of the region's text interval under the chosen block's coverage -- one interval.  The answer is about the block's columns in WALK
+ *             order from the column that holds reference base t_lo through the column that holds t_hi - 1, both included
+ *   classes   the CIGAR pass's, by its rule: a seed is '=' throughout, an equal-length gap that needed no DP is classified base against base, a DP gap is read from the
+ *             op string of its DP job, a pure deletion or insertion record is one class throughout
+ *   n_eq, n_x, n_del   columns of that class in the span; each holds a reference base of the span: n_eq + n_x + n_del == t_hi - t_lo
+ *   n_ins     the I columns strictly inside the span; inserted bases in front of its first or behind its last reference-bearing column are not counted
+ *   q_lo      the first query base at or behind the span's first column in walk order, 0-based in the contig as stored, whatever the strand: gsa_lift's qpos of t_lo
+ *             when that column is '=' / 'X', qpos + 1 when it is 'D'
+ *   q_hi      q_lo + n_eq + n_x + n_ins; a span wholly inside a deletion has q_lo == q_hi.  In a bundle q_lo and q_hi are relative to contig k
+ * The counts cannot overflow: a span is shorter than its reference sequence and its query bases are fewer than the contig's, both < 2^31.
+ * One hit per region that some block overlaps, ascending in idx; regions no block overlaps are absent. */
+typedef struct { int32_t idx, block;          /* index into the regions given to gsa_regions_set; block among contig k's blocks (gsa_result::blocks) */
+                 int32_t off_lo, off_hi;      /* the covered part of the region in FORWARD coordinates, relative to beg: [beg + off_lo, beg + off_hi) */
+                 int32_t q_lo, q_hi;
+                 uint32_t n_eq, n_x, n_del, n_ins;
+                 uint8_t rev, _pad0; uint16_t n_cover; int32_t _pad1; } gsa_region_hit;   /* 48 bytes; rev = 1: the chosen block lies on the reverse strand */
+typedef struct { int64_t n_hits; const gsa_region_hit *hits; } gsa_region_lifts;
+/* The regions to lift: n of them are copied to the context's device and stay until the next gsa_regions_set or gsa_destroy; n = 0 clears them.  A clone starts
+ * without regions.  A region outside [0, G), empty, reversed or crossing a sequence boundary: GSA_ERR_ARG with the first offender and its entry number in
+ * gsa_last_error, nothing changed.  n >= 2^31 - 256: GSA_ERR_LIMIT.  Device memory: about 16 (the region) + 48 (its hit) + 8 (its chosen block and n_cover
+ * between the launches) bytes per region, and 16 bytes per record of the result for the class prefix. */
+int gsa_regions_set(gsa_ctx *ctx, const int64_t *beg, const int64_t *end, int64_t n);
+/* The regions of gsa_regions_set lifted through the stage-8 result the context holds.  Validity, call order, k and the error codes are those of gsa_block_cigars;
+ * without regions GSA_ERR_STATE.  No blocks or no hits: n_hits = 0.  A DP record without a job, or a span the records do not reach, is counted on the device and
+ * fails the call with GSA_ERR_STATE.  The answer lives in buffers of its own: the seven other passes return what they returned before, in any call order, and so
+ * does this call after one of them.  Memory is owned by the context and valid until the next call on it; the hits come home in one copy into pinned memory. */
+int gsa_lift_regions(gsa_ctx *ctx, int32_t k, gsa_region_lifts *out);
+/* measurement: host wall time the calling threads spent inside gsa_lift_regions on this context since it was created, and the number of calls.  Always on. */
+int gsa_get_region_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+
 /* gsa_align_many with optional passes run by the worker in front of the callback -- before the prefetch after next can touch the contig's
- * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track) | GSA_WANT_SEGS (gsa_block_segs) | GSA_WANT_PROJ (gsa_project).  *ex and what it
+ * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track) | GSA_WANT_SEGS (gsa_block_segs) | GSA_WANT_PROJ (gsa_project) | GSA_WANT_REGIONS (gsa_lift_regions).  *ex and what it
  * points to are valid during the callback only, like *res. */
 #define GSA_WANT_VARIANTS 1u
 #define GSA_WANT_CIGARS   2u
@@ -548,6 +586,7 @@ int gsa_get_proj_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 #define GSA_WANT_TRACK    32u  /* gsa_ref_track of every contig; every context of ctx[] must hold a window (gsa_track_set), else GSA_ERR_STATE before any contig is aligned */
 #define GSA_WANT_SEGS     64u  /* gsa_block_segs; implies GSA_WANT_CIGARS */
 #define GSA_WANT_PROJ     128u /* gsa_project of every contig, behind the other passes; it adds nothing behind gsa_extras; every context of ctx[] must hold an accumulator (gsa_proj_open), else GSA_ERR_STATE before any contig is aligned -- but where NO context of ctx[] holds one the bit is refused like an unknown one, GSA_ERR_ARG, as it was before the pass existed */
+#define GSA_WANT_REGIONS  256u /* gsa_lift_regions of every contig; every context of ctx[] must hold regions (gsa_regions_set), else GSA_ERR_STATE before any contig is aligned */
 typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;   /* NULL where not asked for */
 /* The contig's cs strings inside the callback of gsa_align_many_ex: the library hands the callback a LARGER object whose head is the gsa_extras
  * (which keeps its two members and its 16 bytes), and this call reaches what lies behind it -- so it is valid for the `ex` the library passed
@@ -559,6 +598,8 @@ int gsa_extras_lift(const gsa_extras *ex, gsa_lifts *out);
 int gsa_extras_track(const gsa_extras *ex, gsa_tracks *out);
 /* The contig's chain segments inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_SEGS was not asked for). */
 int gsa_extras_segs(const gsa_extras *ex, gsa_segs *out);
+/* The contig's lifted regions inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_REGIONS was not asked for). */
+int gsa_extras_regions(const gsa_extras *ex, gsa_region_lifts *out);
 typedef int (*gsa_result_ex_fn)(void *user, int32_t contig, const gsa_result *res, const gsa_extras *ex);
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
                       uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user);
