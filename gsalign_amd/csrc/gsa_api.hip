@@ -37,107 +37,54 @@ static int rewind_to_hits(gsa_ctx *c)
 }
 
 // What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip, k_proj.hip, k_regions.hip) ask of the context before they run; `who`: the export, for the messages;
-// need_positions: the pass reads the positions of gsa_lift_set; need_window: the window of gsa_track_set; need_acc: it paints into the accumulator of gsa_proj_open; need_regions: it reads the regions of gsa_regions_set
-static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, bool need_positions = false, bool need_window = false, bool need_acc = false, bool need_regions = false)
+// need: the pass reads the positions of gsa_lift_set / the window of gsa_track_set / paints into the accumulator of gsa_proj_open / reads the regions of gsa_regions_set
+enum { NEED_POSITIONS = 1, NEED_WINDOW = 2, NEED_ACC = 4, NEED_REGIONS = 8 };
+static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, unsigned need = 0)
 {
 	const std::string w(who);
 	if (c->stage != 8 || c->split) return gsa_fail(c, GSA_ERR_STATE, w + ": the context holds no finished (stage 8) result");
 	// (the pass reads the contig's bases on the device: a prefetch into the slot that held them leaves another contig there)
 	if (c->q_cur == -2) return gsa_fail(c, GSA_ERR_STATE, w + ": the contig's device copy was overwritten by a prefetch");
 	if (k < 0 || k >= (c->bnd.n ? c->bnd.n : 1)) return gsa_fail(c, GSA_ERR_ARG, w + ": contig index out of range");
-	if (need_positions && c->lift_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no positions (gsa_lift_set first)");
-	if (need_window && c->track_w <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no window (gsa_track_set first)");
-	if (need_acc && !c->proj) return gsa_fail(c, GSA_ERR_STATE, w + ": no accumulator (gsa_proj_open first)");
-	if (need_regions && c->reg_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no regions (gsa_regions_set first)");
+	if ((need & NEED_POSITIONS) && c->lift_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no positions (gsa_lift_set first)");
+	if ((need & NEED_WINDOW) && c->track_w <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no window (gsa_track_set first)");
+	if ((need & NEED_ACC) && !c->proj) return gsa_fail(c, GSA_ERR_STATE, w + ": no accumulator (gsa_proj_open first)");
+	if ((need & NEED_REGIONS) && c->reg_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no regions (gsa_regions_set first)");
 	GSA_CHECK(c, hipSetDevice(c->device));
 	return GSA_OK;
 }
-static int pass_timing(const gsa_ctx *c, double gsa_ctx::*sum, long long gsa_ctx::*calls, double *ms_sum, int64_t *n_calls)
+static int pass_timing(const gsa_ctx *c, Pass pass, double *ms_sum, int64_t *n_calls)
 {
 	if (!c || !ms_sum || !n_calls) return GSA_ERR_ARG;
-	*ms_sum = c->*sum; *n_calls = (int64_t)(c->*calls);
+	*ms_sum = c->pass_stat[pass].ms_sum; *n_calls = (int64_t)c->pass_stat[pass].calls;
 	return GSA_OK;
 }
 
-// the cs string of every block of the stage-8 result the context holds: k_cs.hip
-// (cig: the CIGARs the pass computed on its way, for gsa_align_many_ex -- they lie in the CIGAR pass's own buffers)
-int cs_call(gsa_ctx *c, int32_t k, gsa_cs *out, gsa_cigars *cig)
+// One export of a pass over the stage-8 result the context holds: the answer zeroed (an answer the pass may do without: out_optional), the preconditions, the pass itself
+// (`run`, its driver in its k_*.hip) between two clock reads, its time and the call counted
+template <class Out, class Run>
+static int result_pass(gsa_ctx *c, int32_t k, const char *who, unsigned need, Pass pass, Out *out, Run run, bool out_optional = false)
 {
-	if (!c || !out) return GSA_ERR_ARG;
-	out->n_blocks = 0; out->n_bytes = 0; out->blk = nullptr; out->cs = nullptr;
-	int rc = result_pass_ready(c, k, "gsa_block_cs");
-	if (rc) return rc;
+	if (!c || (!out && !out_optional)) return GSA_ERR_ARG;
+	if (out) *out = Out();
+	if (const int rc = result_pass_ready(c, k, who, need)) return rc;
 	const auto t0 = std::chrono::steady_clock::now();
-	rc = block_cs(c, k, out, cig);
-	c->cs_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->cs_calls++;
+	const int rc = run();
+	c->pass_stat[pass].ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->pass_stat[pass].calls++;
 	return rc;
 }
 
-// the positions of gsa_lift_set through the stage-8 result the context holds: k_lift.hip
-int lift_call(gsa_ctx *c, int32_t k, gsa_lifts *out)
-{
-	if (!c || !out) return GSA_ERR_ARG;
-	out->n_hits = 0; out->hits = nullptr;
-	int rc = result_pass_ready(c, k, "gsa_lift", true);
-	if (rc) return rc;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = lift_positions(c, k, out);
-	c->lift_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->lift_calls++;
-	return rc;
-}
-
-// the regions of gsa_regions_set through the stage-8 result the context holds: k_regions.hip
-int regions_call(gsa_ctx *c, int32_t k, gsa_region_lifts *out)
-{
-	if (!c || !out) return GSA_ERR_ARG;
-	out->n_hits = 0; out->hits = nullptr;
-	int rc = result_pass_ready(c, k, "gsa_lift_regions", false, false, false, true);
-	if (rc) return rc;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = lift_regions(c, k, out);
-	c->reg_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->reg_calls++;
-	return rc;
-}
-
-// the per-window track of the stage-8 result the context holds: k_track.hip
-int track_call(gsa_ctx *c, int32_t k, gsa_tracks *out)
-{
-	if (!c || !out) return GSA_ERR_ARG;
-	out->n_win = 0; out->win = nullptr;
-	int rc = result_pass_ready(c, k, "gsa_ref_track", false, true);
-	if (rc) return rc;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = ref_track(c, k, out);
-	c->track_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->track_calls++;
-	return rc;
-}
-
-// the chain triples of every block of the stage-8 result the context holds: k_segs.hip
+// (cig: the CIGARs the cs pass computed on its way, for gsa_align_many_ex -- they lie in the CIGAR pass's own buffers; cig / have of the segs pass: as block_segs)
+int cs_call(gsa_ctx *c, int32_t k, gsa_cs *out, gsa_cigars *cig) { return result_pass(c, k, "gsa_block_cs", 0, PASS_CS, out, [&] { return block_cs(c, k, out, cig); }); }
+int lift_call(gsa_ctx *c, int32_t k, gsa_lifts *out) { return result_pass(c, k, "gsa_lift", NEED_POSITIONS, PASS_LIFT, out, [&] { return lift_positions(c, k, out); }); }
+int regions_call(gsa_ctx *c, int32_t k, gsa_region_lifts *out) { return result_pass(c, k, "gsa_lift_regions", NEED_REGIONS, PASS_REG, out, [&] { return lift_regions(c, k, out); }); }
+int track_call(gsa_ctx *c, int32_t k, gsa_tracks *out) { return result_pass(c, k, "gsa_ref_track", NEED_WINDOW, PASS_TRACK, out, [&] { return ref_track(c, k, out); }); }
 int segs_call(gsa_ctx *c, int32_t k, gsa_segs *out, gsa_cigars *cig, const gsa_cigars *have)
 {
-	if (!c || !out) return GSA_ERR_ARG;
-	out->n_blocks = 0; out->n_segs = 0; out->blk = nullptr; out->seg = nullptr;
-	if (cig) { cig->n_blocks = 0; cig->n_ops = 0; cig->blk = nullptr; cig->ops = nullptr; }
-	int rc = result_pass_ready(c, k, "gsa_block_segs");
-	if (rc) return rc;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = block_segs(c, k, out, cig, have);
-	c->seg_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->seg_calls++;
-	return rc;
+	if (c && out && cig) *cig = gsa_cigars();
+	return result_pass(c, k, "gsa_block_segs", 0, PASS_SEG, out, [&] { return block_segs(c, k, out, cig, have); });
 }
-
-// the blocks of the stage-8 result the context holds painted into its accumulator: k_proj.hip
-int proj_call(gsa_ctx *c, int32_t k, gsa_proj_stat *out)
-{
-	if (!c) return GSA_ERR_ARG;
-	if (out) { out->n_blocks = 0; out->_pad = 0; out->n_cols = 0; }
-	int rc = result_pass_ready(c, k, "gsa_project", false, false, true);
-	if (rc) return rc;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = project_blocks(c, k, out);
-	c->proj_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->proj_calls++;
-	return rc;
-}
+int proj_call(gsa_ctx *c, int32_t k, gsa_proj_stat *out) { return result_pass(c, k, "gsa_project", NEED_ACC, PASS_PROJ, out, [&] { return project_blocks(c, k, out); }, true); }
 
 extern "C" {
 // Back to stage 0 with the same contig: the query stays where gsa_set_query put it (device and host copy).
@@ -303,24 +250,14 @@ int gsa_call_variants(gsa_ctx *c, int32_t k, gsa_variants *out)
 	const int rc = result_pass_ready(c, k, "gsa_call_variants");
 	return rc ? rc : call_variants(c, k, out);
 }
-int gsa_get_variant_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::var_ms_sum, &gsa_ctx::var_calls, ms_sum, n_calls); }
+int gsa_get_variant_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_VAR, ms_sum, n_calls); }
 
 // the CIGAR of every block of the stage-8 result the context holds: k_cigar.hip
-int gsa_block_cigars(gsa_ctx *c, int32_t k, gsa_cigars *out)
-{
-	if (!c || !out) return GSA_ERR_ARG;
-	out->n_blocks = 0; out->n_ops = 0; out->blk = nullptr; out->ops = nullptr;
-	int rc = result_pass_ready(c, k, "gsa_block_cigars");
-	if (rc) return rc;
-	const auto t0 = std::chrono::steady_clock::now();
-	rc = block_cigars(c, k, out);
-	c->cig_ms_sum += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); c->cig_calls++;
-	return rc;
-}
-int gsa_get_cigar_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::cig_ms_sum, &gsa_ctx::cig_calls, ms_sum, n_calls); }
+int gsa_block_cigars(gsa_ctx *c, int32_t k, gsa_cigars *out) { return result_pass(c, k, "gsa_block_cigars", 0, PASS_CIG, out, [&] { return block_cigars(c, k, out); }); }
+int gsa_get_cigar_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_CIG, ms_sum, n_calls); }
 
 int gsa_block_cs(gsa_ctx *c, int32_t k, gsa_cs *out) { return cs_call(c, k, out, nullptr); }
-int gsa_get_cs_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::cs_ms_sum, &gsa_ctx::cs_calls, ms_sum, n_calls); }
+int gsa_get_cs_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_CS, ms_sum, n_calls); }
 
 int gsa_lift_set(gsa_ctx *c, const int64_t *pos, int64_t n)
 {
@@ -339,7 +276,7 @@ int gsa_lift_set(gsa_ctx *c, const int64_t *pos, int64_t n)
 	return GSA_OK;
 }
 int gsa_lift(gsa_ctx *c, int32_t k, gsa_lifts *out) { return lift_call(c, k, out); }
-int gsa_get_lift_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::lift_ms_sum, &gsa_ctx::lift_calls, ms_sum, n_calls); }
+int gsa_get_lift_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_LIFT, ms_sum, n_calls); }
 
 int gsa_regions_set(gsa_ctx *c, const int64_t *beg, const int64_t *end, int64_t n)
 {
@@ -365,7 +302,7 @@ int gsa_regions_set(gsa_ctx *c, const int64_t *beg, const int64_t *end, int64_t 
 	return GSA_OK;
 }
 int gsa_lift_regions(gsa_ctx *c, int32_t k, gsa_region_lifts *out) { return regions_call(c, k, out); }
-int gsa_get_region_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::reg_ms_sum, &gsa_ctx::reg_calls, ms_sum, n_calls); }
+int gsa_get_region_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_REG, ms_sum, n_calls); }
 
 int gsa_track_set(gsa_ctx *c, int32_t window)
 {
@@ -379,10 +316,10 @@ int gsa_track_set(gsa_ctx *c, int32_t window)
 	return GSA_OK;
 }
 int gsa_ref_track(gsa_ctx *c, int32_t k, gsa_tracks *out) { return track_call(c, k, out); }
-int gsa_get_track_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::track_ms_sum, &gsa_ctx::track_calls, ms_sum, n_calls); }
+int gsa_get_track_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_TRACK, ms_sum, n_calls); }
 
 int gsa_block_segs(gsa_ctx *c, int32_t k, gsa_segs *out) { return segs_call(c, k, out, nullptr, nullptr); }
-int gsa_get_seg_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::seg_ms_sum, &gsa_ctx::seg_calls, ms_sum, n_calls); }
+int gsa_get_seg_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_SEG, ms_sum, n_calls); }
 
 int gsa_proj_open(gsa_ctx *c, gsa_ctx *share, uint32_t flags) { return c ? proj_open(c, share, flags) : GSA_ERR_ARG; }
 int gsa_proj_close(gsa_ctx *c)
@@ -417,7 +354,7 @@ int gsa_proj_merge(gsa_ctx *c, int64_t p0, int64_t n, const uint32_t *words)
 	if (n == 0) return GSA_OK;
 	return words ? proj_merge(c, p0, n, words) : GSA_ERR_ARG;
 }
-int gsa_get_proj_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, &gsa_ctx::proj_ms_sum, &gsa_ctx::proj_calls, ms_sum, n_calls); }
+int gsa_get_proj_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_PROJ, ms_sum, n_calls); }
 
 int gsa_get_wall_sums(gsa_ctx *c, double ms[10], int64_t *n)
 {
@@ -445,8 +382,7 @@ int gsa_set_profiling(gsa_ctx *c, int enable)
 		c->up->copy_ms = c->up->wait_ms = c->up->bytes = 0;
 		c->up->jobs = 0;
 	}
-	c->var_ms_sum = 0;
-	c->var_calls = 0;
+	c->pass_stat[PASS_VAR] = PassStat();
 	c->prof_var = (enable & 8) != 0;
 	c->profiling = (enable & 1) != 0;
 	c->count_blocks = (enable & 2) != 0;

@@ -95,6 +95,10 @@ struct Options {
 // that opened it (gsa_proj_open) and freed by the last one that lets go of it.  dirty: a pass that failed left words behind that nobody vouches for.
 struct ProjAcc { u32 *words = nullptr; i64 G = 0; int device = 0; std::atomic<int> refs{1}; std::atomic<int> dirty{0}; };
 
+// the passes over a stage-8 result, as gsa_ctx::pass_stat counts them
+enum Pass { PASS_VAR, PASS_CIG, PASS_CS, PASS_LIFT, PASS_TRACK, PASS_SEG, PASS_PROJ, PASS_REG, PASS_N };
+struct PassStat { double ms_sum = 0; long long calls = 0; };
+
 struct gsa_ctx {
 	int device = 0;
 	Options opt;
@@ -240,43 +244,40 @@ struct gsa_ctx {
 	DevBuf p_frags, p_blk; bool result_pinned = false;
 	// ---- variants (k_variants.hip): block table, per-record counts, per-workgroup sums + kind counters, the output; pinned: block table, header {n, kinds}, output ----
 	DevBuf d_vblk, d_vcnt, d_vwg, d_var, p_vblk, p_vhdr, p_var;
-	bool prof_var = false; hipEvent_t ev_var[2] = {nullptr, nullptr}; double var_ms_sum = 0; long long var_calls = 0;      // device time of the variant passes since gsa_set_profiling (gsa_get_variant_timing)
+	bool prof_var = false; hipEvent_t ev_var[2] = {nullptr, nullptr};
+	// time and calls per pass (gsa_get_*_timing).  PASS_VAR: device time of the variant passes between its two events, since gsa_set_profiling; every other entry: host
+	// wall time inside the export (a cs / segs call's CIGAR pass included), always on -- two clock reads per call -- and never reset
+	PassStat pass_stat[PASS_N];
 	// ---- per-block CIGARs (k_cigar.hip): block table in / out, per-record run-start and column counts, per-workgroup sums, their prefix sums, the run starts {column << 4 | class}, the ops;
 	// pinned: block table in, header {ops, columns, records without a job}, block table out, ops ----
 	DevBuf d_cblk, d_cout, d_ccnt, d_cwg, d_cpre, d_crun, d_cops, p_cblk, p_chdr, p_cout, p_cops;
-	double cig_ms_sum = 0; long long cig_calls = 0;      // host wall time inside gsa_block_cigars (always on: two clock reads per call)
 	// ---- per-block cs strings (k_cs.hip): the runs' first positions (written by the CIGAR walk, block_cigars(.., pos)), per-op byte counts, per-workgroup sums, the ops' offsets,
 	// block table out, the bytes; pinned: header {bytes, blocks too long, bases out of range}, block table out, the bytes ----
 	DevBuf d_crpos, d_cqpos, d_slen, d_swg, d_spre, d_sout, d_cs, p_shdr, p_sout, p_cs;
-	double cs_ms_sum = 0; long long cs_calls = 0;        // host wall time inside gsa_block_cs, its CIGAR pass included
-	// ---- lifted reference positions (k_lift.hip): the positions of gsa_lift_set, the block table sorted by start, per position {chosen table entry, n_cover}, per-workgroup
-	// sums + error counters, the hits; pinned: block table, header {hits, records without a job, positions outside their record}, the hits ----
+	// ---- lifted reference positions (k_lift.hip): the positions of gsa_lift_set, the span table sorted by start and per position {chosen table entry, n_cover} (both
+	// k_regions.hip's too: a call builds them and has consumed them before it returns), per-workgroup sums + error counters, the hits; pinned: span table, header {hits,
+	// records without a job, positions outside their record}, the hits ----
 	DevBuf d_lpos, d_lblk, d_lpick, d_lwg, d_lhit, p_lblk, p_lhdr, p_lhit;
 	i64 lift_n = 0;                                      // positions held (0: none; a clone starts without)
-	double lift_ms_sum = 0; long long lift_calls = 0;    // host wall time inside gsa_lift
 	// ---- per-window reference track (k_track.hip): the counted blocks' table, the merged intervals, the dense per-window counts {n_eq, n_x, n_del, n_ins} (all zero between
 	// calls: EMIT clears what it reads), per-workgroup sums + error counters, the windows; pinned: block table, intervals, header {windows, records without a job, columns
 	// outside their record}, the windows ----
 	DevBuf d_tblk, d_tiv, d_tbin, d_twg, d_tout, p_tblk, p_tiv, p_thdr, p_tout;
 	i32 track_w = 0; i64 track_nwin = 0;                 // window length (0: none; a clone starts without) and the windows of the whole reference at that length
 	size_t track_zeroed = 0; bool track_dirty = false;   // entries of d_tbin known to be zero; a call that failed between COUNT and EMIT left counts behind
-	double track_ms_sum = 0; long long track_calls = 0;  // host wall time inside gsa_ref_track
 	// ---- per-block chain segments (k_segs.hip): per-workgroup sums + error counter, segment starts in front of every run, the segments' boundaries {start position,
 	// first column, end column, query position}, the blocks' table, the triples; pinned: header {segments, triples that are no chain line}, block table, triples ----
 	DevBuf d_sgwg, d_sgpre, d_sgbnd, d_sgout, d_sgseg, p_sghdr, p_sgout, p_sgseg;
-	double seg_ms_sum = 0; long long seg_calls = 0;      // host wall time inside gsa_block_segs, its CIGAR pass included
 	// ---- the query projected onto the reference (k_proj.hip): the accumulator this context paints into (null: none; a clone starts without), the painted blocks' table,
 	// per-record prefix of the run records' trimmed columns (entry [W]: their sum), per-workgroup sums + counters, device staging of fetch (characters) and merge (words);
 	// pinned: block table, header {run columns, records without a job, columns outside their record or sequence, gap columns}, staging of fetch and merge ----
 	ProjAcc *proj = nullptr; u32 proj_flags = 0;
 	DevBuf d_pblk, d_ppre, d_pwg, d_pstage, p_pblk, p_phdr, p_pstage;
-	double proj_ms_sum = 0; long long proj_calls = 0;    // host wall time inside gsa_project
-	// ---- lifted reference intervals (k_regions.hip): the regions of gsa_regions_set (n begs, then n ends), the block table sorted by start with the blocks' first work
-	// items, the per-record prefix of the four class counts, per region {chosen table entry, n_cover}, per-workgroup sums + error counters, the hits; pinned: block table,
-	// header {hits, records without a job, spans outside their records}, the hits ----
-	DevBuf d_rgpos, d_rgblk, d_rgpre, d_rgpick, d_rgwg, d_rghit, p_rgblk, p_rghdr, p_rghit;
+	// ---- lifted reference intervals (k_regions.hip; table and picks: the lift pass's d_lblk / d_lpick / p_lblk): the regions of gsa_regions_set (n begs, then n ends),
+	// the per-record prefix of the four class counts, per-workgroup sums + error counters, the hits; pinned: header {hits, records without a job, spans outside their
+	// records}, the hits ----
+	DevBuf d_rgpos, d_rgpre, d_rgwg, d_rghit, p_rghdr, p_rghit;
 	i64 reg_n = 0;                                       // regions held (0: none; a clone starts without)
-	double reg_ms_sum = 0; long long reg_calls = 0;      // host wall time inside gsa_lift_regions
 	// what growing buffers cost this context (dev_ensure / pin_ensure: hipMalloc, hipHostMalloc, the frees and the quiesce in front of them) -- gsa_get_alloc_stats
 	double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 };
@@ -296,11 +297,11 @@ struct gsa_ctx {
 	X(e_id) X(e_rec) X(e_list) X(e_off1) X(e_off2) X(e_opsoff) X(e_nops) X(e_ops) X(e_rev) X(r_head) X(f_early) X(r_orig) X(r_tmp_orig) \
 	X(j_frag) X(j_opsoff) X(j_nops) X(d_ops) X(j_cells) X(d_alnoff) X(bl_alnlen) X(bl_score) X(d_bblk) X(d_dp_arena) \
 	X(d_vblk) X(d_vcnt) X(d_vwg) X(d_var) X(d_cblk) X(d_cout) X(d_ccnt) X(d_cwg) X(d_cpre) X(d_crun) X(d_cops) X(d_crpos) X(d_cqpos) X(d_slen) X(d_swg) X(d_spre) X(d_sout) X(d_cs) \
-	X(d_lpos) X(d_lblk) X(d_lpick) X(d_lwg) X(d_lhit) X(d_tblk) X(d_tiv) X(d_tbin) X(d_twg) X(d_tout) X(d_sgwg) X(d_sgpre) X(d_sgbnd) X(d_sgout) X(d_sgseg) X(d_pblk) X(d_ppre) X(d_pwg) X(d_pstage) X(d_rgpos) X(d_rgblk) X(d_rgpre) X(d_rgpick) X(d_rgwg) X(d_rghit) \
+	X(d_lpos) X(d_lblk) X(d_lpick) X(d_lwg) X(d_lhit) X(d_tblk) X(d_tiv) X(d_tbin) X(d_twg) X(d_tout) X(d_sgwg) X(d_sgpre) X(d_sgbnd) X(d_sgout) X(d_sgseg) X(d_pblk) X(d_ppre) X(d_pwg) X(d_pstage) X(d_rgpos) X(d_rgpre) X(d_rgwg) X(d_rghit) \
 	X(leaf[0]) X(leaf[1]) X(leaf[2]) X(leaf[3]) X(leaf[4]) X(leaf[5]) X(leaf[6]) X(leaf[7]) X(leaf[8])
 #define GSA_PINBUFS(X) \
 	X(p_frags) X(p_tail) X(p_leaf) X(p_blk) X(p_dp) X(p_sj) X(p_sj_early) X(p_jpatch) X(p_early) X(qs[0].p_bndtab) X(qs[1].p_bndtab) X(p_bblk) X(p_ba0) \
-	X(p_vblk) X(p_vhdr) X(p_var) X(p_cblk) X(p_chdr) X(p_cout) X(p_cops) X(p_shdr) X(p_sout) X(p_cs) X(p_lblk) X(p_lhdr) X(p_lhit) X(p_tblk) X(p_tiv) X(p_thdr) X(p_tout) X(p_sghdr) X(p_sgout) X(p_sgseg) X(p_pblk) X(p_phdr) X(p_pstage) X(p_rgblk) X(p_rghdr) X(p_rghit)
+	X(p_vblk) X(p_vhdr) X(p_var) X(p_cblk) X(p_chdr) X(p_cout) X(p_cops) X(p_shdr) X(p_sout) X(p_cs) X(p_lblk) X(p_lhdr) X(p_lhit) X(p_tblk) X(p_tiv) X(p_thdr) X(p_tout) X(p_sghdr) X(p_sgout) X(p_sgseg) X(p_pblk) X(p_phdr) X(p_pstage) X(p_rghdr) X(p_rghit)
 
 // A buffer is about to be freed: nothing of this context may still use it -- not only the main stream: the early striped DP launch runs on
 // stream_aux[0] beside stages 3-7 and shares direction / boundary / ticket buffers with the late launch, strings and record copies run on
@@ -397,6 +398,7 @@ void bundle_join_lists(gsa_ctx *c);            // gsa_blocks.cpp   ... joined ag
 #define GSA_BUNDLE_MAX_CONTIGS 4096
 int reset_run_state(gsa_ctx *c);      // gsa_query.hip  (back to stage 0: nothing of the previous run in flight or half-consumed; the query, its geometry and `bnd` stay)
 int set_query_bundle(gsa_ctx *c, const char *const *query, const int32_t *qlen, int32_t n, bool dev_q);   // gsa_query.hip  (gsa_align_bundle's gsa_set_query)
+// (the exports gsa_align_many_ex calls too; all of them: result_pass in gsa_api.hip)
 int lift_call(gsa_ctx *c, int32_t k, gsa_lifts *out);   // gsa_api.hip  (gsa_lift)
 int track_call(gsa_ctx *c, int32_t k, gsa_tracks *out);   // gsa_api.hip  (gsa_ref_track)
 int proj_call(gsa_ctx *c, int32_t k, gsa_proj_stat *out);   // gsa_api.hip  (gsa_project)

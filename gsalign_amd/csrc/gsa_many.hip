@@ -123,10 +123,12 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 	for (int k = 0; k < n_ctx; k++) if (!ctx[k]) return GSA_ERR_ARG;
 	const bool dev_q = (flags & GSA_MANY_DEVICE) != 0;
 	if (dev_q) for (int k = 1; k < n_ctx; k++) if (ctx[k]->device != ctx[0]->device) return gsa_fail(ctx[0], GSA_ERR_ARG, "GSA_MANY_DEVICE: the contexts must share one GPU (the contigs live in its memory)");
-	// (GSA_WANT_LIFT: a context without positions would fail its first contig with the others under way)
-	if (sk.want & GSA_WANT_LIFT) for (int k = 0; k < n_ctx; k++) if (ctx[k]->lift_n <= 0) return gsa_fail(ctx[k], GSA_ERR_STATE, "gsa_align_many_ex (GSA_WANT_LIFT): the context holds no positions (gsa_lift_set first)");
-	if (sk.want & GSA_WANT_TRACK) for (int k = 0; k < n_ctx; k++) if (ctx[k]->track_w <= 0) return gsa_fail(ctx[k], GSA_ERR_STATE, "gsa_align_many_ex (GSA_WANT_TRACK): the context holds no window (gsa_track_set first)");
-	if (sk.want & GSA_WANT_REGIONS) for (int k = 0; k < n_ctx; k++) if (ctx[k]->reg_n <= 0) return gsa_fail(ctx[k], GSA_ERR_STATE, "gsa_align_many_ex (GSA_WANT_REGIONS): the context holds no regions (gsa_regions_set first)");
+	// (what a pass reads must be set on every context: one without would fail its first contig with the others under way)
+	static const struct { uint32_t want; bool (*set)(const gsa_ctx *); const char *msg; } needs[3] = {
+		{ GSA_WANT_LIFT, [](const gsa_ctx *c) { return c->lift_n > 0; }, "gsa_align_many_ex (GSA_WANT_LIFT): the context holds no positions (gsa_lift_set first)" },
+		{ GSA_WANT_TRACK, [](const gsa_ctx *c) { return c->track_w > 0; }, "gsa_align_many_ex (GSA_WANT_TRACK): the context holds no window (gsa_track_set first)" },
+		{ GSA_WANT_REGIONS, [](const gsa_ctx *c) { return c->reg_n > 0; }, "gsa_align_many_ex (GSA_WANT_REGIONS): the context holds no regions (gsa_regions_set first)" } };
+	for (const auto &nd : needs) if (sk.want & nd.want) for (int k = 0; k < n_ctx; k++) if (!nd.set(ctx[k])) return gsa_fail(ctx[k], GSA_ERR_STATE, nd.msg);
 	// (GSA_WANT_PROJ: the bit exists for callers that have opened an accumulator.  Where NO context of ctx[] holds one it is refused like any bit the call does not know --
 	//  GSA_ERR_ARG, what 128 gave before the pass existed; where some hold one and others do not, the call is half set up: GSA_ERR_STATE.  Either way before any contig is aligned)
 	if (sk.want & GSA_WANT_PROJ) {
@@ -211,6 +213,18 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 	return err.load();
 }
 
+// one answer of a later pass behind the public gsa_extras: zeroed, then the pass's if it ran (GSA_ERR_STATE: it was not asked for)
+template <class T>
+static int extras_get(const gsa_extras *ex, const T *ExtrasFull::*which, T *out)
+{
+	if (!ex || !out) return GSA_ERR_ARG;
+	*out = T();
+	const T *p = ((const ExtrasFull *)ex)->*which;
+	if (!p) return GSA_ERR_STATE;
+	*out = *p;
+	return GSA_OK;
+}
+
 extern "C" {
 int gsa_align_many(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n, uint32_t flags, gsa_result_fn on_result, void *user)
 {
@@ -230,54 +244,11 @@ int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *que
 	return align_many_impl(ctx, n_ctx, query, qlen, n, flags, sk, user);
 }
 
-// the cs strings behind the gsa_extras a gsa_align_many_ex callback was handed (GSA_WANT_CS)
-int gsa_extras_cs(const gsa_extras *ex, gsa_cs *out)
-{
-	if (!ex || !out) return GSA_ERR_ARG;
-	out->n_blocks = 0; out->n_bytes = 0; out->blk = nullptr; out->cs = nullptr;
-	const gsa_cs *cs = ((const ExtrasFull *)ex)->cs;
-	if (!cs) return GSA_ERR_STATE;
-	*out = *cs;
-	return GSA_OK;
-}
-// the lifted positions behind it (GSA_WANT_LIFT)
-int gsa_extras_lift(const gsa_extras *ex, gsa_lifts *out)
-{
-	if (!ex || !out) return GSA_ERR_ARG;
-	out->n_hits = 0; out->hits = nullptr;
-	const gsa_lifts *l = ((const ExtrasFull *)ex)->lift;
-	if (!l) return GSA_ERR_STATE;
-	*out = *l;
-	return GSA_OK;
-}
-// the chain segments behind it (GSA_WANT_SEGS)
-int gsa_extras_segs(const gsa_extras *ex, gsa_segs *out)
-{
-	if (!ex || !out) return GSA_ERR_ARG;
-	out->n_blocks = 0; out->n_segs = 0; out->blk = nullptr; out->seg = nullptr;
-	const gsa_segs *s = ((const ExtrasFull *)ex)->segs;
-	if (!s) return GSA_ERR_STATE;
-	*out = *s;
-	return GSA_OK;
-}
-// the per-window track behind it (GSA_WANT_TRACK)
-int gsa_extras_track(const gsa_extras *ex, gsa_tracks *out)
-{
-	if (!ex || !out) return GSA_ERR_ARG;
-	out->n_win = 0; out->win = nullptr;
-	const gsa_tracks *t = ((const ExtrasFull *)ex)->track;
-	if (!t) return GSA_ERR_STATE;
-	*out = *t;
-	return GSA_OK;
-}
-// the lifted regions behind it (GSA_WANT_REGIONS)
-int gsa_extras_regions(const gsa_extras *ex, gsa_region_lifts *out)
-{
-	if (!ex || !out) return GSA_ERR_ARG;
-	out->n_hits = 0; out->hits = nullptr;
-	const gsa_region_lifts *r = ((const ExtrasFull *)ex)->regions;
-	if (!r) return GSA_ERR_STATE;
-	*out = *r;
-	return GSA_OK;
-}
+// the answers behind the gsa_extras a gsa_align_many_ex callback was handed: cs strings (GSA_WANT_CS), lifted positions (GSA_WANT_LIFT), chain segments (GSA_WANT_SEGS),
+// the per-window track (GSA_WANT_TRACK), lifted regions (GSA_WANT_REGIONS)
+int gsa_extras_cs(const gsa_extras *ex, gsa_cs *out) { return extras_get(ex, &ExtrasFull::cs, out); }
+int gsa_extras_lift(const gsa_extras *ex, gsa_lifts *out) { return extras_get(ex, &ExtrasFull::lift, out); }
+int gsa_extras_segs(const gsa_extras *ex, gsa_segs *out) { return extras_get(ex, &ExtrasFull::segs, out); }
+int gsa_extras_track(const gsa_extras *ex, gsa_tracks *out) { return extras_get(ex, &ExtrasFull::track, out); }
+int gsa_extras_regions(const gsa_extras *ex, gsa_region_lifts *out) { return extras_get(ex, &ExtrasFull::regions, out); }
 } // extern "C"

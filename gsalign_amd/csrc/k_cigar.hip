@@ -21,11 +21,7 @@
 // early) and the two sequences, never read from the string pools: the strings of the large DP jobs never exist in d_tail.  'D' puts '-' into
 // the reference row (CIGAR I), 'I' into the query row (CIGAR D) (ksw2_alignment.cpp:264-272); an equal-length gap that needed no DP is all
 // 'M'; a pure insertion / deletion record is one run whatever its length.
-#include <cstring>
-#include "gsa_fm.h"
 #include "gsa_walk.h"
-
-#define CIG_SERIAL 64      // gap records of at most this many columns are walked by one lane, longer ones by a wavefront in 64-column steps
 
 struct CigIn : GapIn {
 	i32 nb; i64 W; const CigBlk *blk;
@@ -52,7 +48,7 @@ __device__ __forceinline__ CigRec cig_load(const CigIn &a, i64 i)
 }
 
 // class of a column that holds a base in both rows
-__device__ __forceinline__ i32 cig_pair(uint8_t r, uint8_t q) { const int x = gsa_nt4(r); return (x < 4 && x == gsa_nt4(q)) ? (i32)GSA_CIGAR_EQ : (i32)GSA_CIGAR_X; }
+__device__ __forceinline__ i32 cig_pair(uint8_t r, uint8_t q) { return col_mismatch(r, q) ? (i32)GSA_CIGAR_X : (i32)GSA_CIGAR_EQ; }
 __device__ __forceinline__ i32 cig_class(const CigIn &a, int ch, i64 rp, i32 qp)
 {
 	return ch == 'D' ? (i32)GSA_CIGAR_INS : (ch == 'I' ? (i32)GSA_CIGAR_DEL : cig_pair(a.ref[rp], a.query[qp]));
@@ -111,14 +107,12 @@ __device__ i32 cig_lane(const CigIn &a, const CigRec &g, i32 prev, i64 *run, i64
 		const i32 cls = cig_class(a, ch, rp, qp);
 		cnt[cig_slot(cls)]++;
 		if (cls != prev) { if (EMIT) cig_put<POS>(a, run, slot + n, col + i, cls, rp, qp); n++; prev = cls; }
-		if (ch != 'D') rp++;
-		if (ch != 'I') qp++;
+		col_advance(ch, rp, qp);
 	}
 	return n;
 }
 
-// a long walk by a whole wavefront, 64 columns per step: a lane's reference / query position is the step's base plus the number of lower lanes whose
-// column consumes a base of that side, its slot the base plus the number of lower lanes that start a run
+// a long walk by a whole wavefront, 64 columns per step (wave_step): a lane's slot is the step's base plus the number of lower lanes that start a run
 template <bool EMIT, bool POS>
 __device__ i32 cig_wave(const CigIn &a, const CigRec &g, i32 prev, i64 *run, i64 slot, i64 col, i32 cnt[4])
 {
@@ -126,19 +120,16 @@ __device__ i32 cig_wave(const CigIn &a, const CigRec &g, i32 prev, i64 *run, i64
 	const unsigned long long below = (1ull << lane) - 1ull;
 	i64 rp0 = g.rpos; i32 qp0 = g.qpos, n = 0; i32 carry = prev;      // carry: class of the column in front of the step
 	for (i32 base = 0; base < g.L; base += 64) {
-		const i32 p = base + lane; const bool valid = p < g.L;
-		const int ch = valid ? (g.op ? (int)g.op[p] : (int)'M') : 0;
-		const bool c1 = ch == 'M' || ch == 'I', c2 = ch == 'M' || ch == 'D';
-		const unsigned long long m1 = __ballot(c1), m2 = __ballot(c2);
-		const i64 rp = rp0 + __popcll(m1 & below); const i32 qp = qp0 + __popcll(m2 & below);
+		const WaveCol w = wave_step(g.op, g.L, base, rp0, qp0);
+		const bool valid = w.ch != 0;
 		i32 cls = 0;
-		if (valid) cls = ch == 'M' ? cig_pair(a.ref[rp], a.query[qp]) : (ch == 'D' ? (i32)GSA_CIGAR_INS : (i32)GSA_CIGAR_DEL);
+		if (valid) cls = w.ch == 'M' ? cig_pair(a.ref[w.rp], a.query[w.qp]) : (w.ch == 'D' ? (i32)GSA_CIGAR_INS : (i32)GSA_CIGAR_DEL);
 		i32 pcls = __shfl_up(cls, 1); if (lane == 0) pcls = carry;
 		const bool st = valid && cls != pcls;
 		const unsigned long long ms = __ballot(st);
 		if (valid) cnt[cig_slot(cls)]++;
-		if (EMIT && st) cig_put<POS>(a, run, slot + n + __popcll(ms & below), col + p, cls, rp, qp);
-		rp0 += __popcll(m1); qp0 += __popcll(m2); n += __popcll(ms); carry = __shfl(cls, 63);
+		if (EMIT && st) cig_put<POS>(a, run, slot + n + __popcll(ms & below), col + w.p, cls, w.rp, w.qp);
+		n += __popcll(ms); carry = __shfl(cls, 63);
 	}
 	return n;
 }
@@ -184,7 +175,7 @@ __global__ void __launch_bounds__(256) k_cig_pass(CigIn a, i32 *ns, i32 *nc, i64
 		}
 	}
 	__syncthreads();
-	const bool wide = g.kind == CG_WALK && g.L > CIG_SERIAL;
+	const bool wide = g.kind == CG_WALK && g.L > WALK_SERIAL;
 	i32 cnt[4] = { 0, 0, 0, 0 };
 	i32 n = 0;
 	if (wide) { const int at = atomicAdd(&s_n, 1); s_list[at] = tid; s_prev[tid] = prev; s_slot[tid] = slot; s_col[tid] = col; }

@@ -10,21 +10,17 @@
 //           query bytes and hit neighbouring words: 256 contiguous bytes per wave instruction, ascending on the forward strand, descending on the reverse strand.  The
 //           grid is sized by the host-known sum of the blocks' spans (no read-back of the total); tiles beyond the device total leave.
 //           (A walk forward from the tile's first record was the first sketch; the bounded search costs the same six steps whether the tile holds two records or two hundred.)
-//   GAPS    a work item per record again, DP-gap records only: at most PROJ_SERIAL columns by their lane, longer ones by a wavefront in 64-column steps
+//   GAPS    a work item per record again, DP-gap records only: at most WALK_SERIAL columns by their lane, longer ones by a wavefront in 64-column steps
 //   TEXT    words -> characters, 16 per lane, one 16-byte store;  MERGE  host words into the array, the maximum stays
 // No workgroup waits for another, nothing spins; every atomic's index is checked against G; the query is read for covered columns only and the reference text not at all
 // (a column's character is the query's).  As in the other passes the columns of a DP gap come from the op string of its DP job (gsa_walk.h), never from the string pools.
-#include <algorithm>
-#include <cstring>
-#include "gsa_fm.h"
 #include "gsa_walk.h"
 
-#define PROJ_SERIAL 64        // gap records of at most this many columns are walked by one lane, longer ones by a wavefront in 64-column steps
 #define PROJ_TILE 2048        // columns per workgroup of k_proj_runs: eight per lane
 #define PROJ_CHUNK ((i64)1 << 22)      // positions per staging round of fetch and merge: 16 MB of words
 
-// one painted block: the text positions it covers [start, end) (end clamped to its chromosome copy), its records (absolute), its first work item, strand, key
-struct ProjBlk { i64 start, end, frag_off, wbase; i32 n_frag, rev; u32 key; i32 _pad; };
+// one painted block (gsa_walk.h's span table entry, unsorted) and the key its columns offer
+struct ProjBlk : SpanBlk { u32 key; i32 _pad; };
 struct ProjIn : GapIn {
 	const ProjBlk *blk; i32 nb;
 	i64 W, G;
@@ -48,7 +44,7 @@ struct ProjRec { ProjBlk b; gsa_frag f; i32 ftype; i64 i; };
 __device__ __forceinline__ ProjRec proj_rec(const ProjIn &a, i64 w)
 {
 	ProjRec x;
-	x.b = a.blk[blk_last_le(a.blk, a.nb, &ProjBlk::wbase, w)];
+	x.b = a.blk[blk_last_le(a.blk, a.nb, &SpanBlk::wbase, w)];
 	x.i = x.b.frag_off + (w - x.b.wbase);
 	x.f = a.frag[x.i]; x.ftype = a.ftype[x.i];
 	return x;
@@ -76,12 +72,6 @@ __global__ void __launch_bounds__(256) k_proj_prefix(ProjIn a, i64 *pre, i64 *wg
 	const i64 e = wg_excl_scan<i64>(v, s_w);
 	if (w < a.W) pre[w] = e;
 	if (threadIdx.x == 255) wg[blockIdx.x] = e + v;
-}
-__global__ void __launch_bounds__(256) k_proj_scan(i64 nwg, i64 *wg, i64 *total)
-{
-	__shared__ i64 s_w[4];
-	const i64 t = wg_scan_sums(wg, nwg, s_w);
-	if (threadIdx.x == 0) *total = t;
 }
 __global__ void __launch_bounds__(256) k_proj_add(i64 W, i64 *pre, const i64 *wg)
 {
@@ -123,7 +113,7 @@ __global__ void __launch_bounds__(256) k_proj_runs(ProjIn a, const i64 *pre, uns
 	}
 }
 
-// the columns of a gap of at most PROJ_SERIAL ops (op[0 .. L)), by one lane; returns the columns offered.  'D' puts '-' into the reference row (no reference base), 'I'
+// the columns of a gap of at most WALK_SERIAL ops (op[0 .. L)), by one lane; returns the columns offered.  'D' puts '-' into the reference row (no reference base), 'I'
 // into the query row (code 6), 'M' pairs a base of either side
 __device__ i32 proj_lane(const ProjIn &a, const ProjRec &x, const uint8_t *op, i32 L, unsigned long long *cnt)
 {
@@ -138,38 +128,30 @@ __device__ i32 proj_lane(const ProjIn &a, const ProjRec &x, const uint8_t *op, i
 				if (ch != 'I') { if (qp - x.f.qpos >= x.f.qlen || qp < 0 || qp >= a.qtot) { ok = false; code = 0u; } else code = proj_code(a.query[qp]); }
 				if (code) { proj_offer(a, x.b, rp, code, cnt); n++; }
 			}
-			rp++;
 		}
-		if (ch != 'I') qp++;
+		col_advance(ch, rp, qp);
 	}
 	if (rp != rend) ok = false;      // (the ops hold fewer reference bases than the record)
 	if (!ok) atomicAdd(cnt + PJ_OUT, 1ull);
 	return n;
 }
 
-// the same by a whole wavefront, 64 columns per step: a lane's reference / query position is the step's base plus the number of lower lanes whose column consumes a
-// base of that side; returns the lane's own offered columns
+// the same by a whole wavefront, 64 columns per step (wave_step); returns the lane's own offered columns
 __device__ i32 proj_wave(const ProjIn &a, const ProjRec &x, const uint8_t *op, i32 L, unsigned long long *cnt)
 {
 	const int lane = threadIdx.x & 63;
-	const unsigned long long below = (1ull << lane) - 1ull;
 	i64 rp0 = x.f.rpos; i32 qp0 = x.f.qpos, n = 0; bool ok = true;
 	const i64 rend = x.f.rpos + x.f.rlen;
 	for (i32 base = 0; base < L; base += 64) {
-		const i32 p = base + lane;
-		const int ch = p < L ? (int)op[p] : 0;
-		const bool c1 = ch == 'M' || ch == 'I', c2 = ch == 'M' || ch == 'D';
-		const unsigned long long m1 = __ballot(c1), m2 = __ballot(c2);
-		const i64 rp = rp0 + __popcll(m1 & below); const i32 qp = qp0 + __popcll(m2 & below);
-		if (c1) {
-			if (rp >= rend) ok = false;
-			else if (rp >= x.b.start && rp < x.b.end) {
+		const WaveCol w = wave_step(op, L, base, rp0, qp0);
+		if (w.c1) {
+			if (w.rp >= rend) ok = false;
+			else if (w.rp >= x.b.start && w.rp < x.b.end) {
 				u32 code = 6u;
-				if (ch == 'M') { if (qp - x.f.qpos >= x.f.qlen || qp < 0 || qp >= a.qtot) { ok = false; code = 0u; } else code = proj_code(a.query[qp]); }
-				if (code) { proj_offer(a, x.b, rp, code, cnt); n++; }
+				if (w.ch == 'M') { if (w.qp - x.f.qpos >= x.f.qlen || w.qp < 0 || w.qp >= a.qtot) { ok = false; code = 0u; } else code = proj_code(a.query[w.qp]); }
+				if (code) { proj_offer(a, x.b, w.rp, code, cnt); n++; }
 			}
 		}
-		rp0 += __popcll(m1); qp0 += __popcll(m2);
 	}
 	if (rp0 != rend) ok = false;
 	if (__ballot(!ok) && lane == 0) atomicAdd(cnt + PJ_OUT, 1ull);
@@ -190,7 +172,7 @@ __global__ void __launch_bounds__(256) k_proj_gaps(ProjIn a, unsigned long long 
 		if (x.ftype == FT_DP && x.f.qlen > 0 && x.f.rlen > 0) {
 			const uint8_t *op = nullptr; i32 L = 0;
 			if (!gap_ops(a, x.i, x.ftype, x.f, op, L) || !op) atomicAdd(cnt + PJ_NOJOB, 1ull);
-			else if (L > PROJ_SERIAL) s_list[atomicAdd(&s_n, 1)] = tid;
+			else if (L > WALK_SERIAL) s_list[atomicAdd(&s_n, 1)] = tid;
 			else n = proj_lane(a, x, op, L, cnt);
 		}
 	}
@@ -239,7 +221,7 @@ static int proj_paint(gsa_ctx *c, const ProjIn &a, i64 span, i64 *hdr)
 	GSA_CHECK(c, hipMemsetAsync(cnt, 0, PJ_NCNT * sizeof(unsigned long long), st));
 	hipLaunchKernelGGL(k_proj_prefix, dim3((unsigned)nwg), dim3(256), 0, st, a, pre, wg);
 	GSA_CHECK(c, hipGetLastError());
-	hipLaunchKernelGGL(k_proj_scan, dim3(1), dim3(256), 0, st, nwg, wg, pre + a.W);
+	hipLaunchKernelGGL(k_wg_total<>, dim3(1), dim3(256), 0, st, nwg, wg, pre + a.W);
 	GSA_CHECK(c, hipGetLastError());
 	hipLaunchKernelGGL(k_proj_add, dim3((unsigned)nwg), dim3(256), 0, st, a.W, pre, (const i64 *)wg);
 	GSA_CHECK(c, hipGetLastError());
@@ -264,29 +246,20 @@ int project_blocks(gsa_ctx *c, i32 k, gsa_proj_stat *out)
 	const size_t nb = rr.nb;
 	if (nb == 0 || c->n_frags <= 0) return GSA_OK;
 	if (!c->result_pinned) return gsa_fail(c, GSA_ERR_STATE, "gsa_project: the context holds no finished (stage 8) result");
-	if (!pin_ensure<ProjBlk>(c, c->p_pblk, nb) || !pin_ensure<i64>(c, c->p_phdr, 1 + PJ_NCNT)) return GSA_ERR_NOMEM;
-	// the block table: a few KB from the blocks and their first and last records, which the host holds (as lift_positions builds its own)
-	ProjBlk *hb = c->p_pblk.as<ProjBlk>(); i32 nt = 0; i64 W = 0, span = 0;
-	const gsa_rec *recs = c->p_frags.as<gsa_rec>() + rr.f0;
-	for (size_t j = 0; j < nb; j++) {
-		const gsa_block &bl = c->h_blocks[rr.b0 + j];
-		if (bl.n_frag <= 0 || (bl.bdup != 0 && (c->proj_flags & GSA_PROJ_NO_DUP))) continue;
-		gsa_frag first, last;
-		gsa_rec_expand(recs, bl.frag_off, &first); gsa_rec_expand(recs, bl.frag_off + bl.n_frag - 1, &last);
-		const i64 fwd = c->h_chr_fwd[(size_t)bl.chr], len = c->h_chr_len[(size_t)bl.chr];
-		const i64 lim = bl.bdir ? fwd + len : 2 * c->G - fwd;      // end of the block's chromosome copy (iExtension, tools.cpp:192-202)
-		ProjBlk &v = hb[nt];
-		v.start = first.rpos; v.end = std::min<i64>(last.rpos + last.rlen, lim);
-		if (v.end <= v.start) continue;
-		v.frag_off = bl.frag_off + rr.f0; v.wbase = W; v.n_frag = bl.n_frag; v.rev = bl.bdir ? 0 : 1; v._pad = 0;
+	if (!pin_ensure<i64>(c, c->p_phdr, 1 + PJ_NCNT)) return GSA_ERR_NOMEM;
+	// the painted blocks: duplicates too unless the accumulator was opened without them
+	i32 nt = 0; i64 W = 0, span = 0;
+	auto keep = [&](const gsa_block &bl) { return bl.bdup == 0 || !(c->proj_flags & GSA_PROJ_NO_DUP); };
+	auto extra = [&](const gsa_block &bl, ProjBlk &v, const gsa_frag &, const gsa_frag &) {
 		v.key = (bl.bdup == 0 ? 0x80000000u : 0u) | ((u32)std::min<i64>(std::max<i64>(bl.score, 0), (1 << 28) - 1) << 3);
-		W += bl.n_frag; span += v.end - v.start; nt++;
-	}
+		span += v.end - v.start;
+		return (int)GSA_OK;
+	};
+	if (const int rc = span_build<ProjBlk>(c, rr, "gsa_project", c->p_pblk, 0, keep, extra, nt, W)) return rc;
 	if (nt == 0) return GSA_OK;
-	if (W >= (1ll << 31) - 256) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_project: too many records");
 	const i64 nwg = (W + 255) / 256;
 	ENS(ProjBlk, d_pblk, (size_t)nt); ENS(i64, d_ppre, (size_t)W + 1); ENS(i64, d_pwg, (size_t)nwg + PJ_NCNT);      // sums | counters
-	GSA_CHECK(c, hipMemcpyAsync(c->d_pblk.p, hb, (size_t)nt * sizeof(ProjBlk), hipMemcpyHostToDevice, c->stream));
+	GSA_CHECK(c, hipMemcpyAsync(c->d_pblk.p, c->p_pblk.p, (size_t)nt * sizeof(ProjBlk), hipMemcpyHostToDevice, c->stream));
 	ProjIn a;
 	gap_in_fill(c, a);
 	a.blk = c->d_pblk.as<ProjBlk>(); a.nb = nt; a.W = W; a.G = c->G; a.acc = pa->words;

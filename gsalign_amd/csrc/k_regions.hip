@@ -2,11 +2,11 @@
 // the device, over what stage 8 left there.
 //
 // A region [beg, end) of the forward reference is the text interval [beg, end) for forward-strand blocks and [2G - end, 2G - beg) for reverse-strand blocks.  The blocks
-// of both strands stand in k_lift.hip's table (sorted by first text position, running maximum of the clamped ends beside it), which here also carries every block's
-// first work item, so the same table serves the per-record passes.  The two end columns of a region are two walks; everything between them is a difference of a
+// of both strands stand in gsa_walk.h's span table, the one k_lift.hip reads (sorted by first text position, running maximum of the clamped ends beside it, every
+// block's first work item), so the same table serves the cover search and the per-record passes.  The two end columns of a region are two walks; everything between them is a difference of a
 // per-record prefix, so no column of the records in between is looked at.
 //   CLASS   one work item per record of the table's blocks: the record's four counts {eq, x, del, ins}, untrimmed, for the whole record.  A seed, a pure deletion and
-//           a pure insertion are arithmetic; a gap of at most REG_SERIAL columns is walked by its lane, a longer one goes through s_list / s_n to a wavefront that takes
+//           a pure insertion are arithmetic; a gap of at most WALK_SERIAL columns is walked by its lane, a longer one goes through s_list / s_n to a wavefront that takes
 //           64 columns per step with ballot / popcount.  The same launch leaves the exclusive prefix inside the workgroup and the workgroups' sums
 //   SCAN    one workgroup turns the four arrays of sums into the workgroups' first values;  ADD makes the prefix global.  (uint32_t, modulo 2^32 from end to end: only
 //           differences inside ONE block are ever taken, and those are below 2^31.)  CLASS, SCAN and ADD depend on the result only, not on the regions
@@ -18,19 +18,10 @@
 //           that record is walked once, from the first column of the span to the last.  The hit goes to its slot, so hits are dense and ascending
 // Neighbouring lanes of COVER and EMIT handle neighbouring regions: sorted input gives near-uniform search addresses; nothing depends on the order.  No workgroup waits
 // for another, nothing spins.  As in the other passes the columns of a DP gap come from the op string of its DP job (gsa_walk.h), never from the string pools.
-#include <algorithm>
-#include <cstring>
-#include "gsa_fm.h"
 #include "gsa_walk.h"
 
-#define REG_SERIAL 64      // gap records of at most this many columns are walked by one lane, longer ones by a wavefront in 64-column steps
-
-// one block with records, in the order of `start`: the text positions it covers [start, end) (end clamped to its chromosome copy), the greatest end of the entries up to
-// this one, its records (absolute), its first work item (ascending with the table: it is assigned after the sort), and what the choice and the hit need
-struct RegBlk { i64 start, end, maxend, frag_off, wbase; i32 n_frag, score, bdup, block, rev, _pad; };
-struct RegPick { i32 ent; uint16_t n_cover, _pad; };       // the chosen table entry (-1: no block overlaps the region)
 struct RegIn : GapIn {
-	const RegBlk *blk; i32 nb;
+	const SpanBlk *blk; i32 nb;
 	i64 W;                                                     // records of the table's blocks: the work items of CLASS, the entries of pre
 	const uint4 *pre;                                          // per record: {eq, x, del, ins} of the records in front of it (EMIT)
 	const i64 *beg, *end; i64 n, G;
@@ -43,9 +34,6 @@ enum { RG_NOJOB = 0, RG_OUT = 1 };
 // counts of a stretch of columns and the query position in front of its first column
 struct RegPart { u32 eq = 0, x = 0, del = 0, ins = 0; i32 q = 0; };
 __device__ __forceinline__ void reg_sum(RegPart &t, const RegPart &r) { t.eq += r.eq; t.x += r.x; t.del += r.del; t.ins += r.ins; }
-
-// a column that holds a base in both rows: true 'X', false '=' (cig_pair's rule)
-__device__ __forceinline__ bool reg_mism(uint8_t r, uint8_t q) { const int x = gsa_nt4(r); return !(x < 4 && x == gsa_nt4(q)); }
 
 // The columns of a gap (op[0 .. L), null: 'M' throughout) from the column that holds reference base ta (clip_lo; else from the first column) through the column that
 // holds tb (clip_hi; else through the last), by one lane.  'D' puts '-' into the reference row (CIGAR I), 'I' into the query row (CIGAR D).  false: the ops do not
@@ -61,30 +49,24 @@ __device__ bool reg_lane(const RegIn &a, const gsa_frag &f, const uint8_t *op, i
 		if (in) {
 			if (ch == 'D') r.ins++;
 			else if (ch == 'I') r.del++;
-			else if (reg_mism(a.ref[rp], a.query[qp])) r.x++;
+			else if (col_mismatch(a.ref[rp], a.query[qp])) r.x++;
 			else r.eq++;
 			if (clip_hi && ch != 'D' && rp == tb) done = true;
 		}
-		if (ch != 'D') rp++;
-		if (ch != 'I') qp++;
+		col_advance(ch, rp, qp);
 	}
 	return in && (done || (!clip_hi && rp - f.rpos == f.rlen && qp - f.qpos == f.qlen));
 }
 
-// the same by a whole wavefront, 64 columns per step: a lane's reference / query position is the step's base plus the number of lower lanes whose column consumes a
-// base of that side; the lanes between the span's first and last column count, every lane ends with the same r
+// the same by a whole wavefront, 64 columns per step (wave_step): the lanes between the span's first and last column count, every lane ends with the same r
 __device__ bool reg_wave(const RegIn &a, const gsa_frag &f, const uint8_t *op, i32 L, bool clip_lo, i64 ta, bool clip_hi, i64 tb, RegPart &r)
 {
 	const int lane = threadIdx.x & 63;
-	const unsigned long long below = (1ull << lane) - 1ull;
 	i64 rp0 = f.rpos; i32 qp0 = f.qpos; bool in = !clip_lo, done = false;
 	r.q = f.qpos;
 	for (i32 base = 0; base < L && !done; base += 64) {
-		const i32 p = base + lane;
-		const int ch = p < L ? (op ? (int)op[p] : (int)'M') : 0;
-		const bool c1 = ch == 'M' || ch == 'I', c2 = ch == 'M' || ch == 'D';
-		const unsigned long long m1 = __ballot(c1), m2 = __ballot(c2);
-		const i64 rp = rp0 + __popcll(m1 & below); const i32 qp = qp0 + __popcll(m2 & below);
+		const WaveCol w = wave_step(op, L, base, rp0, qp0);
+		const int ch = w.ch; const bool c1 = w.c1, c2 = w.c2; const i64 rp = w.rp; const i32 qp = w.qp;
 		const bool out = (c1 && (rp - f.rpos >= f.rlen || rp >= 2 * a.G)) || (c2 && (qp - f.qpos >= f.qlen || qp < 0 || qp >= a.qtot));
 		if (__ballot(out)) return false;
 		unsigned long long span = ~0ull;                   // the step's lanes inside the span
@@ -98,10 +80,9 @@ __device__ bool reg_wave(const RegIn &a, const gsa_frag &f, const uint8_t *op, i
 			if (me) { const int e = __ffsll((long long)me) - 1; done = true; if (e < 63) span &= (1ull << (e + 1)) - 1ull; }
 		}
 		const bool mine = ch != 0 && ((span >> lane) & 1ull);
-		const bool mm = mine && ch == 'M' && reg_mism(a.ref[rp], a.query[qp]);
+		const bool mm = mine && ch == 'M' && col_mismatch(a.ref[rp], a.query[qp]);
 		r.eq += (u32)__popcll(__ballot(mine && ch == 'M' && !mm)); r.x += (u32)__popcll(__ballot(mm));
 		r.del += (u32)__popcll(__ballot(mine && ch == 'I')); r.ins += (u32)__popcll(__ballot(mine && ch == 'D'));
-		rp0 += __popcll(m1); qp0 += __popcll(m2);
 	}
 	return in && (done || (!clip_hi && rp0 - f.rpos == f.rlen && qp0 - f.qpos == f.qlen));
 }
@@ -126,7 +107,7 @@ struct RegRec { i64 i; gsa_frag f; i32 ftype; };
 __device__ __forceinline__ RegRec reg_rec(const RegIn &a, i64 w)
 {
 	RegRec x;
-	const RegBlk b = a.blk[blk_last_le(a.blk, a.nb, &RegBlk::wbase, w)];
+	const SpanBlk b = a.blk[blk_last_le(a.blk, a.nb, &SpanBlk::wbase, w)];
 	x.i = b.frag_off + (w - b.wbase);
 	x.f = a.frag[x.i]; x.ftype = a.ftype[x.i];
 	return x;
@@ -149,7 +130,7 @@ __global__ void __launch_bounds__(256) k_reg_class(RegIn a, uint4 *pre, i64 *wg,
 		RegPart r; const uint8_t *op = nullptr; i32 L = 0;
 		int kind = reg_piece(a, x.i, x.f, x.ftype, false, 0, false, 0, r, op, L);
 		if (kind == RG_WALK) {
-			if (L > REG_SERIAL) { s_list[atomicAdd(&s_n, 1)] = tid; queued = true; kind = RG_QUEUED; }
+			if (L > WALK_SERIAL) { s_list[atomicAdd(&s_n, 1)] = tid; queued = true; kind = RG_QUEUED; }
 			else if (!reg_lane(a, x.f, op, L, false, 0, false, 0, r)) kind = RG_BADSPAN;
 		}
 		if (kind == RG_BADJOB) atomicAdd(bad + RG_NOJOB, 1ull);
@@ -194,73 +175,28 @@ __global__ void __launch_bounds__(256) k_reg_class_add(i64 W, uint4 *pre, const 
 	pre[w] = p;
 }
 
-// the choice: not a duplicate, then the greater overlap, then the greater score, then the smaller block index
-__device__ __forceinline__ bool reg_better(const RegBlk &x, i64 ox, const RegBlk &y, i64 oy)
-{
-	if ((x.bdup != 0) != (y.bdup != 0)) return x.bdup == 0;
-	if (ox != oy) return ox > oy;
-	if (x.score != y.score) return x.score > y.score;
-	return x.block < y.block;
-}
-
-// the blocks that overlap the text interval [lo, hi): counted into n, the best of them (and of `best`, whose overlap is `bo`) into best
-__device__ __forceinline__ void reg_cover(const RegIn &a, i64 lo, i64 hi, i32 &best, i64 &bo, u32 &n)
-{
-	if (a.blk[0].start >= hi) return;
-	for (i32 j = blk_last_le(a.blk, a.nb, &RegBlk::start, hi - 1); j >= 0 && a.blk[j].maxend > lo; j--) {
-		const RegBlk b = a.blk[j];
-		if (b.end <= lo) continue;
-		const i64 o = (b.end < hi ? b.end : hi) - (b.start > lo ? b.start : lo);
-		n++;
-		if (best < 0 || reg_better(b, o, a.blk[best], bo)) { best = j; bo = o; }
-	}
-}
-
-__global__ void __launch_bounds__(256) k_reg_cover(RegIn a, RegPick *pick, i64 *wg)
+// the choice: not a duplicate, then the greater overlap, then the greater score, then the smaller block index (span_better)
+__global__ void __launch_bounds__(256) k_reg_cover(RegIn a, SpanPick *pick, i64 *wg)
 {
 	__shared__ i32 s_w[4];
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	const i64 w = (i64)blockIdx.x * 256 + tid;
-	i32 best = -1; i64 bo = 0; u32 n = 0;
-	if (w < a.n) {
-		const i64 beg = a.beg[w], end = a.end[w];
-		reg_cover(a, beg, end, best, bo, n);
-		reg_cover(a, 2 * a.G - end, 2 * a.G - beg, best, bo, n);
-		RegPick k; k.ent = best; k.n_cover = (uint16_t)(n > 65535u ? 65535u : n); k._pad = 0;
-		pick[w] = k;
-	}
-	i32 tot = best >= 0 ? 1 : 0;
-	for (int d = 32; d; d >>= 1) tot += __shfl_xor(tot, d);
-	if (lane == 0) s_w[wv] = tot;
-	__syncthreads();
-	if (tid == 0) wg[blockIdx.x] = (i64)s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-__global__ void __launch_bounds__(256) k_reg_scan(i64 nwg, i64 *wg, i64 *hdr)
-{
-	__shared__ i64 s_w[4];
-	const i64 total = wg_scan_sums(wg, nwg, s_w);
-	if (threadIdx.x == 0) hdr[0] = total;
+	const i64 w = (i64)blockIdx.x * 256 + threadIdx.x;
+	SpanPick k; k.ent = -1;
+	if (w < a.n) pick[w] = k = span_pick(a.blk, a.nb, a.G, a.beg[w], a.end[w]);
+	wg_count(k.ent >= 0, s_w, wg);
 }
 
 // what EMIT knows of a region before it looks at a column: the span [t_lo, t_hi), the records iA / iB that hold t_lo / t_hi - 1, the hit without its counts
-struct RegAt { RegBlk b; i64 t_lo = 0, t_hi = 0, iA = 0, iB = 0; gsa_region_hit h; };
+struct RegAt { SpanBlk b; i64 t_lo = 0, t_hi = 0, iA = 0, iB = 0; gsa_region_hit h; };
 
-__device__ __forceinline__ i64 reg_rec_of(const RegIn &a, i64 lo, i64 hi, i64 t)      // the last of records [lo, hi) with rpos <= t (record lo starts at or before t)
-{
-	while (hi - lo > 1) { const i64 m = (lo + hi) >> 1; if (a.frag[m].rpos <= t) lo = m; else hi = m; }
-	return lo;
-}
-
-__device__ __forceinline__ RegAt reg_at(const RegIn &a, i64 w, const RegPick &pk)
+__device__ __forceinline__ RegAt reg_at(const RegIn &a, i64 w, const SpanPick &pk)
 {
 	RegAt x;
 	x.b = a.blk[pk.ent];
 	const i64 beg = a.beg[w], end = a.end[w];
 	const i64 lo = x.b.rev ? 2 * a.G - end : beg, hi = x.b.rev ? 2 * a.G - beg : end;
 	x.t_lo = lo > x.b.start ? lo : x.b.start; x.t_hi = hi < x.b.end ? hi : x.b.end;
-	x.iA = reg_rec_of(a, x.b.frag_off, x.b.frag_off + x.b.n_frag, x.t_lo);
-	x.iB = reg_rec_of(a, x.iA, x.b.frag_off + x.b.n_frag, x.t_hi - 1);
+	x.iA = span_rec_of(a.frag, x.b.frag_off, x.b.frag_off + x.b.n_frag, x.t_lo);
+	x.iB = span_rec_of(a.frag, x.iA, x.b.frag_off + x.b.n_frag, x.t_hi - 1);
 	memset(&x.h, 0, sizeof(x.h));
 	x.h.idx = (int32_t)w; x.h.block = x.b.block; x.h.rev = (uint8_t)x.b.rev; x.h.n_cover = pk.n_cover;
 	x.h.off_lo = (int32_t)(x.b.rev ? hi - x.t_hi : x.t_lo - lo); x.h.off_hi = (int32_t)(x.b.rev ? hi - x.t_lo : x.t_hi - lo);
@@ -276,7 +212,7 @@ __device__ __forceinline__ int reg_end_piece(const RegIn &a, const RegAt &x, int
 	return reg_piece(a, i, f, a.ftype[i], clip_lo, x.t_lo, clip_hi, x.t_hi - 1, r, op, L);
 }
 
-__global__ void __launch_bounds__(256) k_reg_emit(RegIn a, const RegPick *pick, const i64 *wg, unsigned long long *bad, gsa_region_hit *out)
+__global__ void __launch_bounds__(256) k_reg_emit(RegIn a, const SpanPick *pick, const i64 *wg, unsigned long long *bad, gsa_region_hit *out)
 {
 	__shared__ i32 s_list[512], s_w[4], s_q[256];
 	__shared__ u32 s_v[256][4];
@@ -285,7 +221,7 @@ __global__ void __launch_bounds__(256) k_reg_emit(RegIn a, const RegPick *pick, 
 	const i64 w = (i64)blockIdx.x * 256 + tid;
 	if (tid == 0) s_n = 0;
 	s_v[tid][0] = s_v[tid][1] = s_v[tid][2] = s_v[tid][3] = 0u; s_q[tid] = 0;
-	RegPick pk; pk.ent = -1; pk.n_cover = 0; pk._pad = 0;
+	SpanPick pk; pk.ent = -1; pk.n_cover = 0; pk._pad = 0;
 	if (w < a.n) pk = pick[w];
 	const bool hit = pk.ent >= 0 && pk.ent < a.nb;
 	const i64 slot = wg[blockIdx.x] + wg_excl_scan<i32>(hit ? 1 : 0, s_w);      // (its barrier also publishes s_n = 0 and the cleared rows)
@@ -298,7 +234,7 @@ __global__ void __launch_bounds__(256) k_reg_emit(RegIn a, const RegPick *pick, 
 			gsa_frag f; bool cl, ch; RegPart r; const uint8_t *op = nullptr; i32 L = 0;
 			int kind = reg_end_piece(a, x, which, f, cl, ch, r, op, L);
 			if (kind == RG_WALK) {
-				if (L > REG_SERIAL) { s_list[atomicAdd(&s_n, 1)] = 2 * tid + which; if (which) q1 = true; else q0 = true; kind = RG_QUEUED; }
+				if (L > WALK_SERIAL) { s_list[atomicAdd(&s_n, 1)] = 2 * tid + which; if (which) q1 = true; else q0 = true; kind = RG_QUEUED; }
 				else if (!reg_lane(a, f, op, L, cl, x.t_lo, ch, x.t_hi - 1, r)) kind = RG_BADSPAN;
 			}
 			if (kind == RG_BADJOB) { atomicAdd(bad + RG_NOJOB, 1ull); fail = true; }
@@ -351,37 +287,21 @@ int lift_regions(gsa_ctx *c, i32 k, gsa_region_lifts *out)
 	if (nb == 0 || c->n_frags <= 0 || n <= 0) return GSA_OK;
 	if (!c->result_pinned) return gsa_fail(c, GSA_ERR_STATE, "gsa_lift_regions: the context holds no finished (stage 8) result");
 	hipStream_t st = c->stream;
-	if (!pin_ensure<RegBlk>(c, c->p_rgblk, nb) || !pin_ensure<i64>(c, c->p_rghdr, 4)) return GSA_ERR_NOMEM;
-	// the block table: a few KB from the blocks and their first and last records, which the host holds (as lift_positions builds its own)
-	RegBlk *hb = c->p_rgblk.as<RegBlk>(); i32 nt = 0;
-	const gsa_rec *recs = c->p_frags.as<gsa_rec>() + rr.f0;
-	for (size_t j = 0; j < nb; j++) {
-		const gsa_block &bl = c->h_blocks[rr.b0 + j];
-		if (bl.n_frag <= 0) continue;
-		gsa_frag first, last;
-		gsa_rec_expand(recs, bl.frag_off, &first); gsa_rec_expand(recs, bl.frag_off + bl.n_frag - 1, &last);
-		const i64 fwd = c->h_chr_fwd[(size_t)bl.chr], len = c->h_chr_len[(size_t)bl.chr];
-		const i64 lim = bl.bdir ? fwd + len : 2 * c->G - fwd;      // end of the block's chromosome copy (iExtension, tools.cpp:192-202)
-		RegBlk &v = hb[nt];
-		v.start = first.rpos; v.end = std::min<i64>(last.rpos + last.rlen, lim); v.maxend = 0; v.wbase = 0;
-		v.frag_off = bl.frag_off + rr.f0; v.n_frag = bl.n_frag; v.score = bl.score; v.bdup = bl.bdup; v.block = (i32)j; v.rev = bl.bdir ? 0 : 1; v._pad = 0;
-		if (v.end > v.start) nt++;
-	}
+	if (!pin_ensure<i64>(c, c->p_rghdr, 4)) return GSA_ERR_NOMEM;
+	// lift_positions' table, in its buffers: each call builds it and has consumed it before it returns
+	i32 nt = 0; i64 W = 0;
+	if (const int rc = span_build<SpanBlk>(c, rr, "gsa_lift_regions", c->p_lblk, SPAN_SORT, span_keep_all, span_no_extra, nt, W)) return rc;
 	if (nt == 0) return GSA_OK;
-	std::sort(hb, hb + nt, [](const RegBlk &x, const RegBlk &y) { return x.start != y.start ? x.start < y.start : x.block < y.block; });
-	i64 W = 0;
-	for (i32 j = 0; j < nt; j++) { hb[j].maxend = j ? std::max(hb[j - 1].maxend, hb[j].end) : hb[j].end; hb[j].wbase = W; W += hb[j].n_frag; }
-	if (W >= (1ll << 31) - 256) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_lift_regions: too many records");
 	const i64 nwg = (n + 255) / 256, nwg_c = (W + 255) / 256;
-	ENS(RegBlk, d_rgblk, (size_t)nt); ENS(RegPick, d_rgpick, (size_t)n); ENS(uint4, d_rgpre, (size_t)W);
+	ENS(SpanBlk, d_lblk, (size_t)nt); ENS(SpanPick, d_lpick, (size_t)n); ENS(uint4, d_rgpre, (size_t)W);
 	ENS(i64, d_rgwg, (size_t)nwg + 2 + 4 * (size_t)nwg_c);      // the regions' sums | {records without a job, spans outside their records} | the records' four arrays of sums
 	i64 *wg = c->d_rgwg.as<i64>(); unsigned long long *bad = (unsigned long long *)(wg + nwg); i64 *wg_c = wg + nwg + 2;
 	i64 *hdr = c->p_rghdr.as<i64>();
-	GSA_CHECK(c, hipMemcpyAsync(c->d_rgblk.p, hb, (size_t)nt * sizeof(RegBlk), hipMemcpyHostToDevice, st));
+	GSA_CHECK(c, hipMemcpyAsync(c->d_lblk.p, c->p_lblk.p, (size_t)nt * sizeof(SpanBlk), hipMemcpyHostToDevice, st));
 	GSA_CHECK(c, hipMemsetAsync(bad, 0, 2 * sizeof(unsigned long long), st));
 	RegIn a;
 	gap_in_fill(c, a);
-	a.blk = c->d_rgblk.as<RegBlk>(); a.nb = nt; a.W = W; a.pre = c->d_rgpre.as<uint4>();
+	a.blk = c->d_lblk.as<SpanBlk>(); a.nb = nt; a.W = W; a.pre = c->d_rgpre.as<uint4>();
 	a.beg = c->d_rgpos.as<i64>(); a.end = a.beg + n; a.n = n; a.G = c->G;
 	a.qoff = rr.qoff; a.qtot = c->bnd.n ? c->b_off[(size_t)c->bnd.n] : c->qlen; a.n_out = 0;
 	// CLASS + PREFIX: of the result alone
@@ -391,9 +311,9 @@ int lift_regions(gsa_ctx *c, i32 k, gsa_region_lifts *out)
 	GSA_CHECK(c, hipGetLastError());
 	hipLaunchKernelGGL(k_reg_class_add, dim3((unsigned)nwg_c), dim3(256), 0, st, W, c->d_rgpre.as<uint4>(), (const i64 *)wg_c, nwg_c);
 	GSA_CHECK(c, hipGetLastError());
-	hipLaunchKernelGGL(k_reg_cover, dim3((unsigned)nwg), dim3(256), 0, st, a, c->d_rgpick.as<RegPick>(), wg);
+	hipLaunchKernelGGL(k_reg_cover, dim3((unsigned)nwg), dim3(256), 0, st, a, c->d_lpick.as<SpanPick>(), wg);
 	GSA_CHECK(c, hipGetLastError());
-	hipLaunchKernelGGL(k_reg_scan, dim3(1), dim3(256), 0, st, nwg, wg, hdr);
+	hipLaunchKernelGGL(k_wg_total<>, dim3(1), dim3(256), 0, st, nwg, wg, hdr);
 	GSA_CHECK(c, hipGetLastError());
 	GSA_CHECK(c, hipStreamSynchronize(st));
 	const i64 nh = hdr[0];
@@ -402,7 +322,7 @@ int lift_regions(gsa_ctx *c, i32 k, gsa_region_lifts *out)
 		// the output is sized from the scan's total; it goes home in one copy
 		ENS(gsa_region_hit, d_rghit, (size_t)nh); if (!pin_ensure<gsa_region_hit>(c, c->p_rghit, (size_t)nh)) return GSA_ERR_NOMEM;
 		a.n_out = nh;
-		hipLaunchKernelGGL(k_reg_emit, dim3((unsigned)nwg), dim3(256), 0, st, a, (const RegPick *)c->d_rgpick.as<RegPick>(), (const i64 *)wg, bad, c->d_rghit.as<gsa_region_hit>());
+		hipLaunchKernelGGL(k_reg_emit, dim3((unsigned)nwg), dim3(256), 0, st, a, (const SpanPick *)c->d_lpick.as<SpanPick>(), (const i64 *)wg, bad, c->d_rghit.as<gsa_region_hit>());
 		GSA_CHECK(c, hipGetLastError());
 		GSA_CHECK(c, hipMemcpyAsync(c->p_rghit.p, c->d_rghit.p, (size_t)nh * sizeof(gsa_region_hit), hipMemcpyDeviceToHost, st));
 	}

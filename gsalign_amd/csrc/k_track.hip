@@ -17,17 +17,13 @@
 //           slot, so the windows are dense and ascend by (chr, start)
 // No workgroup waits for another, nothing spins.  As in the other passes the columns of a DP gap come from the op string of its DP job (gsa_walk.h), never from the
 // string pools.
-#include <algorithm>
-#include <cstring>
 #include <vector>
-#include "gsa_fm.h"
 #include "gsa_walk.h"
 
-#define TRK_SERIAL 64      // gap records of at most this many columns (that touch at most two windows) are walked by one lane
-
-// one counted block with records: its records (absolute) and first work item, the text positions it covers [start, end) (end clamped to its chromosome copy), and the
-// way from a text position t to a window: local = rev ? org - t : t - org inside the block's sequence of clen bases, window win0 + local / W.  Entry [nb]: wbase = items
-struct TrkBlk { i64 frag_off, wbase, start, end, org; i32 n_frag, rev, win0, clen; };
+// one counted block with records (gsa_walk.h's span table entry, unsorted) and the way from a text position t to a window: local = rev ? org - t : t - org inside the
+// block's sequence of clen bases, window win0 + local / W.  Entry [nb]: wbase = items.  Padded to 128 bytes: with a power-of-two stride the searches index by a shift,
+// which keeps k_trk_count at the 64 registers it had with its own 56-byte entry (80 bytes unpadded: 66, a wave per SIMD less; the table is a few KB either way)
+struct TrkBlk : SpanBlk { i64 org; i32 win0, clen; i64 _pad[6]; };
 // one merged interval [s, e) of covered forward positions inside sequence chr (clen bases, first window win0), sorted by (chr, s) and disjoint; wbase: its first work
 // item (one per window it touches).  Entry [niv]: wbase = items
 struct TrkIv { i64 wbase; i32 chr, s, e, clen, win0, _pad; };
@@ -64,9 +60,6 @@ __device__ __forceinline__ i32 trk_win(const TrkIn &a, const TrkBlk &b, i64 t)
 	const i64 w = (i64)b.win0 + (i64)((u32)l / (u32)a.W);
 	return w < a.nbin ? (i32)w : -1;
 }
-
-// field of a column that holds a base in both rows: 0 '=' / 1 'X' (cig_pair's rule)
-__device__ __forceinline__ int trk_pair(uint8_t r, uint8_t q) { const int x = gsa_nt4(r); return (x < 4 && x == gsa_nt4(q)) ? 0 : 1; }
 
 // n into field f of v[4] (by selects: a run-time index would put the array into scratch)
 __device__ __forceinline__ void trk_add(u32 v[4], int f, u32 n)
@@ -115,7 +108,7 @@ __device__ __forceinline__ TrkAt trk_at(const TrkIn &a, i64 w)
 	return x;
 }
 
-// one column of a walked gap: the field it counts in ('M': 0 until the caller has compared the two bases -- they are read for counted columns only) and the text
+// one column of a walked gap: the field it counts in ('M': 0 '=' until the caller has compared the two bases -- they are read for counted columns only) and the text
 // position it is charged to; false: no count (trimmed)
 __device__ __forceinline__ bool trk_col(const TrkBlk &b, int ch, i64 rp, int &f, i64 &t)
 {
@@ -124,7 +117,7 @@ __device__ __forceinline__ bool trk_col(const TrkBlk &b, int ch, i64 rp, int &f,
 	return t >= b.start && t < b.end;
 }
 
-// a gap of at most TRK_SERIAL columns that touches the windows wa / wb only, by one lane; false: a column outside its record
+// a gap of at most WALK_SERIAL columns that touches the windows wa / wb only, by one lane; false: a column outside its record
 __device__ bool trk_lane(const TrkIn &a, const TrkAt &x, u32 vA[4], u32 vB[4])
 {
 	const TrkRec &g = x.g;
@@ -133,34 +126,25 @@ __device__ bool trk_lane(const TrkIn &a, const TrkAt &x, u32 vA[4], u32 vB[4])
 		const int ch = g.op ? (int)g.op[i] : (int)'M';
 		if ((ch != 'D' && rp - g.rpos >= g.rlen) || (ch != 'I' && qp - g.qpos >= g.qlen)) return false;
 		int f; i64 t;
-		if (trk_col(x.b, ch, rp, f, t)) { if (ch == 'M') f = trk_pair(a.ref[rp], a.query[qp]); if (trk_win(a, x.b, t) == x.wa) trk_add(vA, f, 1u); else trk_add(vB, f, 1u); }
-		if (ch != 'D') rp++;
-		if (ch != 'I') qp++;
+		if (trk_col(x.b, ch, rp, f, t)) { if (ch == 'M') f = (int)col_mismatch(a.ref[rp], a.query[qp]); if (trk_win(a, x.b, t) == x.wa) trk_add(vA, f, 1u); else trk_add(vB, f, 1u); }
+		col_advance(ch, rp, qp);
 	}
 	return rp - g.rpos == g.rlen && qp - g.qpos == g.qlen;
 }
 
-// the same by a whole wavefront, 64 columns per step: a lane's reference / query position is the step's base plus the number of lower lanes whose column consumes a
-// base of that side
+// the same by a whole wavefront, 64 columns per step (wave_step)
 __device__ bool trk_wave(const TrkIn &a, const TrkAt &x)
 {
 	const TrkRec &g = x.g;
-	const int lane = threadIdx.x & 63;
-	const unsigned long long below = (1ull << lane) - 1ull;
 	i64 rp0 = g.rpos; i32 qp0 = g.qpos; bool ok = true;
 	for (i32 base = 0; base < g.L; base += 64) {
-		const i32 p = base + lane;
-		const int ch = p < g.L ? (g.op ? (int)g.op[p] : (int)'M') : 0;
-		const bool c1 = ch == 'M' || ch == 'I', c2 = ch == 'M' || ch == 'D';
-		const unsigned long long m1 = __ballot(c1), m2 = __ballot(c2);
-		const i64 rp = rp0 + __popcll(m1 & below); const i32 qp = qp0 + __popcll(m2 & below);
-		const bool out = (c1 && rp - g.rpos >= g.rlen) || (c2 && qp - g.qpos >= g.qlen);
+		const WaveCol w = wave_step(g.op, g.L, base, rp0, qp0);
+		const bool out = (w.c1 && w.rp - g.rpos >= g.rlen) || (w.c2 && w.qp - g.qpos >= g.qlen);
 		if (__ballot(out)) { ok = false; break; }
 		u32 v[4] = { 0, 0, 0, 0 }; i32 key = -1;
 		int f; i64 t;
-		if (ch && trk_col(x.b, ch, rp, f, t)) { if (ch == 'M') f = trk_pair(a.ref[rp], a.query[qp]); key = trk_win(a, x.b, t); if (key >= 0) trk_add(v, f, 1u); else ok = false; }
+		if (w.ch && trk_col(x.b, w.ch, w.rp, f, t)) { if (w.ch == 'M') f = (int)col_mismatch(a.ref[w.rp], a.query[w.qp]); key = trk_win(a, x.b, t); if (key >= 0) trk_add(v, f, 1u); else ok = false; }
 		trk_flush(a, key, v);
-		rp0 += __popcll(m1); qp0 += __popcll(m2);
 	}
 	return __ballot(!ok) == 0ull && rp0 - g.rpos == g.rlen && qp0 - g.qpos == g.qlen;
 }
@@ -196,7 +180,7 @@ __global__ void __launch_bounds__(256) k_trk_count(TrkIn a, unsigned long long *
 		if (x.bad) atomicAdd(bad + 1, 1ull);
 		if (g.kind == TK_BAD) atomicAdd(bad, 1ull);
 		else if (g.kind == TK_NONE) { }
-		else if (span > 1 || (g.kind == TK_WALK && g.L > TRK_SERIAL)) { const int at = atomicAdd(&s_n, 1); s_list[at] = tid; }
+		else if (span > 1 || (g.kind == TK_WALK && g.L > WALK_SERIAL)) { const int at = atomicAdd(&s_n, 1); s_list[at] = tid; }
 		else {
 			kA = x.wa; if (x.wb != x.wa) kB = x.wb;
 			if (g.kind == TK_INS) vA[3] = (u32)g.qlen;
@@ -237,13 +221,8 @@ __device__ __forceinline__ TrkItem trk_item(const TrkIn &a, i64 w)
 __global__ void __launch_bounds__(256) k_trk_own(TrkIn a, i64 *wg)
 {
 	__shared__ i32 s_w[4];
-	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-	const i64 w = (i64)blockIdx.x * 256 + tid;
-	i32 tot = (w < a.n_items && trk_item(a, w).own) ? 1 : 0;
-	for (int d = 32; d; d >>= 1) tot += __shfl_xor(tot, d);
-	if (lane == 0) s_w[wv] = tot;
-	__syncthreads();
-	if (tid == 0) wg[blockIdx.x] = (i64)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+	const i64 w = (i64)blockIdx.x * 256 + threadIdx.x;
+	wg_count(w < a.n_items && trk_item(a, w).own, s_w, wg);
 }
 
 __global__ void __launch_bounds__(256) k_trk_scan(i64 nwg, i64 *wg, const unsigned long long *bad, i64 *hdr)
@@ -286,36 +265,27 @@ int ref_track(gsa_ctx *c, i32 k, gsa_tracks *out)
 	if (!c->result_pinned) return gsa_fail(c, GSA_ERR_STATE, "gsa_ref_track: the context holds no finished (stage 8) result");
 	hipStream_t st = c->stream;
 	const size_t nchr = c->h_chr_len.size();
-	if (!pin_ensure<TrkBlk>(c, c->p_tblk, nb + 1) || !pin_ensure<i64>(c, c->p_thdr, 4)) return GSA_ERR_NOMEM;
+	if (!pin_ensure<i64>(c, c->p_thdr, 4)) return GSA_ERR_NOMEM;
 	std::vector<i32> win0(nchr + 1, 0);
 	for (size_t i = 0; i < nchr; i++) win0[i + 1] = win0[i] + (i32)(((i64)c->h_chr_len[i] + W - 1) / W);
-	// the counted blocks, and their trimmed spans in forward coordinates: a few KB from the blocks and their first and last records, which the host holds
-	TrkBlk *hb = c->p_tblk.as<TrkBlk>(); i32 nt = 0; i64 items = 0; unsigned long long depth = 0;
+	// the counted blocks (not duplicates, on a sequence the index knows), and their trimmed spans in forward coordinates
+	i32 nt = 0; i64 items = 0; unsigned long long depth = 0;
 	std::vector<TrkIv> iv;
-	const gsa_rec *recs = c->p_frags.as<gsa_rec>() + rr.f0;
-	for (size_t j = 0; j < nb; j++) {
-		const gsa_block &bl = c->h_blocks[rr.b0 + j];
-		if (bl.bdup != 0 || bl.n_frag <= 0 || bl.chr < 0 || (size_t)bl.chr >= nchr) continue;
-		gsa_frag first, last;
-		gsa_rec_expand(recs, bl.frag_off, &first); gsa_rec_expand(recs, bl.frag_off + bl.n_frag - 1, &last);
+	auto keep = [&](const gsa_block &bl) { return bl.bdup == 0 && bl.chr >= 0 && (size_t)bl.chr < nchr; };
+	auto extra = [&](const gsa_block &bl, TrkBlk &v, const gsa_frag &first, const gsa_frag &last) {
 		const i64 fwd = c->h_chr_fwd[(size_t)bl.chr], len = c->h_chr_len[(size_t)bl.chr];
-		const i64 lim = bl.bdir ? fwd + len : 2 * c->G - fwd;      // end of the block's chromosome copy (iExtension, tools.cpp:192-202)
-		TrkBlk &v = hb[nt];
-		v.frag_off = bl.frag_off + rr.f0; v.wbase = items; v.start = first.rpos; v.end = std::min<i64>(last.rpos + last.rlen, lim);
-		v.rev = bl.bdir ? 0 : 1; v.org = v.rev ? 2 * c->G - 1 - fwd : fwd; v.n_frag = bl.n_frag; v.win0 = win0[(size_t)bl.chr]; v.clen = (i32)len;
-		if (v.end <= v.start) continue;
+		v.org = v.rev ? 2 * c->G - 1 - fwd : fwd; v.win0 = win0[(size_t)bl.chr]; v.clen = (i32)len;
 		const i64 s = v.rev ? v.org - (v.end - 1) : v.start - v.org, e = v.rev ? v.org - v.start + 1 : v.end - v.org;      // [s, e) inside the sequence
 		if (s < 0 || e > len) return gsa_fail(c, GSA_ERR_STATE, "internal: gsa_ref_track met a block outside its reference sequence");
 		depth += (unsigned long long)(last.rpos + last.rlen - first.rpos) + (unsigned long long)std::max<i64>((i64)last.qpos + last.qlen - first.qpos, 0);
 		TrkIv u; u.wbase = 0; u.chr = bl.chr; u.s = (i32)s; u.e = (i32)e; u.clen = (i32)len; u.win0 = v.win0; u._pad = 0;
 		iv.push_back(u);
-		items += bl.n_frag; nt++;
-	}
+		return (int)GSA_OK;
+	};
+	if (const int rc = span_build<TrkBlk>(c, rr, "gsa_ref_track", c->p_tblk, SPAN_SENTINEL, keep, extra, nt, items)) return rc;
 	if (nt == 0) return GSA_OK;
 	// (the counts are uint32_t, and none can exceed the columns of the counted blocks: include/gsa_hip.h)
 	if (depth > 0xffffffffull) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_ref_track: the counted blocks span " + std::to_string(depth) + " bases, more than a 32-bit count holds");
-	if (items >= (1ll << 31) - 256) return gsa_fail(c, GSA_ERR_LIMIT, "gsa_ref_track: too many records");
-	{ TrkBlk &v = hb[nt]; memset(&v, 0, sizeof(v)); v.wbase = items; }
 	std::sort(iv.begin(), iv.end(), [](const TrkIv &x, const TrkIv &y) { return x.chr != y.chr ? x.chr < y.chr : (x.s != y.s ? x.s < y.s : x.e < y.e); });
 	size_t niv = 0;
 	for (size_t j = 0; j < iv.size(); j++) {
@@ -344,7 +314,7 @@ int ref_track(gsa_ctx *c, i32 k, gsa_tracks *out)
 	}
 	i64 *wg = c->d_twg.as<i64>(); unsigned long long *bad = (unsigned long long *)(wg + nwg_e);
 	i64 *hdr = c->p_thdr.as<i64>();
-	GSA_CHECK(c, hipMemcpyAsync(c->d_tblk.p, hb, ((size_t)nt + 1) * sizeof(TrkBlk), hipMemcpyHostToDevice, st));
+	GSA_CHECK(c, hipMemcpyAsync(c->d_tblk.p, c->p_tblk.p, ((size_t)nt + 1) * sizeof(TrkBlk), hipMemcpyHostToDevice, st));
 	GSA_CHECK(c, hipMemcpyAsync(c->d_tiv.p, hv, (niv + 1) * sizeof(TrkIv), hipMemcpyHostToDevice, st));
 	GSA_CHECK(c, hipMemsetAsync(bad, 0, 2 * sizeof(unsigned long long), st));
 	TrkIn a;

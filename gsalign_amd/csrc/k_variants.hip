@@ -14,10 +14,7 @@
 // jobs launched early) and the two sequences -- an aligned column is the sequence byte or '-' (ksw2_alignment.cpp:264-272:
 // 'D' puts '-' into aln1, 'I' into aln2); an equal-length gap that needed no DP is all 'M'.  One byte per column instead
 // of two, and one code path.
-#include "gsa_fm.h"
 #include "gsa_walk.h"
-
-#define VAR_SERIAL 64      // records of at most this many columns are walked by one lane, longer ones by a wavefront in 64-column steps
 
 struct VarBlk { i64 frag_off; i32 n_frag, chr, block, wbase; };      // one surviving, non-duplicate block: first record (absolute), records, its reference sequence, index in gsa_result::blocks, first work item
 struct VarIn : GapIn {
@@ -93,8 +90,7 @@ __device__ i32 var_lane(const VarIn &a, const VarGap &g, const VarBlk &vb, gsa_v
 	return n;
 }
 
-// a long walk by a whole wavefront, 64 columns per step: positions and slots from ballots -- a lane's rp / qp is the step's base plus the
-// number of lower lanes whose column consumes a reference / query base, its slot the base plus the number of lower lanes that start a variant
+// a long walk by a whole wavefront, 64 columns per step (wave_step): a lane's slot is the step's base plus the number of lower lanes that start a variant
 template <bool EMIT>
 __device__ i32 var_wave(const VarIn &a, const VarGap &g, const VarBlk &vb, gsa_variant *out, i64 slot, i32 cnt[3])
 {
@@ -102,11 +98,8 @@ __device__ i32 var_wave(const VarIn &a, const VarGap &g, const VarBlk &vb, gsa_v
 	const unsigned long long below = (1ull << lane) - 1ull;
 	i64 rp0 = g.rpos; i32 qp0 = g.qpos, n = 0; int carry = 0;      // carry: the column in front of the step
 	for (i32 base = 0; base < g.L; base += 64) {
-		const i32 p = base + lane; const bool valid = p < g.L;
-		const int ch = valid ? (g.op ? (int)g.op[p] : (int)'M') : 0;
-		const bool c1 = ch == 'M' || ch == 'I', c2 = ch == 'M' || ch == 'D';
-		const unsigned long long m1 = __ballot(c1), m2 = __ballot(c2);
-		const i64 rp = rp0 + __popcll(m1 & below); const i32 qp = qp0 + __popcll(m2 & below);
+		const WaveCol w = wave_step(g.op, g.L, base, rp0, qp0);
+		const i32 p = w.p; const int ch = w.ch; const i64 rp = w.rp; const i32 qp = w.qp;
 		int pch = __shfl_up(ch, 1); if (lane == 0) pch = carry;
 		const bool ins = ch == 'D' && pch != 'D', del = ch == 'I' && pch != 'I';
 		const bool sub = ch == 'M' && var_subst(a.ref[rp], a.query[qp]);
@@ -118,7 +111,7 @@ __device__ i32 var_wave(const VarIn &a, const VarGap &g, const VarBlk &vb, gsa_v
 			if (!sub) { run = 1; while (p + run < g.L && g.op[p + run] == ch) run++; }
 			var_put(a, out, slot + n + __popcll(ms & below), vb, sub ? 0 : (ins ? 3 : 4), sub ? rp : rp - 1, sub ? qp : qp - 1, run);
 		}
-		rp0 += __popcll(m1); qp0 += __popcll(m2); n += __popcll(ms); carry = __shfl(ch, 63);
+		n += __popcll(ms); carry = __shfl(ch, 63);
 	}
 	return n;
 }
@@ -145,7 +138,7 @@ __global__ void __launch_bounds__(256) k_var_pass(VarIn a, i32 *nv, i64 *wg, uns
 	const i64 wgb = EMIT ? wg[blockIdx.x] : 0;      // the workgroup's first slot
 	if (EMIT) slot = wgb + wg_excl_scan<i32>(w < a.W ? nv[w] : 0, s_w);      // the workgroup's first slot plus the counts in front of the record inside it
 	__syncthreads();
-	const bool wide = g.cls == VC_WALK && g.L > VAR_SERIAL;
+	const bool wide = g.cls == VC_WALK && g.L > WALK_SERIAL;
 	i32 n = 0;
 	if (wide) { const int at = atomicAdd(&s_n, 1); s_list[at] = tid; }
 	else if (g.cls == VC_BAD) { if (!EMIT) atomicAdd(&kinds[3], 1ull); }
@@ -227,7 +220,7 @@ int call_variants(gsa_ctx *c, i32 k, gsa_variants *out)
 	}
 	if (timed) GSA_CHECK(c, hipEventRecord(c->ev_var[1], st));
 	GSA_CHECK(c, hipStreamSynchronize(st));
-	if (timed) { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_var[0], c->ev_var[1]) == hipSuccess) { c->var_ms_sum += ms; c->var_calls++; } (void)hipGetLastError(); }
+	if (timed) { float ms = 0; if (hipEventElapsedTime(&ms, c->ev_var[0], c->ev_var[1]) == hipSuccess) { c->pass_stat[PASS_VAR].ms_sum += ms; c->pass_stat[PASS_VAR].calls++; } (void)hipGetLastError(); }
 	out->n = n; out->v = n ? c->p_var.as<gsa_variant>() : nullptr; out->n_snv = hdr[1]; out->n_ins = hdr[2]; out->n_del = hdr[3];
 	return GSA_OK;
 }
