@@ -517,6 +517,8 @@ int gsa_set_option(gsa_ctx *c, const char *name, int64_t value)
 	else if (k == "pd_bitmap") c->opt.pd_bitmap = value != 0;
 	else if (k == "dp_side") c->opt.dp_side = value != 0;
 	else if (k == "dp_pair") { if (!in(0, 3)) return gsa_fail(c, GSA_ERR_ARG, "dp_pair: 0 never, 1 where it costs fewer wave-steps in a long class, 2 always, 3 where it costs fewer wave-steps"); c->opt.dp_pair = (int)value; }
+	else if (k == "dp_band") { if (!in(0, 2)) return gsa_fail(c, GSA_ERR_ARG, "dp_band: 0 never, 1 where the band costs at most 3/4 of the striped wave-steps, 2 every job the layout admits"); c->opt.dp_band = (int)value; }
+	else if (k == "dp_band_margin") { if (!in(1, 63)) return gsa_fail(c, GSA_ERR_ARG, "dp_band_margin: 1 .. 63 diagonals"); c->opt.dp_band_margin = (int)value; }
 	else if (k == "pd_two_level_min") { if (!in(0, BIG)) return gsa_fail(c, GSA_ERR_ARG, "pd_two_level_min: >= 0 blocks"); c->opt.pd_two_level_min = value; }
 	else if (k == "pd_bytes") { if (!in(0, 2)) return gsa_fail(c, GSA_ERR_ARG, "pd_bytes: 0 never, 1 by the hit count, 2 always"); c->opt.pd_bytes = (int)value; }
 	else if (k == "pres_from_kmer") c->opt.pres_from_kmer = value != 0;      // (takes effect at the next gsa_set_params that rebuilds the table)

@@ -83,6 +83,8 @@ struct Options {
 	int sweep_shape = -1;              // k_dense_sweep's launch shape: -1 by the number of dense chunks, 0 = four chunks per two-wave workgroup / 160-start segments, 1 = one chunk per four-wave workgroup / 40-start segments
 	int dp_side = 0;                   // 1: the striped DP's lower size class on a stream of its own, beside the upper class (0: behind it)
 	int dp_pair = 1;                   // the striped DP runs two jobs side by side in a wave's 16-bit halves: 0 never (every job in the lagged form), 1 where that costs fewer wave-steps, in size classes of at least DP_PAIR_MIN_JOBS jobs, 2 every two neighbours of a size class, 3 as 1 in a class of any length (2, 3: tests)
+	int dp_band = 1;                   // near-diagonal striped jobs run in k_dp_band first and keep its result where the certificate holds: 0 never, 1 where the band costs at most 3/4 of the striped form's wave-steps, 2 every job the layout admits (tests)
+	int dp_band_margin = 32;           // B: the band certified is the diagonals [min(0, n - m) - B, max(0, n - m) + B]
 	int64_t walk_chain_min = 100000;   // contigs with more seeds than this walk their window chain in slices (k_walk_chain) instead of one workgroup's LDS (k_walk_windows); tests: 0
 	int64_t pd_two_level_min = 2000000;   // PosDiff bitmaps of more blocks than this (a reference above ~1 Gbp) are scanned in two passes: list the touched blocks, count those (tests: 0)
 	int pd_bytes = 1;                  // the PosDiff bitmap of a contig (bundle) whose hits scatter (-sen: thousands of chance hits per chunk) is filled through a byte per value, plain stores, and packed
@@ -235,6 +237,9 @@ struct gsa_ctx {
 	bool dp_timeout = false, dp_safe = false;      // a striped launch tripped its wait bound; repeat the contig with one job per launch
 	int dp_fake_timeout = 0;                       // test hook (GSA_DP_FAKE_TIMEOUT=n at gsa_create): the next n contigs report a hand-off time-out once, so the retry paths run
 	u32 dp_epoch = 0;                              // tag of the boundary granules of the current striped launch
+	DevBuf d_band_dir, d_band_seq, d_band_cert, d_band_stat;   // band DP (k_dp_band.hip): direction nibbles, the pairs' code strings, {certified tag per job, "has an N" per pair}, the certified-jobs counter
+	u32 band_epoch = 0;                            // tag of the certified flags of the current band launch
+	u64 band_eligible = 0;                         // jobs given to k_dp_band since the context was made (gsa_get_dp_band_stats)
 	DevBuf p_dp, p_sj, p_sj_early;                 // pinned: mailbox + large-job list; stripe job tables (read by the kernels in place)
 	DevBuf d_alnoff;
 	DevBuf bl_alnlen, bl_score;
@@ -293,7 +298,7 @@ struct gsa_ctx {
 	X(d_btab) X(d_flag2) X(d_scan2) X(d_i64a) X(b_q) X(b_len) X(b_r) X(b_gb) X(b_ge) X(c_q) X(c_len) X(c_r) X(c_gb) X(c_ge) X(c_bid) X(blk_beg) X(blk_end) X(blk_score) \
 	X(r_q) X(r_len) X(r_r) X(r_bid) X(r_tmp_q) X(r_tmp_len) X(r_tmp_r) X(r_tmp_bid) X(r_cut4) X(r_cut5) X(r_simjob) X(r_simres) X(d_leaf) \
 	X(fb_seedbase) X(fb_sbeg) X(fb_fragbase) X(f_rec) X(f_rec16) X(f_type) X(f_mism) X(f_alnlen) X(f_job) X(f_score) \
-	X(d_dp_lane_order) X(d_dp_bnd) X(d_dp_ctr) X(d_dp_jobs) X(d_dp_large) X(d_tail) \
+	X(d_dp_lane_order) X(d_dp_bnd) X(d_dp_ctr) X(d_dp_jobs) X(d_dp_large) X(d_tail) X(d_band_dir) X(d_band_seq) X(d_band_cert) X(d_band_stat) \
 	X(e_id) X(e_rec) X(e_list) X(e_off1) X(e_off2) X(e_opsoff) X(e_nops) X(e_ops) X(e_rev) X(r_head) X(f_early) X(r_orig) X(r_tmp_orig) \
 	X(j_frag) X(j_opsoff) X(j_nops) X(d_ops) X(j_cells) X(d_alnoff) X(bl_alnlen) X(bl_score) X(d_bblk) X(d_dp_arena) \
 	X(d_vblk) X(d_vcnt) X(d_vwg) X(d_var) X(d_cblk) X(d_cout) X(d_ccnt) X(d_cwg) X(d_cpre) X(d_crun) X(d_cops) X(d_crpos) X(d_cqpos) X(d_slen) X(d_swg) X(d_spre) X(d_sout) X(d_cs) \
@@ -408,6 +413,12 @@ int cs_call(gsa_ctx *c, int32_t k, gsa_cs *out, gsa_cigars *cig);   // gsa_api.h
 struct LgJob { i32 job, m, n; };
 int launch_stripes(gsa_ctx *c, hipStream_t ss, std::vector<LgJob> &large, const uint8_t *pool1, const i64 *off1, const uint8_t *pool2, const i64 *off2,
                    uint8_t *ops, const i64 *ops_off, i32 *ops_len, uint8_t *rev, int err_slot);   // k_dp_stripe.hip
+// the band class of a striped batch (k_dp_band.hip): large[idx[k]] are its jobs, in the order of their certified flags cert[k] (the returned array: == tag where job k's result stands)
+struct BandJob { i32 job, m, n, base; i64 diroff, seqoff; };      // base: diagonal i - j of lane 0's even diagonal; seqoff: the pair's code strings (in X's entry)
+bool dp_band_eligible(const gsa_ctx *c, int m, int n, i64 stripe_steps);
+size_t dp_band_table_bytes(size_t njobs);
+int launch_band(gsa_ctx *c, hipStream_t st, const std::vector<LgJob> &large, const std::vector<i32> &idx, BandJob *tab, const uint8_t *pool1, const i64 *off1, const uint8_t *pool2, const i64 *off2,
+                uint8_t *ops, const i64 *ops_off, i32 *ops_len, uint8_t *rev, const u32 **cert, u32 *tag);
 int launch_small_dp(gsa_ctx *c, hipStream_t st, i32 nlane, const i32 *order_lane, i32 nsmall, const i32 *order_small, const uint8_t *pool1, const i64 *off1, const i32 *len1,
                     const uint8_t *pool2, const i64 *off2, const i32 *len2, uint8_t *ops, const i64 *ops_off, i32 *ops_len, const i32 *jfrag, gsa_frag *frag);   // k_dp_small.hip  (k_dp_lane + k_dp_small beside `st`; ev[12] marks their end)
 struct Ksw2Launch { i32 n = 0, nsmall = 0, nlarge = 0; bool small_in_flight = false; };      // what run_ksw2_jobs left running

@@ -8,7 +8,8 @@
 //    alignment.  Both kernels and their launch (launch_small_dp): k_dp_small.hip.
 //  * k_dp_stripe  everything else (up to 5000 x 5000): the target columns are cut into 64-wide stripes, one wavefront
 //    per PAIR of stripes (packed 16-bit VALU), boundary columns handed over through LDS / HBM.  The kernel and its
-//    launch by size class of the reference fragment (launch_stripes): k_dp_stripe.hip.
+//    launch by size class of the reference fragment (launch_stripes): k_dp_stripe.hip.  Its near-diagonal jobs run in
+//    k_dp_band first (a window of 128 diagonals, two jobs per wavefront, certified or redone here): k_dp_band.hip.
 #include <algorithm>
 #include <cstring>
 #include "gsa_ctx.h"

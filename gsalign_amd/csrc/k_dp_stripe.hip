@@ -39,7 +39,7 @@
 // whatever order the dispatcher starts workgroups in and whatever else competes for the CUs.  The wait is still
 // bounded (2 s of wall clock): a launch that trips it is repeated job by job (gsa_align_contig, dp_safe).
 // ---------------------------------------------------------------------------
-struct StripeJob { i32 job, m, n, P; i64 diroff, bndoff; i32 ctr, first_block; };
+struct StripeJob { i32 job, m, n, P; i64 diroff, bndoff; i32 ctr, first_block; i32 cert, pad_; };      // cert: the job's flag in the band class's list, -1: not in it
 #define DP_TILE_ROWS 160        // local diagonals of a traceback tile (64 diagonal steps need 128); a multiple of 8
 #define DP_STRIPE_BYTES(M) ((((size_t)(M) + 63 + 7) >> 3) << 8)      // (M + 63) anti-diagonals of 64 nibbles, in blocks of eight
 #define DP_C1_PAD 320           // code bytes around the reference fragment: 128 "N" rows in front (stripe B starts 64 steps late, lane 63 another 63), the rest behind
@@ -94,7 +94,8 @@ __device__ __forceinline__ u32 dp_unpack4(u32 g) { return (g & 0xfu) | ((g & 0xf
 template <int WPB, int SBS>
 __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ blk2job, const StripeJob *__restrict__ sjobs, const uint8_t *__restrict__ pool1, const i64 *__restrict__ off1,
                                                    const uint8_t *__restrict__ pool2, const i64 *__restrict__ off2, uint8_t *dirbase, u32 *bndbase, u32 *ctr,
-                                                   uint8_t *revbase, uint8_t *ops, const i64 *__restrict__ ops_off, i32 *ops_len, u32 ep, i32 lds_c1, i32 lds_rows, u32 *err, i32 tick_slot)
+                                                   uint8_t *revbase, uint8_t *ops, const i64 *__restrict__ ops_off, i32 *ops_len, u32 ep, i32 lds_c1, i32 lds_rows, u32 *err, i32 tick_slot,
+                                                   const u32 *__restrict__ cert, u32 cert_tag)
 {
 	extern __shared__ __attribute__((aligned(16))) u32 C2[];           // the reference fragment as byte selectors of the two stripes' score tables
 	// The traceback tile ALIASES the forward pass's LDS (codes + boundary columns): the wave that walks back drew the last
@@ -119,6 +120,10 @@ __global__ void __launch_bounds__(64 * WPB) k_dp_stripe(const i32 *__restrict__ 
 	// dependent reads across the link cost less than a copy operation in front of the launch
 	const StripeJob sj = sjobs[blk2job[bid]];
 	const StripeJob sy = SBS ? sjobs[blk2job[bid] + 1] : sj;            // side by side: job Y of the pair (the high halves)
+	// The band kernel (k_dp_band.hip) ran in front of this launch: a job it certified has its result, and its workgroups leave here -- behind the launch
+	// ticket, which names the job and which every workgroup of a launch must draw (the last one clears it), in front of the job's own ticket, its boundary
+	// granules and its direction blocks.  Side by side: only where both partners are certified; else the pair runs as ever and rewrites the same bytes.
+	if (sj.cert >= 0 && cert[sj.cert] == cert_tag && (!SBS || (sy.cert >= 0 && cert[sy.cert] == cert_tag))) return;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const int m = sj.m, n = sj.n, P = sj.P, PP = SBS ? (P > sy.P ? P : sy.P) : (P + 1) >> 1;      // PP: waves of the (virtual) job
 	const int mB = SBS ? sy.m : m, nB = SBS ? sy.n : n;                                    // the high halves' job (lagged: the same one)
@@ -550,9 +555,22 @@ int launch_stripes(gsa_ctx *c, hipStream_t st, std::vector<LgJob> &large, const 
 			dp_make_units(large, sg.b, sg.e, mode == 3 ? 1 : mode, sg.units);
 			for (const DpUnit &u : sg.units) { c->dp_stats[0] += u.y >= 0 ? 2 : 1; c->dp_stats[1] += u.y >= 0 ? 2 : 0; }
 		}
-		if (!pin_ensure<char>(c, psj, (cnt + 1) * sizeof(StripeJob) + (nb_ub + 2) * 4)) return GSA_ERR_NOMEM;
+		// The band class: the near-diagonal jobs of the batch go through k_dp_band first (launch_band); they keep their place in the lists below, and their
+		// workgroups leave the striped kernel where the band result is certified.  band_ord: a job's place in the band list (its flag), by place in `large`
+		std::vector<i32> band_idx, band_ord(cnt, -1);
+		if (c->opt.dp_band && !c->dp_safe) {
+			for (size_t k = first; k < first + cnt; k++) {
+				const LgJob &g = large[k];
+				if (dp_band_eligible(c, g.m, g.n, std::min(dp_steps_lagged(g.m, g.n), dp_steps_pair(g.m, g.n, g.m, g.n) / 2))) band_idx.push_back((i32)k);
+			}
+			std::sort(band_idx.begin(), band_idx.end(), [&](i32 p, i32 q) { const int sp = large[(size_t)p].m + large[(size_t)p].n, sq = large[(size_t)q].m + large[(size_t)q].n; return sp != sq ? sp > sq : large[(size_t)p].job < large[(size_t)q].job; });
+			for (size_t k = 0; k < band_idx.size(); k++) band_ord[(size_t)band_idx[k] - first] = (i32)k;
+		}
+		const size_t sj_bytes = ((cnt + 1) * sizeof(StripeJob) + (nb_ub + 2) * 4 + 15) & ~(size_t)15;
+		if (!pin_ensure<char>(c, psj, sj_bytes + dp_band_table_bytes(band_idx.size()))) return GSA_ERR_NOMEM;
 		StripeJob *sj = psj.as<StripeJob>();
 		i32 *b2j_all = (i32 *)(sj + cnt + 1);
+		BandJob *band_tab = (BandJob *)(psj.as<char>() + sj_bytes);
 		i64 dbytes = 128, bwords = 0; i32 nctr = 2 * NSEG; size_t b2j_used = 0, nsj = 0;      // (ctr[0 .. 2 NSEG - 1]: launch tickets of the size classes' two forms)
 		for (Seg &sg : seg) {
 			for (int form = 0; form < 2; form++) {
@@ -564,6 +582,7 @@ int launch_stripes(gsa_ctx *c, hipStream_t st, std::vector<LgJob> &large, const 
 					StripeJob s[2];
 					for (int q = 0; q < nj; q++) {
 						const LgJob &g = large[q ? (size_t)u.y : u.x];
+						s[q].cert = band_ord[(q ? (size_t)u.y : u.x) - first]; s[q].pad_ = 0;
 						const i64 cells = (((i64)g.n + 63) / 64) * (i64)DP_STRIPE_BYTES(g.m);   // stripe-local direction nibbles
 						s[q].job = g.job; s[q].m = g.m; s[q].n = g.n; s[q].P = (g.n + 63) / 64;
 						s[q].diroff = dbytes; dbytes += cells + 128;
@@ -595,6 +614,8 @@ int launch_stripes(gsa_ctx *c, hipStream_t st, std::vector<LgJob> &large, const 
 		//  was measured at 250 Mb: same step time, the refinement passes beside them starve instead: the chip is busy either way)
 		// (option dp_side: the lower class on a stream of its own -- it then starts with the upper one instead of behind it; the classes share
 		//  nothing but the error word: tickets per class, direction / boundary bytes per job)
+		const u32 *cert = nullptr; u32 cert_tag = 0;
+		if (!band_idx.empty()) { int rc = launch_band(c, st, large, band_idx, band_tab, pool1, off1, pool2, off2, ops, ops_off, ops_len, rev, &cert, &cert_tag); if (rc) return rc; }
 		auto blocks_of = [&](int si) { return seg[si].nblocks[0] + seg[si].nblocks[1]; };
 		const bool side = c->opt.dp_side && c->stream_aux[3] && blocks_of(NSEG - 1) > 0 && (blocks_of(0) > 0 || blocks_of(1) > 0 || blocks_of(2) > 0);
 		// A class's unpaired jobs -- what found no partner in (stripe count, m) order: the odd sizes, the largest among them -- run BESIDE its pairs, on
@@ -610,10 +631,10 @@ int launch_stripes(gsa_ctx *c, hipStream_t st, std::vector<LgJob> &large, const 
 			hipStream_t st = (beside && sg.nblocks[1] > 0) ? c->stream_aux[3] : st_seg;      // (of the lagged launch)
 			c->dp_stats[2] += sg.nblocks[0] > 0; c->dp_stats[3] += sg.nblocks[1] > 0;
 			if (sg.nblocks[0] > 0) {
-				if (sg.wpb == 4) hipLaunchKernelGGL((k_dp_stripe<4, 0>), dim3((unsigned)sg.nblocks[0]), dim3(256), sg.dyn_lds, st, (const i32 *)sg.b2j[0], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si);
-				else hipLaunchKernelGGL((k_dp_stripe<1, 0>), dim3((unsigned)sg.nblocks[0]), dim3(64), sg.dyn_lds, st, (const i32 *)sg.b2j[0], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si);
+				if (sg.wpb == 4) hipLaunchKernelGGL((k_dp_stripe<4, 0>), dim3((unsigned)sg.nblocks[0]), dim3(256), sg.dyn_lds, st, (const i32 *)sg.b2j[0], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si, cert, cert_tag);
+				else hipLaunchKernelGGL((k_dp_stripe<1, 0>), dim3((unsigned)sg.nblocks[0]), dim3(64), sg.dyn_lds, st, (const i32 *)sg.b2j[0], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si, cert, cert_tag);
 			}
-			if (sg.nblocks[1] > 0) hipLaunchKernelGGL((k_dp_stripe<4, 1>), dim3((unsigned)sg.nblocks[1]), dim3(256), sg.dyn_lds, st_seg, (const i32 *)sg.b2j[1], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si + 1);
+			if (sg.nblocks[1] > 0) hipLaunchKernelGGL((k_dp_stripe<4, 1>), dim3((unsigned)sg.nblocks[1]), dim3(256), sg.dyn_lds, st_seg, (const i32 *)sg.b2j[1], (const StripeJob *)sj, pool1, off1, pool2, off2, dir + 256, bnd, ctr, rev, ops, ops_off, ops_len, c->dp_epoch, (i32)(sg.mpad * 4), (i32)sg.lds_rows, (u32 *)(mail + err_slot), 2 * si + 1, cert, cert_tag);
 		}
 		if (side || beside) { GSA_CHECK(c, hipEventRecord(c->ev[25], c->stream_aux[3])); GSA_CHECK(c, hipStreamWaitEvent(st, c->ev[25], 0)); }
 		GSA_CHECK(c, hipGetLastError());

@@ -186,6 +186,11 @@ void gsa_release_reserved(int device);
  *   "dp_pair"        the striped DP puts two jobs of a size class side by side into the 16-bit halves of a wavefront: 1 (default) = where that costs fewer
  *                    wave-steps than the two jobs one after the other and the class holds at least 4096 jobs (shorter lists are bound by their longest
  *                    job, not by instructions), 0 = never, 2 = every two neighbours, 3 = by the step count alone (2, 3: tests).  Results do not depend on it
+ *   "dp_band"        near-diagonal jobs of the striped DP are first evaluated inside a band of diagonals, two jobs per wavefront, a step per anti-diagonal
+ *                    (m + n steps instead of (m + 63) per 64 columns); a job whose band score proves the band exact keeps that result, any other runs in the
+ *                    striped kernel as before: 1 (default) = jobs whose band costs at most 3/4 of the striped wave-steps, 0 = never, 2 = every job the
+ *                    layout admits (tests).  "dp_band_margin" B (32; 1 .. 63): the band is the diagonals from min(0, n - m) - B to max(0, n - m) + B and
+ *                    must fit 128 diagonals.  Results do not depend on either
  *   "walk_chain_min" seeds; a contig with more seeds than this walks its window chain (chaining, GSAlign.cpp:326-338) in slices of the candidate list,
  *                    one launch (default 100 000; below that one workgroup holds the chain in LDS).  Results do not depend on it (tests: 0)
  *   "pd_two_level_min" blocks; PosDiff bitmaps larger than this are scanned in two passes (touched blocks listed, then counted); default 2 000 000
@@ -749,6 +754,10 @@ int gsa_get_seed_stats(gsa_ctx *ctx, uint64_t stats[8]);
 /* What the striped gap DP launched since the context was made (sums; a clone starts at zero): [0] jobs, [1] of them side by side with a partner
  * (option "dp_pair"), [2] launches of the lagged form, [3] launches of the side-by-side form. */
 int gsa_get_dp_stats(gsa_ctx *ctx, uint64_t stats[4]);
+/* What the band class of the striped gap DP did since the context was made (options "dp_band", "dp_band_margin"; a clone starts at zero): [0] jobs
+ * evaluated inside the diagonal band, [1] of them certified -- the band result is the full matrix's and stands --, [2] fallen back to the striped
+ * kernel.  Waits for the context's work in flight. */
+int gsa_get_dp_band_stats(gsa_ctx *ctx, uint64_t stats[3]);
 
 #ifdef __cplusplus
 }
