@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libgsa_hip.so")
 
 EXPORTS = [
     "gsa_default_params", "gsa_create", "gsa_create_opts", "gsa_reserve_index", "gsa_release_reserved", "gsa_clone", "gsa_clone_to_device", "gsa_host_alloc", "gsa_host_free", "gsa_destroy", "gsa_set_params", "gsa_last_error", "gsa_align_contig", "gsa_align_many", "gsa_align_bundle",
-    "gsa_align_contig_device", "gsa_set_query_device", "gsa_device_alloc", "gsa_device_free", "gsa_device_upload", "gsa_get_seed_stats", "gsa_get_dp_stats", "gsa_get_dp_band_stats", "gsa_hit_buffers", "gsa_seed_chunks", "gsa_hit_count", "gsa_export_hits", "gsa_import_hits", "gsa_finish_contig",
+    "gsa_align_contig_device", "gsa_set_query_device", "gsa_device_alloc", "gsa_device_free", "gsa_device_upload", "gsa_get_seed_stats", "gsa_get_dp_stats", "gsa_get_dp_band_stats", "gsa_get_launch_counters", "gsa_hit_buffers", "gsa_seed_chunks", "gsa_hit_count", "gsa_export_hits", "gsa_import_hits", "gsa_finish_contig",
     "gsa_set_query", "gsa_rewind", "gsa_run_to", "gsa_seed_count", "gsa_get_seeds", "gsa_group_count", "gsa_get_groups", "gsa_get_blocks",
     "gsa_bwt_search_batch", "gsa_ksw2_batch", "gsa_gap_similarity_batch", "gsa_get_counters", "gsa_get_timings", "gsa_set_profiling", "gsa_bind_host_thread",
     "gsa_prefetch_contig", "gsa_prefetch_bundle", "gsa_cancel_prefetch", "gsa_get_wall_sums", "gsa_get_alloc_stats", "gsa_debug_buffers", "gsa_set_option", "gsa_host_register", "gsa_host_unregister",
@@ -702,6 +702,14 @@ class Aligner:
         """Sums since the context was made: striped DP jobs evaluated inside the diagonal band, of them certified, fallen back to the striped kernel."""
         st = np.zeros(3, np.uint64)
         self._ck(self.lib.gsa_get_dp_band_stats(self.ctx, _p(st, C.c_uint64)))
+        return st
+
+    def launch_counters(self) -> np.ndarray:
+        """The counters a context never resets: [0] look-back epoch, [1] fused-pass ticket, [2] DP granule epoch, [3] band tag, [4] chain-walk epoch, [5] chain-walk
+        ticket, [6] slices of the last sliced chain walk, [7] bytes of the boundary-granule buffer.  Raises GsaError ("ticket drift") if a device ticket word
+        differs from the host's value."""
+        st = np.zeros(8, np.uint64)
+        self._ck(self.lib.gsa_get_launch_counters(self.ctx, _p(st, C.c_uint64)))
         return st
 
     def _params(self, slen=15, ind=25, clr=200, alen=200, idy=70, sen=0, one=0) -> Params:

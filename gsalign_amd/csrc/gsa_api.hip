@@ -446,4 +446,25 @@ int gsa_get_counters(gsa_ctx *c, uint64_t counters[8]) { if (!c) return GSA_ERR_
 int gsa_get_timings(gsa_ctx *c, float ms[8]) { if (!c) return GSA_ERR_ARG; memcpy(ms, c->kernel_ms, sizeof(c->kernel_ms)); if (c->prof_seed && !c->profiling) ms[6] = (float)c->acc_seed_ms; return GSA_OK; }
 int gsa_get_dp_stats(gsa_ctx *c, uint64_t st[4]) { if (!c) return GSA_ERR_ARG; memcpy(st, c->dp_stats, sizeof(c->dp_stats)); return GSA_OK; }
 int gsa_get_seed_stats(gsa_ctx *c, uint64_t st[8]) { if (!c) return GSA_ERR_ARG; memcpy(st, c->dbg, sizeof(c->dbg)); return GSA_OK; }
+// The counters that are never reset, and the two device ticket words held against their host twins: a fused pass (a sliced chain walk) numbers its tiles
+// (slices) `device ticket - host value`, so one draw of difference makes every workgroup of the next launch wait out its bound for a tile that nobody holds.
+int gsa_get_launch_counters(gsa_ctx *c, uint64_t v[8])
+{
+	if (!c || !v) return GSA_ERR_ARG;
+	GSA_CHECK(c, hipSetDevice(c->device));
+	ctx_quiesce(c);
+	u32 lb_dev = 0, walk_dev = 0; uint64_t slices = 0;
+	GSA_CHECK(c, hipMemcpy(&lb_dev, c->d_mail.as<u32>() + M_TICKET, 4, hipMemcpyDeviceToHost));
+	if (c->w_j0.p) {
+		std::vector<unsigned long long> w(c->w_j0.cap / 8);
+		GSA_CHECK(c, hipMemcpy(w.data(), c->w_j0.p, w.size() * 8, hipMemcpyDeviceToHost));
+		walk_dev = (u32)w[0];
+		// (entry words: from word 4 on, one per slice; slice 0 has none)
+		if (c->walk_last_epoch) { slices = 1; for (size_t k = 5; k < w.size(); k++) slices += (u32)(w[k] >> 32) == c->walk_last_epoch; }
+	}
+	v[0] = c->lb_epoch; v[1] = c->lb_base; v[2] = c->dp_epoch; v[3] = c->band_epoch; v[4] = c->walk_epoch; v[5] = c->walk_ticket; v[6] = slices; v[7] = c->d_dp_bnd.cap;
+	if (lb_dev != c->lb_base) return gsa_fail(c, GSA_ERR_STATE, "ticket drift: the fused passes' device ticket is " + std::to_string(lb_dev) + ", the host counts " + std::to_string(c->lb_base));
+	if (c->w_j0.p && walk_dev != c->walk_ticket) return gsa_fail(c, GSA_ERR_STATE, "ticket drift: the chain walk's device ticket is " + std::to_string(walk_dev) + ", the host counts " + std::to_string(c->walk_ticket));
+	return GSA_OK;
+}
 } // extern "C"

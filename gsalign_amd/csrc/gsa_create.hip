@@ -501,6 +501,28 @@ int gsa_device_upload(int device, void *dst, const void *src, size_t bytes)
 	return GSA_OK;
 }
 
+// Test hooks "dbg_*": the launch counters that are never reset (DESIGN, "Counters that are never reset"), put where they come round, so that tests/test_gpu_wrap_states.py
+// runs the host lines that handle a wrap.  An epoch only moves forward and stays inside its width: the hook itself can make no stale word valid again.  A ticket takes
+// any value, on the host and on the device together.  Nothing of the context is in flight while either changes.
+static int dbg_set_launch_counter(gsa_ctx *c, const std::string &k, int64_t value)
+{
+	GSA_CHECK(c, hipSetDevice(c->device));
+	ctx_quiesce(c);
+	if ((k == "dbg_walk_epoch" || k == "dbg_walk_ticket") && !c->w_j0.p) return gsa_fail(c, GSA_ERR_STATE, k + ": no window chain has been walked in slices yet (the first one starts both counters at zero)");
+	u32 *epoch = k == "dbg_dp_epoch" ? &c->dp_epoch : k == "dbg_band_epoch" ? &c->band_epoch : k == "dbg_lb_epoch" ? &c->lb_epoch : k == "dbg_walk_epoch" ? &c->walk_epoch : nullptr;
+	if (epoch) {
+		const int64_t top = k == "dbg_dp_epoch" ? 0xffffll : k == "dbg_lb_epoch" ? 0x3fffffffll : 0xffffffffll;
+		if (value < (int64_t)*epoch || value > top) return gsa_fail(c, GSA_ERR_ARG, k + ": " + std::to_string((long long)*epoch) + " (the counter's value: it only moves forward) .. " + std::to_string((long long)top));
+		*epoch = (u32)value;
+		return GSA_OK;
+	}
+	if (value < 0 || value > 0xffffffffll) return gsa_fail(c, GSA_ERR_ARG, k + ": 0 .. 2^32 - 1");
+	const u32 v = (u32)value;
+	if (k == "dbg_lb_ticket") { GSA_CHECK(c, hipMemcpy(c->d_mail.as<u32>() + M_TICKET, &v, 4, hipMemcpyHostToDevice)); c->lb_base = v; }
+	else { GSA_CHECK(c, hipMemcpy(c->w_j0.p, &v, 4, hipMemcpyHostToDevice)); c->walk_ticket = v; }
+	return GSA_OK;
+}
+
 int gsa_set_option(gsa_ctx *c, const char *name, int64_t value)
 {
 	if (!c || !name) return GSA_ERR_ARG;
@@ -526,6 +548,7 @@ int gsa_set_option(gsa_ctx *c, const char *name, int64_t value)
 	else if (k == "sweep_shape") { if (value < -1 || value > 1) return gsa_fail(c, GSA_ERR_ARG, "sweep_shape: -1, 0 or 1"); c->opt.sweep_shape = (int)value; }
 	else if (k == "dp_safe") c->dp_safe = value != 0;                    // (test hook)
 	else if (k == "dp_fake_timeout") { if (!in(0, 1 << 20)) return gsa_fail(c, GSA_ERR_ARG, "dp_fake_timeout: >= 0"); c->dp_fake_timeout = (int)value; }    // (test hook)
+	else if (k == "dbg_dp_epoch" || k == "dbg_band_epoch" || k == "dbg_lb_epoch" || k == "dbg_walk_epoch" || k == "dbg_lb_ticket" || k == "dbg_walk_ticket") return dbg_set_launch_counter(c, k, value);    // (test hooks)
 	else return gsa_fail(c, GSA_ERR_ARG, "gsa_set_option: unknown option " + k);
 	return GSA_OK;
 }

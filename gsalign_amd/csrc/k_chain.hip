@@ -1056,10 +1056,14 @@ int stage2_chain(gsa_ctx *c)
 		ENS(unsigned long long, w_j0, (size_t)grid + 8);
 		if (c->w_j0.cap != cap0) { GSA_CHECK(c, hipMemsetAsync(c->w_j0.p, 0, c->w_j0.cap, st)); c->walk_ticket = 0; c->walk_epoch = 0; }
 		unsigned long long *words = c->w_j0.as<unsigned long long>();
-		hipLaunchKernelGGL(k_walk_chain, dim3(grid), dim3(WC_T), 0, st, na, candEx, clist, (const i32 *)c->d_flag2.as<i32>(), ws, (u32 *)words, c->walk_ticket, words + 4, c->walk_epoch + 1, mail + M_LBERR);
+		// (an entry word of tag 0 is one that was never written: the launch epoch is never 0.  When the counter comes round the entry words are cleared -- behind
+		//  every earlier launch on this stream -- and counting restarts at 1, like the epochs of the look-back words and the DP's granules; the ticket goes on)
+		u32 epoch = c->walk_epoch + 1;
+		if (epoch == 0) { GSA_CHECK(c, hipMemsetAsync(words + 4, 0, c->w_j0.cap - 32, st)); epoch = 1; }
+		hipLaunchKernelGGL(k_walk_chain, dim3(grid), dim3(WC_T), 0, st, na, candEx, clist, (const i32 *)c->d_flag2.as<i32>(), ws, (u32 *)words, c->walk_ticket, words + 4, epoch, mail + M_LBERR);
 		// (the slice numbering of every later launch depends on these two: they advance only for a launch that was accepted)
 		GSA_CHECK(c, hipGetLastError());
-		c->walk_epoch++; c->walk_ticket += grid;
+		c->walk_epoch = c->walk_last_epoch = epoch; c->walk_ticket += grid;
 	}
 	// C. outliers
 	ENS(unsigned long long, w_best, na + 1); ENS(unsigned long long, w_sum, na + 1); ENS(i32, w_n, na + 1);

@@ -201,6 +201,11 @@ void gsa_release_reserved(int device);
  *                    on the bitmap; 2 = always through the bytes (tests).  Results do not depend on it
  *   "seed_lhop"      test hook: entries of the seed kernel's long-hop table that a chunk may use (a power of two >= 16; 0 = all of them)
  *   "dp_safe", "dp_fake_timeout"   test hooks: one striped DP job per launch; the next n contigs report a stripe hand-off time-out once
+ *   "dbg_dp_epoch", "dbg_band_epoch", "dbg_lb_epoch", "dbg_walk_epoch"   test hooks: set a launch epoch (gsa_get_launch_counters [2], [3], [0], [4]) once the
+ *                    context's work in flight is through, so that the next launch is the one that comes round.  Forward only and inside the counter's width
+ *                    (16, 32, 30, 32 bits): GSA_ERR_ARG otherwise -- the hook can make no stale word valid again
+ *   "dbg_lb_ticket", "dbg_walk_ticket"   test hooks: set a ticket counter ([1], [5]), the host's value and the device word together; any 32-bit value.  The two
+ *                    "walk" hooks: GSA_ERR_STATE before the context's first sliced chain walk (which starts both counters at zero)
  * Unknown names and values outside an option's range (negative sizes, seed_budget 0, ...): GSA_ERR_ARG, nothing changed.
  * Until round 4 some of these were environment variables read by the library (GSA_SPLIT_MIN, GSA_BUNDLE_CONTIG, GSA_BUNDLE_CAP, GSA_SEED_BUDGET,
  * GSA_DP_LANE, GSA_SEED_MODE, GSA_NO_PDBITMAP, GSA_FORCE_WIDE, GSA_KMER_K, GSA_DP_SAFE, GSA_DP_FAKE_TIMEOUT, GSA_NO_BIND): the library ignores
@@ -758,6 +763,13 @@ int gsa_get_dp_stats(gsa_ctx *ctx, uint64_t stats[4]);
  * evaluated inside the diagonal band, [1] of them certified -- the band result is the full matrix's and stands --, [2] fallen back to the striped
  * kernel.  Waits for the context's work in flight. */
 int gsa_get_dp_band_stats(gsa_ctx *ctx, uint64_t stats[3]);
+/* The launch counters a context never resets ("Counters that are never reset"; a clone starts at zero): [0] epoch of the fused passes' look-back
+ * words (30 bits), [1] the host's value of their ticket counter (32 bits, modular), [2] epoch of the striped DP's boundary granules (16 bits), [3] tag of the
+ * band class's certificate flags, [4] epoch and [5] ticket value of the sliced window-chain walk, [6] slices the last sliced walk went through -- 1 + the entry
+ * words that carry its epoch, read back from the device; 0 if there was none --, [7] bytes held by the boundary-granule buffer (unchanged between two calls:
+ * the buffer was not replaced).  Waits for the context's work in flight and reads the two device ticket words: GSA_ERR_STATE ("ticket drift") if one differs
+ * from the host's value -- the next launch of that kind would wait out its bound. */
+int gsa_get_launch_counters(gsa_ctx *ctx, uint64_t v[8]);
 
 #ifdef __cplusplus
 }

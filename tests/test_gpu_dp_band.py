@@ -157,6 +157,79 @@ def test_mixed_batch_and_half_certified_pair(cx_index, want_of):
         a.close()
 
 
+def _long_related(rng, m, n):
+    """m x n near DP_BAND_MAX_LEN: 2 % substitutions, one 20-base insertion and one 20-base deletion (and the indel that n - m asks for, in the middle)"""
+    a = _rand(rng, m)
+    b = _subst(rng, a, 0.02)
+    b = np.concatenate([b[:m // 4], _rand(rng, 20), b[m // 4:3 * m // 4], b[3 * m // 4 + 20:]])
+    k = m // 2
+    b = np.concatenate([b[:k], _rand(rng, n - m), b[k:]]) if n >= m else np.concatenate([b[:k], b[k + m - n:]])
+    assert b.size == n
+    return ACGT[a].tobytes(), ACGT[b].tobytes()
+
+
+def _with_six_n(rng, pair):
+    s1, s2 = bytearray(pair[0]), bytearray(pair[1])
+    for q in rng.choice(len(s1), 3, replace=False): s1[q] = ord("N")
+    for q in rng.choice(len(s2), 3, replace=False): s2[q] = ord("N")
+    return bytes(s1), bytes(s2)
+
+
+def test_single_jobs_at_the_stated_limit(cx_index, want_of):
+    """The band's absolute 16-bit scores are argued for sides up to DP_BAND_MAX_LEN = 5000 (gsa_dp.h): 5000 x 5000 identical (certified); with 2 %
+    substitutions and two 20-base indels (at this length that optimum is already below UB), unrelated, and A...A against C...C -- every column a mismatch,
+    the lowest scores a window can hold --, which fall back; n - m at the largest value either way that the layout and the length limit admit at this
+    size, 2 % diverged and 0.5 % diverged (certified: walked back inside the band); one base past the length limit either way: refused, not counted.  One
+    job per batch: its partner half of the wavefront is empty."""
+    rng = np.random.default_rng(60)
+    B = 32
+    a = _rand(rng, 5000)
+    up, dn = _limits(4940, B)
+    assert (up, dn) == (60, -60)                  # (here the length limit binds first: 4940 + 60 = 5000 ...)
+    up2, _ = _limits(4937, B); _, dn2 = _limits(4938, B)
+    assert (up2, dn2) == (63, -62)                # (... and here the 128 diagonals do, with the longer side at 5000)
+    singles = [("identical", (ACGT[a].tobytes(), ACGT[a].tobytes()), True), ("related", _long_related(rng, 5000, 5000), True),
+               ("unrelated", (ACGT[a].tobytes(), ACGT[_rand(rng, 5000)].tobytes()), True), ("A against C", (b"A" * 5000, b"C" * 5000), True),
+               ("4940 x 5000", _long_related(rng, 4940, 4940 + up), True), ("5000 x 4940", _long_related(rng, 4940 - dn, 4940), True),
+               ("4937 x 5000", _long_related(rng, 4937, 4937 + up2), True), ("5000 x 4938", _long_related(rng, 4938 - dn2, 4938), True),
+               ("4940 x 5000, close", _with_delta(rng, 4940, up, rate=0.005), True), ("5000 x 4940, close", _with_delta(rng, 4940 - dn, dn, rate=0.005), True),
+               ("5001 x 5000", _long_related(rng, 5001, 5000), False), ("5000 x 5001", _long_related(rng, 5000, 5001), False)]
+    g = capi.Aligner(cx_index)
+    try:
+        g.set_option("dp_band", 2)
+        cert = {}
+        for what, pair, admitted in singles:
+            assert br.fits(len(pair[0]), len(pair[1]), B) == admitted, what
+            n_adm, n_cert = _run(g, [pair], want_of, B, what)
+            assert n_adm == int(admitted), what
+            cert[what] = n_cert
+        assert cert["identical"] == cert["4940 x 5000, close"] == cert["5000 x 4940, close"] == 1 and cert["unrelated"] == cert["A against C"] == 0, cert
+    finally:
+        g.close()
+
+
+def test_long_and_short_job_share_a_wavefront(cx_index, want_of):
+    """The band list pairs neighbours in (m + n) order: a batch of two jobs puts them into the two halves of ONE wavefront.  5000 x 5000 beside 65 x 66: the
+    short job's half goes on computing for thousands of steps past its end.  The same with six N in the long job only and in the short job only (the
+    kernel's "has an N" form is chosen per pair, not per job), and a 4999 x 5000 unrelated job that falls back beside a 66 x 65 identical one that is
+    certified."""
+    rng = np.random.default_rng(61)
+    B = 32
+    long_, short = _with_delta(rng, 5000, 0, rate=0.005), _with_delta(rng, 65, 1)      # (0.5 % substitutions: the long job is certified -- it walks back inside the band)
+    x = _rand(rng, 66)
+    batches = [("long + short", [long_, short]), ("N in the long job", [_with_six_n(rng, long_), short]), ("N in the short job", [long_, _with_six_n(rng, short)]),
+               ("one certified partner", [(ACGT[_rand(rng, 4999)].tobytes(), ACGT[_rand(rng, 5000)].tobytes()), (ACGT[x].tobytes(), ACGT[x[:65]].tobytes())])]
+    g = capi.Aligner(cx_index)
+    try:
+        g.set_option("dp_band", 2)
+        for what, P in batches:
+            assert [(len(p[0]), len(p[1])) for p in P] in ([(5000, 5000), (65, 66)], [(4999, 5000), (66, 65)])
+            n_adm, n_cert = _run(g, P, want_of, B, what)
+            assert n_adm == 2 and n_cert == (1 if what == "one certified partner" else 2), (what, n_adm, n_cert)
+    finally:
+        g.close()
+
+
 def test_default_rule_on_a_contig(oracle_built, tmp_path):
     """The benchmark's generator at 4 Mb, -alen 5000, default options: every stage-8 array equals the oracle's, jobs are certified, and as many fall
     back as the restated certificate says of the reference's gap alignments -- at B = 32 none."""
