@@ -29,6 +29,7 @@ EXPORTS = [
     "gsa_block_segs", "gsa_get_seg_timing", "gsa_extras_segs",
     "gsa_proj_open", "gsa_proj_close", "gsa_proj_clear", "gsa_project", "gsa_proj_fetch", "gsa_proj_merge", "gsa_get_proj_timing",
     "gsa_regions_set", "gsa_lift_regions", "gsa_get_region_timing", "gsa_extras_regions",
+    "gsa_qtrack_set", "gsa_query_track", "gsa_get_qtrack_timing", "gsa_extras_qtrack",
     "gsa_index_sizes", "gsa_build_index", "gsa_get_index_build_stats",
     "gsa_create_from_pac", "gsa_export_index_table",
     "gsa_build_index_opts", "gsa_get_index_build_stats2", "gsa_set_index_build_caps", "gsa_plan_index_batches",
@@ -161,6 +162,15 @@ class Tracks(C.Structure):
     _fields_ = [("n_win", C.c_int64), ("win", C.POINTER(TrackWin))]
 
 
+class QTrackWin(C.Structure):
+    """gsa_qtrack_win, 32 bytes (include/gsa_hip.h): one window of the query contig and what the counted blocks put into it."""
+    _fields_ = [("start", C.c_int32), ("len", C.c_int32), ("n_cov", C.c_uint32), ("n_multi", C.c_uint32), ("n_eq", C.c_uint32), ("n_x", C.c_uint32), ("n_ins", C.c_uint32), ("n_del", C.c_uint32)]
+
+
+class QTracks(C.Structure):
+    _fields_ = [("n_win", C.c_int64), ("win", C.POINTER(QTrackWin))]
+
+
 class Seg(C.Structure):
     """gsa_seg, 12 bytes (include/gsa_hip.h): one data line of a chain -- an aligned segment and the gap behind it in output order."""
     _fields_ = [("size", C.c_int32), ("dt", C.c_int32), ("dq", C.c_int32)]
@@ -178,6 +188,7 @@ class Segs(C.Structure):
 SEG_DT = np.dtype([("size", "<i4"), ("dt", "<i4"), ("dq", "<i4")])
 SEG_BLOCK_DT = np.dtype([("seg_off", "<i8"), ("n_seg", "<i4"), ("_pad", "<i4")])
 TRACK_WIN_DT = np.dtype([("chr", "<i4"), ("start", "<i4"), ("len", "<i4"), ("n_cov", "<u4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_del", "<u4"), ("n_ins", "<u4")])
+QTRACK_WIN_DT = np.dtype([("start", "<i4"), ("len", "<i4"), ("n_cov", "<u4"), ("n_multi", "<u4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_ins", "<u4"), ("n_del", "<u4")])
 LIFT_HIT_DT = np.dtype([("idx", "<i4"), ("qpos", "<i4"), ("block", "<i4"), ("cls", "u1"), ("rev", "u1"), ("n_cover", "<u2")])
 REGION_HIT_DT = np.dtype([("idx", "<i4"), ("block", "<i4"), ("off_lo", "<i4"), ("off_hi", "<i4"), ("q_lo", "<i4"), ("q_hi", "<i4"), ("n_eq", "<u4"), ("n_x", "<u4"), ("n_del", "<u4"), ("n_ins", "<u4"),
                           ("rev", "u1"), ("_pad0", "u1"), ("n_cover", "<u2"), ("_pad1", "<i4")])
@@ -186,6 +197,7 @@ BLOCK_CIGAR_DT = np.dtype([("cig_off", "<i8"), ("n_cig", "<i4"), ("n_eq", "<i4")
 CIGAR_LETTERS = "MIDNSHP=X"      # by BAM op code; the library writes I (1), D (2), = (7) and X (8)
 WANT_VARIANTS, WANT_CIGARS, WANT_CS, WANT_LIFT, WANT_TRACK, WANT_SEGS, WANT_PROJ = 1, 2, 4, 16, 32, 64, 128
 WANT_REGIONS = 256
+WANT_QTRACK = 512
 PROJ_NO_DUP = 1
 PROJ_LETTERS = "nACGTN-"         # by the low three bits of an accumulator word (0: uncovered)
 
@@ -211,6 +223,12 @@ def tracks_array(t: "Tracks"):
     """gsa_tracks -> TRACK_WIN_DT array (a copy)."""
     n = int(t.n_win)
     return np.ctypeslib.as_array(C.cast(t.win, C.POINTER(C.c_uint8)), shape=(n * TRACK_WIN_DT.itemsize,)).view(TRACK_WIN_DT).copy() if n else np.zeros(0, TRACK_WIN_DT)
+
+
+def qtracks_array(t: "QTracks"):
+    """gsa_qtracks -> QTRACK_WIN_DT array (a copy)."""
+    n = int(t.n_win)
+    return np.ctypeslib.as_array(C.cast(t.win, C.POINTER(C.c_uint8)), shape=(n * QTRACK_WIN_DT.itemsize,)).view(QTRACK_WIN_DT).copy() if n else np.zeros(0, QTRACK_WIN_DT)
 
 
 def segs_arrays(sg: "Segs"):
@@ -435,7 +453,7 @@ class DeviceContig:
             self.lib.gsa_device_free(self.device, C.c_void_p(self.ptr)); self.ptr = None
 
 
-def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False, track: bool = False, segs: bool = False, proj: bool = False, regions: bool = False) -> None:
+def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle: bool = True, prefetch: bool = True, variants: bool = False, cigars: bool = False, cs: bool = False, lift: bool = False, track: bool = False, segs: bool = False, proj: bool = False, regions: bool = False, qtrack: bool = False) -> None:
     """gsa_align_many: `contigs` (uint8 arrays, or DeviceContig objects -- all of one kind) on the given contexts, one host
     thread per context inside the library.  on_result(contig_index, Result) runs on the worker threads (the Result is valid
     during the call only).  in_order: hand the contigs out as listed (GSA_MANY_IN_ORDER) instead of longest first.
@@ -456,7 +474,9 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     proj=True: gsa_align_many_ex with GSA_WANT_PROJ (every aligner holds an accumulator: proj_open) -- the worker paints every contig behind the other passes; on_result
     gets nothing more.  Some aligners without an accumulator: -4; none with one: -1, like an unknown bit.
     regions=True: gsa_align_many_ex with GSA_WANT_REGIONS (every aligner holds regions: regions_set) -- on_result gets one more argument behind all of those, the contig's
-    RegionLifts (gsa_extras_regions; regions_array copies it out)."""
+    RegionLifts (gsa_extras_regions; regions_array copies it out).
+    qtrack=True: gsa_align_many_ex with GSA_WANT_QTRACK (every aligner holds a query-side window: qtrack_set) -- on_result gets one more argument behind all of those,
+    the contig's QTracks (gsa_extras_qtrack; qtracks_array copies it out)."""
     lib = aligners[0].lib
     n = len(contigs)
     ctxs = (C.c_void_p * len(aligners))(*[a.ctx for a in aligners])
@@ -464,12 +484,13 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
     qs = (C.c_char_p * n)(*[C.cast(c.ptr if on_dev else c.ctypes.data, C.c_char_p) for c in contigs])
     ql = (C.c_int32 * n)(*[int(c.size) for c in contigs])
     flags = (1 if in_order else 0) | (2 if on_dev else 0) | (0 if bundle else 8) | (0 if prefetch else 16)
-    if cigars or cs or lift or track or segs or proj or regions:
+    if cigars or cs or lift or track or segs or proj or regions or qtrack:
         lib.gsa_extras_cs.argtypes = [C.POINTER(Extras), C.POINTER(Cs)]
         lib.gsa_extras_lift.argtypes = [C.POINTER(Extras), C.POINTER(Lifts)]
         lib.gsa_extras_track.argtypes = [C.POINTER(Extras), C.POINTER(Tracks)]
         lib.gsa_extras_segs.argtypes = [C.POINTER(Extras), C.POINTER(Segs)]
         lib.gsa_extras_regions.argtypes = [C.POINTER(Extras), C.POINTER(RegionLifts)]
+        lib.gsa_extras_qtrack.argtypes = [C.POINTER(Extras), C.POINTER(QTracks)]
 
         def ex_cb(user, ci, res, ex):
             e = ex.contents
@@ -504,10 +525,16 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
                 if rc_r != 0:
                     return int(rc_r)
                 args += (rg,)
+            if qtrack:
+                qt = QTracks()
+                rc_q = lib.gsa_extras_qtrack(ex, C.byref(qt))
+                if rc_q != 0:
+                    return int(rc_q)
+                args += (qt,)
             return int((on_result(*args) if on_result else 0) or 0)
         cbx = RESULT_EX_FN(ex_cb)
         lib.gsa_align_many_ex.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, C.c_uint32, RESULT_EX_FN, C.c_void_p]
-        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0) | (WANT_TRACK if track else 0) | (WANT_SEGS if segs else 0) | (WANT_PROJ if proj else 0) | (WANT_REGIONS if regions else 0), cbx, None)
+        rc = lib.gsa_align_many_ex(ctxs, len(aligners), qs, ql, n, flags, (WANT_CIGARS if cigars or cs else 0) | (WANT_CS if cs else 0) | (WANT_VARIANTS if variants else 0) | (WANT_LIFT if lift else 0) | (WANT_TRACK if track else 0) | (WANT_SEGS if segs else 0) | (WANT_PROJ if proj else 0) | (WANT_REGIONS if regions else 0) | (WANT_QTRACK if qtrack else 0), cbx, None)
     elif variants:
         cbv = RESULT_VAR_FN(lambda user, ci, res, var: int((on_result(ci, res.contents, var.contents) if on_result else 0) or 0))
         lib.gsa_align_many_variants.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), C.c_int32, C.c_uint32, RESULT_VAR_FN, C.c_void_p]
@@ -518,7 +545,7 @@ def align_many(aligners, contigs, on_result=None, in_order: bool = False, bundle
         rc = lib.gsa_align_many(ctxs, len(aligners), qs, ql, n, flags, cb, None)
     if rc != 0:
         msgs = [lib.gsa_last_error(a.ctx).decode() for a in aligners]
-        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift or track or segs or proj or regions else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
+        raise GsaError(f"gsa_align_many{'_ex' if cigars or cs or lift or track or segs or proj or regions or qtrack else '_variants' if variants else ''} -> {rc}: {'; '.join(m for m in msgs if m)}")
 
 
 def _p(a, t):
@@ -879,6 +906,25 @@ class Aligner:
         self.lib.gsa_ref_track.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Tracks)]
         self._ck(self.lib.gsa_ref_track(self.ctx, C.c_int32(k), C.byref(t)))
         return tracks_array(t)
+
+    def qtrack_set(self, window: int) -> None:
+        """gsa_qtrack_set: the window length W of this context's per-window query track from now on; 0 clears it.  Independent of track_set."""
+        self.lib.gsa_qtrack_set.argtypes = [C.c_void_p, C.c_int32]
+        self._ck(self.lib.gsa_qtrack_set(self.ctx, C.c_int32(int(window))))
+
+    def qtrack(self, k: int = 0):
+        """gsa_query_track on the stage-8 result this context holds (contig k of a bundle): QTRACK_WIN_DT array, ascending by start."""
+        t = QTracks()
+        self.lib.gsa_query_track.argtypes = [C.c_void_p, C.c_int32, C.POINTER(QTracks)]
+        self._ck(self.lib.gsa_query_track(self.ctx, C.c_int32(k), C.byref(t)))
+        return qtracks_array(t)
+
+    def qtrack_timing(self):
+        """(host wall ms inside gsa_query_track on this context since it was created, number of calls)."""
+        ms, n = C.c_double(0), C.c_int64(0)
+        self.lib.gsa_get_qtrack_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        self._ck(self.lib.gsa_get_qtrack_timing(self.ctx, C.byref(ms), C.byref(n)))
+        return ms.value, int(n.value)
 
     def track_timing(self):
         """(host wall ms inside gsa_ref_track on this context since it was created, number of calls)."""

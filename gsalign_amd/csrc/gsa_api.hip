@@ -36,9 +36,10 @@ static int rewind_to_hits(gsa_ctx *c)
 	return stage1_restore_pdbm(c);
 }
 
-// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip, k_proj.hip, k_regions.hip) ask of the context before they run; `who`: the export, for the messages;
-// need: the pass reads the positions of gsa_lift_set / the window of gsa_track_set / paints into the accumulator of gsa_proj_open / reads the regions of gsa_regions_set
-enum { NEED_POSITIONS = 1, NEED_WINDOW = 2, NEED_ACC = 4, NEED_REGIONS = 8 };
+// What the passes over a stage-8 result (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip, k_proj.hip, k_regions.hip, k_qtrack.hip) ask of the context before they run; `who`: the export, for the messages;
+// need: the pass reads the positions of gsa_lift_set / the window of gsa_track_set / paints into the accumulator of gsa_proj_open / reads the regions of gsa_regions_set /
+// the query-side window of gsa_qtrack_set
+enum { NEED_POSITIONS = 1, NEED_WINDOW = 2, NEED_ACC = 4, NEED_REGIONS = 8, NEED_QWINDOW = 16 };
 static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, unsigned need = 0)
 {
 	const std::string w(who);
@@ -50,6 +51,7 @@ static int result_pass_ready(gsa_ctx *c, int32_t k, const char *who, unsigned ne
 	if ((need & NEED_WINDOW) && c->track_w <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no window (gsa_track_set first)");
 	if ((need & NEED_ACC) && !c->proj) return gsa_fail(c, GSA_ERR_STATE, w + ": no accumulator (gsa_proj_open first)");
 	if ((need & NEED_REGIONS) && c->reg_n <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no regions (gsa_regions_set first)");
+	if ((need & NEED_QWINDOW) && c->qtrack_w <= 0) return gsa_fail(c, GSA_ERR_STATE, w + ": no window (gsa_qtrack_set first)");
 	GSA_CHECK(c, hipSetDevice(c->device));
 	return GSA_OK;
 }
@@ -79,6 +81,7 @@ int cs_call(gsa_ctx *c, int32_t k, gsa_cs *out, gsa_cigars *cig) { return result
 int lift_call(gsa_ctx *c, int32_t k, gsa_lifts *out) { return result_pass(c, k, "gsa_lift", NEED_POSITIONS, PASS_LIFT, out, [&] { return lift_positions(c, k, out); }); }
 int regions_call(gsa_ctx *c, int32_t k, gsa_region_lifts *out) { return result_pass(c, k, "gsa_lift_regions", NEED_REGIONS, PASS_REG, out, [&] { return lift_regions(c, k, out); }); }
 int track_call(gsa_ctx *c, int32_t k, gsa_tracks *out) { return result_pass(c, k, "gsa_ref_track", NEED_WINDOW, PASS_TRACK, out, [&] { return ref_track(c, k, out); }); }
+int qtrack_call(gsa_ctx *c, int32_t k, gsa_qtracks *out) { return result_pass(c, k, "gsa_query_track", NEED_QWINDOW, PASS_QTRACK, out, [&] { return query_track(c, k, out); }); }
 int segs_call(gsa_ctx *c, int32_t k, gsa_segs *out, gsa_cigars *cig, const gsa_cigars *have)
 {
 	if (c && out && cig) *cig = gsa_cigars();
@@ -317,6 +320,15 @@ int gsa_track_set(gsa_ctx *c, int32_t window)
 }
 int gsa_ref_track(gsa_ctx *c, int32_t k, gsa_tracks *out) { return track_call(c, k, out); }
 int gsa_get_track_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_TRACK, ms_sum, n_calls); }
+int gsa_qtrack_set(gsa_ctx *c, int32_t window)
+{
+	if (!c) return GSA_ERR_ARG;
+	if (window < 0) return gsa_fail(c, GSA_ERR_ARG, "gsa_qtrack_set: the window is negative");
+	c->qtrack_w = window;      // (the windows of a contig are fewer than its bases: no limit to check here; the dense array stays, all zero, whatever the window)
+	return GSA_OK;
+}
+int gsa_query_track(gsa_ctx *c, int32_t k, gsa_qtracks *out) { return qtrack_call(c, k, out); }
+int gsa_get_qtrack_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_QTRACK, ms_sum, n_calls); }
 
 int gsa_block_segs(gsa_ctx *c, int32_t k, gsa_segs *out) { return segs_call(c, k, out, nullptr, nullptr); }
 int gsa_get_seg_timing(gsa_ctx *c, double *ms_sum, int64_t *n_calls) { return pass_timing(c, PASS_SEG, ms_sum, n_calls); }

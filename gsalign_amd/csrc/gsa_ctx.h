@@ -98,7 +98,7 @@ struct Options {
 struct ProjAcc { u32 *words = nullptr; i64 G = 0; int device = 0; std::atomic<int> refs{1}; std::atomic<int> dirty{0}; };
 
 // the passes over a stage-8 result, as gsa_ctx::pass_stat counts them
-enum Pass { PASS_VAR, PASS_CIG, PASS_CS, PASS_LIFT, PASS_TRACK, PASS_SEG, PASS_PROJ, PASS_REG, PASS_N };
+enum Pass { PASS_VAR, PASS_CIG, PASS_CS, PASS_LIFT, PASS_TRACK, PASS_SEG, PASS_PROJ, PASS_REG, PASS_QTRACK, PASS_N };
 struct PassStat { double ms_sum = 0; long long calls = 0; };
 
 struct gsa_ctx {
@@ -284,6 +284,12 @@ struct gsa_ctx {
 	// records}, the hits ----
 	DevBuf d_rgpos, d_rgpre, d_rgwg, d_rghit, p_rghdr, p_rghit;
 	i64 reg_n = 0;                                       // regions held (0: none; a clone starts without)
+	// ---- per-window query track (k_qtrack.hip): the counted blocks' span table, both interval lists (depth >= 1 with its sentinel, then depth >= 2), the dense per-window
+	// counts {n_eq, n_x, n_ins, n_del} of ONE contig (all zero between calls: EMIT clears what it reads), per-workgroup sums + error counters, the windows, the gap records
+	// that hold a block's cut with their answers; pinned: span table, intervals, header {windows, records without a job, columns outside their record}, the windows, the cuts ----
+	DevBuf d_qblk, d_qiv, d_qbin, d_qwg, d_qout, d_qcut, p_qblk, p_qiv, p_qhdr, p_qout, p_qcut;
+	i32 qtrack_w = 0;                                    // window length (0: none; a clone starts without); independent of track_w
+	size_t qtrack_zeroed = 0; bool qtrack_dirty = false; // entries of d_qbin known to be zero; a call that failed between COUNT and EMIT left counts behind
 	// what growing buffers cost this context (dev_ensure / pin_ensure: hipMalloc, hipHostMalloc, the frees and the quiesce in front of them) -- gsa_get_alloc_stats
 	double alloc_ms = 0; long long alloc_n = 0, alloc_bytes = 0;
 };
@@ -303,11 +309,11 @@ struct gsa_ctx {
 	X(e_id) X(e_rec) X(e_list) X(e_off1) X(e_off2) X(e_opsoff) X(e_nops) X(e_ops) X(e_rev) X(r_head) X(f_early) X(r_orig) X(r_tmp_orig) \
 	X(j_frag) X(j_opsoff) X(j_nops) X(d_ops) X(j_cells) X(d_alnoff) X(bl_alnlen) X(bl_score) X(d_bblk) X(d_dp_arena) \
 	X(d_vblk) X(d_vcnt) X(d_vwg) X(d_var) X(d_cblk) X(d_cout) X(d_ccnt) X(d_cwg) X(d_cpre) X(d_crun) X(d_cops) X(d_crpos) X(d_cqpos) X(d_slen) X(d_swg) X(d_spre) X(d_sout) X(d_cs) \
-	X(d_lpos) X(d_lblk) X(d_lpick) X(d_lwg) X(d_lhit) X(d_tblk) X(d_tiv) X(d_tbin) X(d_twg) X(d_tout) X(d_sgwg) X(d_sgpre) X(d_sgbnd) X(d_sgout) X(d_sgseg) X(d_pblk) X(d_ppre) X(d_pwg) X(d_pstage) X(d_rgpos) X(d_rgpre) X(d_rgwg) X(d_rghit) \
+	X(d_lpos) X(d_lblk) X(d_lpick) X(d_lwg) X(d_lhit) X(d_tblk) X(d_tiv) X(d_tbin) X(d_twg) X(d_tout) X(d_sgwg) X(d_sgpre) X(d_sgbnd) X(d_sgout) X(d_sgseg) X(d_pblk) X(d_ppre) X(d_pwg) X(d_pstage) X(d_rgpos) X(d_rgpre) X(d_rgwg) X(d_rghit) X(d_qblk) X(d_qiv) X(d_qbin) X(d_qwg) X(d_qout) X(d_qcut) \
 	X(leaf[0]) X(leaf[1]) X(leaf[2]) X(leaf[3]) X(leaf[4]) X(leaf[5]) X(leaf[6]) X(leaf[7]) X(leaf[8])
 #define GSA_PINBUFS(X) \
 	X(p_frags) X(p_tail) X(p_leaf) X(p_blk) X(p_dp) X(p_sj) X(p_sj_early) X(p_jpatch) X(p_early) X(qs[0].p_bndtab) X(qs[1].p_bndtab) X(p_bblk) X(p_ba0) \
-	X(p_vblk) X(p_vhdr) X(p_var) X(p_cblk) X(p_chdr) X(p_cout) X(p_cops) X(p_shdr) X(p_sout) X(p_cs) X(p_lblk) X(p_lhdr) X(p_lhit) X(p_tblk) X(p_tiv) X(p_thdr) X(p_tout) X(p_sghdr) X(p_sgout) X(p_sgseg) X(p_pblk) X(p_phdr) X(p_pstage) X(p_rghdr) X(p_rghit)
+	X(p_vblk) X(p_vhdr) X(p_var) X(p_cblk) X(p_chdr) X(p_cout) X(p_cops) X(p_shdr) X(p_sout) X(p_cs) X(p_lblk) X(p_lhdr) X(p_lhit) X(p_tblk) X(p_tiv) X(p_thdr) X(p_tout) X(p_sghdr) X(p_sgout) X(p_sgseg) X(p_pblk) X(p_phdr) X(p_pstage) X(p_rghdr) X(p_rghit) X(p_qblk) X(p_qiv) X(p_qhdr) X(p_qout) X(p_qcut)
 
 // A buffer is about to be freed: nothing of this context may still use it -- not only the main stream: the early striped DP launch runs on
 // stream_aux[0] beside stages 3-7 and shares direction / boundary / ticket buffers with the late launch, strings and record copies run on
@@ -388,6 +394,7 @@ int lift_positions(gsa_ctx *c, i32 k, gsa_lifts *out);      // k_lift.hip  (the 
 int block_segs(gsa_ctx *c, i32 k, gsa_segs *out, gsa_cigars *cig_out = nullptr, const gsa_cigars *have = nullptr);   // k_segs.hip  (the chain triples of every block: the CIGAR pass with positions -- or, have: the one that has just run for this contig -- then four launches per run / per segment)
 int ref_track(gsa_ctx *c, i32 k, gsa_tracks *out);          // k_track.hip  (the per-window track of the stage-8 result of contig k at the window of gsa_track_set)
 int lift_regions(gsa_ctx *c, i32 k, gsa_region_lifts *out);   // k_regions.hip  (the regions of gsa_regions_set through the stage-8 result of contig k)
+int query_track(gsa_ctx *c, i32 k, gsa_qtracks *out);       // k_qtrack.hip  (the per-window track of the stage-8 result of contig k over the query contig, at the window of gsa_qtrack_set)
 int project_blocks(gsa_ctx *c, i32 k, gsa_proj_stat *out);   // k_proj.hip  (the blocks of contig k painted into the context's accumulator)
 int proj_open(gsa_ctx *c, gsa_ctx *share, u32 flags);       // k_proj.hip  (gsa_proj_open / close / clear / fetch / merge behind their argument checks)
 int proj_release(gsa_ctx *c);                               // k_proj.hip  (gsa_proj_close, gsa_destroy: the context's reference dropped, the array freed with the last one)
@@ -407,6 +414,7 @@ int set_query_bundle(gsa_ctx *c, const char *const *query, const int32_t *qlen, 
 // (the exports gsa_align_many_ex calls too; all of them: result_pass in gsa_api.hip)
 int lift_call(gsa_ctx *c, int32_t k, gsa_lifts *out);   // gsa_api.hip  (gsa_lift)
 int track_call(gsa_ctx *c, int32_t k, gsa_tracks *out);   // gsa_api.hip  (gsa_ref_track)
+int qtrack_call(gsa_ctx *c, int32_t k, gsa_qtracks *out);   // gsa_api.hip  (gsa_query_track)
 int proj_call(gsa_ctx *c, int32_t k, gsa_proj_stat *out);   // gsa_api.hip  (gsa_project)
 int regions_call(gsa_ctx *c, int32_t k, gsa_region_lifts *out);   // gsa_api.hip  (gsa_lift_regions)
 int segs_call(gsa_ctx *c, int32_t k, gsa_segs *out, gsa_cigars *cig, const gsa_cigars *have);   // gsa_api.hip  (gsa_block_segs; cig / have: as block_segs, for gsa_align_many_ex)

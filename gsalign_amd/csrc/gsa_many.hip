@@ -91,7 +91,7 @@ static std::vector<std::vector<int32_t> > plan_units(const std::vector<int32_t> 
 }
 
 // what the callback of gsa_align_many_ex is handed: the public gsa_extras at the head, the answers of later passes behind it
-struct ExtrasFull { gsa_extras ex; const gsa_cs *cs; const gsa_lifts *lift; const gsa_tracks *track; const gsa_segs *segs; const gsa_region_lifts *regions; };
+struct ExtrasFull { gsa_extras ex; const gsa_cs *cs; const gsa_lifts *lift; const gsa_tracks *track; const gsa_segs *segs; const gsa_region_lifts *regions; const gsa_qtracks *qtrack; };
 // gsa_align_many, gsa_align_many_variants and gsa_align_many_ex: one loop, three ways to hand a finished contig over (the passes asked for run first, in the worker that finished it)
 struct ManySink { gsa_result_fn on_result = nullptr; gsa_result_var_fn on_var = nullptr; gsa_result_ex_fn on_ex = nullptr; uint32_t want = 0; };
 static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n, uint32_t flags, const ManySink &sk, void *user)
@@ -101,7 +101,7 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 	auto deliver = [&](gsa_ctx *c, int32_t k, int32_t ci, const gsa_result *res) -> int {
 		if (sk.on_var) { gsa_variants var; const int rcv = gsa_call_variants(c, k, &var); return rcv != GSA_OK ? rcv : sk.on_var(user, ci, res, &var); }
 		if (sk.on_ex) {
-			gsa_variants var; gsa_cigars cig; gsa_cs cs; gsa_lifts lift; gsa_tracks trk; gsa_segs sg; gsa_region_lifts rg; ExtrasFull full = { { nullptr, nullptr }, nullptr, nullptr, nullptr, nullptr, nullptr }; gsa_extras &ex = full.ex;
+			gsa_variants var; gsa_cigars cig; gsa_cs cs; gsa_lifts lift; gsa_tracks trk; gsa_segs sg; gsa_region_lifts rg; gsa_qtracks qtk; ExtrasFull full = { { nullptr, nullptr }, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr }; gsa_extras &ex = full.ex;
 			// (the variants are copied by no one before the CIGAR pass runs, and both live in buffers of their own: the second pass leaves the first one's answer alone)
 			if (sk.want & GSA_WANT_VARIANTS) { const int rcv = gsa_call_variants(c, k, &var); if (rcv != GSA_OK) return rcv; ex.var = &var; }
 			// (the cs pass runs the CIGAR walk itself, into the CIGAR pass's buffers: its ops are the ones handed out, no second walk)
@@ -112,6 +112,7 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 			if (sk.want & GSA_WANT_LIFT) { const int rcl = lift_call(c, k, &lift); if (rcl != GSA_OK) return rcl; full.lift = &lift; }
 			if (sk.want & GSA_WANT_TRACK) { const int rct = track_call(c, k, &trk); if (rct != GSA_OK) return rct; full.track = &trk; }
 			if (sk.want & GSA_WANT_REGIONS) { const int rcr = regions_call(c, k, &rg); if (rcr != GSA_OK) return rcr; full.regions = &rg; }
+			if (sk.want & GSA_WANT_QTRACK) { const int rcq = qtrack_call(c, k, &qtk); if (rcq != GSA_OK) return rcq; full.qtrack = &qtk; }
 			// (the projection paints into the contexts' accumulator and hands the callback nothing)
 			if (sk.want & GSA_WANT_PROJ) { const int rcp = proj_call(c, k, nullptr); if (rcp != GSA_OK) return rcp; }
 			return sk.on_ex(user, ci, res, &ex);
@@ -124,9 +125,10 @@ static int align_many_impl(gsa_ctx *const *ctx, int32_t n_ctx, const char *const
 	const bool dev_q = (flags & GSA_MANY_DEVICE) != 0;
 	if (dev_q) for (int k = 1; k < n_ctx; k++) if (ctx[k]->device != ctx[0]->device) return gsa_fail(ctx[0], GSA_ERR_ARG, "GSA_MANY_DEVICE: the contexts must share one GPU (the contigs live in its memory)");
 	// (what a pass reads must be set on every context: one without would fail its first contig with the others under way)
-	static const struct { uint32_t want; bool (*set)(const gsa_ctx *); const char *msg; } needs[3] = {
+	static const struct { uint32_t want; bool (*set)(const gsa_ctx *); const char *msg; } needs[4] = {
 		{ GSA_WANT_LIFT, [](const gsa_ctx *c) { return c->lift_n > 0; }, "gsa_align_many_ex (GSA_WANT_LIFT): the context holds no positions (gsa_lift_set first)" },
 		{ GSA_WANT_TRACK, [](const gsa_ctx *c) { return c->track_w > 0; }, "gsa_align_many_ex (GSA_WANT_TRACK): the context holds no window (gsa_track_set first)" },
+		{ GSA_WANT_QTRACK, [](const gsa_ctx *c) { return c->qtrack_w > 0; }, "gsa_align_many_ex (GSA_WANT_QTRACK): the context holds no query-side window (gsa_qtrack_set first)" },
 		{ GSA_WANT_REGIONS, [](const gsa_ctx *c) { return c->reg_n > 0; }, "gsa_align_many_ex (GSA_WANT_REGIONS): the context holds no regions (gsa_regions_set first)" } };
 	for (const auto &nd : needs) if (sk.want & nd.want) for (int k = 0; k < n_ctx; k++) if (!nd.set(ctx[k])) return gsa_fail(ctx[k], GSA_ERR_STATE, nd.msg);
 	// (GSA_WANT_PROJ: the bit exists for callers that have opened an accumulator.  Where NO context of ctx[] holds one it is refused like any bit the call does not know --
@@ -239,16 +241,17 @@ int gsa_align_many_variants(gsa_ctx *const *ctx, int32_t n_ctx, const char *cons
 }
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n, uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user)
 {
-	if (!on_result || (want & ~(uint32_t)(GSA_WANT_VARIANTS | GSA_WANT_CIGARS | GSA_WANT_CS | GSA_WANT_LIFT | GSA_WANT_TRACK | GSA_WANT_SEGS | GSA_WANT_PROJ | GSA_WANT_REGIONS))) return GSA_ERR_ARG;
+	if (!on_result || (want & ~(uint32_t)(GSA_WANT_VARIANTS | GSA_WANT_CIGARS | GSA_WANT_CS | GSA_WANT_LIFT | GSA_WANT_TRACK | GSA_WANT_SEGS | GSA_WANT_PROJ | GSA_WANT_REGIONS | GSA_WANT_QTRACK))) return GSA_ERR_ARG;
 	ManySink sk; sk.on_ex = on_result; sk.want = want;
 	return align_many_impl(ctx, n_ctx, query, qlen, n, flags, sk, user);
 }
 
 // the answers behind the gsa_extras a gsa_align_many_ex callback was handed: cs strings (GSA_WANT_CS), lifted positions (GSA_WANT_LIFT), chain segments (GSA_WANT_SEGS),
-// the per-window track (GSA_WANT_TRACK), lifted regions (GSA_WANT_REGIONS)
+// the per-window track (GSA_WANT_TRACK), lifted regions (GSA_WANT_REGIONS), the per-window query track (GSA_WANT_QTRACK)
 int gsa_extras_cs(const gsa_extras *ex, gsa_cs *out) { return extras_get(ex, &ExtrasFull::cs, out); }
 int gsa_extras_lift(const gsa_extras *ex, gsa_lifts *out) { return extras_get(ex, &ExtrasFull::lift, out); }
 int gsa_extras_segs(const gsa_extras *ex, gsa_segs *out) { return extras_get(ex, &ExtrasFull::segs, out); }
 int gsa_extras_track(const gsa_extras *ex, gsa_tracks *out) { return extras_get(ex, &ExtrasFull::track, out); }
 int gsa_extras_regions(const gsa_extras *ex, gsa_region_lifts *out) { return extras_get(ex, &ExtrasFull::regions, out); }
+int gsa_extras_qtrack(const gsa_extras *ex, gsa_qtracks *out) { return extras_get(ex, &ExtrasFull::qtrack, out); }
 } // extern "C"

@@ -1,5 +1,5 @@
 // gsalign_amd/csrc/gsa_walk.h -- what the passes over a stage-8 result share (k_variants.hip, k_cigar.hip, k_cs.hip, k_lift.hip, k_track.hip, k_segs.hip, k_proj.hip,
-// k_regions.hip): the inputs of a record walk and the op string of a gap record, one step of a gap's columns by a lane and by a wavefront, the "=" / "X"
+// k_regions.hip, k_qtrack.hip): the inputs of a record walk and the op string of a gap record, one step of a gap's columns by a lane and by a wavefront, the "=" / "X"
 // rule, the search for the block of a work item, the two levels of the exclusive scan, the span table of the passes that ask where a block lies on the reference (its
 // host builder, the cover search, the record of a text position), and on the host the blocks of one contig of the result.  What a pass makes of a record -- which
 // records it walks, what a column means -- stays with the pass.
@@ -118,6 +118,33 @@ __device__ __forceinline__ void wg_count(bool hit, i32 *s_w, i64 *wg)
 	if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = tot;
 	__syncthreads();
 	if (threadIdx.x == 0) wg[blockIdx.x] = (i64)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// n into field f of v[4] (by selects: a run-time index would put the array into scratch)
+__device__ __forceinline__ void win_add(u32 v[4], int f, u32 n)
+{
+#pragma unroll
+	for (int k = 0; k < 4; k++) v[k] += k == f ? n : 0u;
+}
+
+// The lanes' counts v[4] for window key (-1: none) into a dense array of four counts per window (k_track.hip, k_qtrack.hip): reduced over runs of equal keys in
+// neighbouring lanes first (a run starts where the key differs from the lane below; equal keys further apart simply make two runs), then one atomicAdd per
+// (run, field).  The whole wavefront calls it.
+__device__ __forceinline__ void win_flush(u32 *bin, i64 nbin, i32 key, u32 v[4])
+{
+	const int lane = threadIdx.x & 63;
+	const i32 pk = __shfl_up(key, 1);
+	const bool head = lane == 0 || pk != key;
+	const unsigned long long hm = __ballot(head);
+	if (__ballot(key >= 0) == 0ull) return;
+	const unsigned long long above = lane == 63 ? 0ull : (hm >> (lane + 1));
+	const int nh = above ? lane + __ffsll((long long)above) : 64;      // the next run's first lane
+	for (int d = 1; d < 64; d <<= 1)
+#pragma unroll
+		for (int f = 0; f < 4; f++) { const u32 x = __shfl_down(v[f], d); if (lane + d < nh) v[f] += x; }
+	if (head && key >= 0 && (i64)key < nbin)
+#pragma unroll
+		for (int f = 0; f < 4; f++) if (v[f]) atomicAdd(bin + 4 * (i64)key + f, v[f]);
 }
 
 // the second level of a scan that leaves nothing but the total behind (a template: every pass's file is a translation unit of its own)

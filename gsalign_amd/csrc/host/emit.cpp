@@ -97,6 +97,7 @@ template struct RawArr<uint32_t>;
 template struct RawArr<gsa_lift_hit>;
 template struct RawArr<gsa_region_hit>;
 template struct RawArr<gsa_track_win>;
+template struct RawArr<gsa_qtrack_win>;
 template struct RawArr<gsa_seg_block>;
 template struct RawArr<gsa_seg>;
 void ContigResult::assign(const gsa_result &r, bool summary_mode)
@@ -953,6 +954,115 @@ void Emitter::track_text(bool first, const QueryContig &q, const gsa_track_win *
 		w = put_int(w, (long long)t.n_x); *w++ = '\t';
 		w = put_int(w, (long long)t.n_del); *w++ = '\t';
 		w = put_int(w, (long long)t.n_ins); *w++ = '\n';
+		o.n = (size_t)(w - o.p);
+		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
+	}
+	if (o.n) sink(std::move(o));
+}
+
+// ---- per-window query track -----------------------------------------------------------------------------------------------------------------
+void gsah_qtrack(const HostIndex &ix, const ContigResult &r, int32_t qlen, int32_t W, std::vector<gsa_qtrack_win> &win)
+{
+	win.clear();
+	if (r.summary || W <= 0 || qlen <= 0) return;      // (a summary result holds neither records nor strings)
+	const size_t nchr = ix.chr_len.size();
+	const int64_t nwin = ((int64_t)qlen + W - 1) / W;
+	std::vector<uint32_t> bin;                    // {n_eq, n_x, n_ins, n_del} per window
+	std::vector<std::pair<int64_t, int> > ev;     // the counted blocks' kept query intervals as (position, -1 / +1)
+	for (size_t bi = 0; bi < r.blocks.size(); bi++) {
+		const gsa_block &b = r.blocks[bi];
+		if (b.bdup != 0 || b.n_frag <= 0 || b.chr < 0 || (size_t)b.chr >= nchr) continue;
+		const gsa_frag first = r.frag(b.frag_off), last = r.frag(b.frag_off + b.n_frag - 1);
+		const int64_t start = first.rpos, end = last.rpos + last.rlen - extension(ix, b, last);
+		if (end <= start) continue;
+		if (bin.empty()) bin.assign((size_t)nwin * 4, 0u);
+		std::atomic<int64_t> q1((int64_t)last.qpos + last.qlen);      // behind the last kept query base: the one record that holds the cut (if any) says where
+		// a range of the block's records: the counts of one window are gathered while the walk stays in it and added when it leaves (several threads may meet in a window)
+		auto piece = [&](size_t fb, size_t fe) {
+			int64_t cur = -1; uint32_t cnt[4] = { 0, 0, 0, 0 };
+			auto flush = [&] {
+				if (cur >= 0 && cur < nwin) for (int f = 0; f < 4; f++) if (cnt[f]) __atomic_fetch_add(&bin[(size_t)cur * 4 + f], cnt[f], __ATOMIC_RELAXED);
+				cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+			};
+			// n columns of field f charged to the query bases q, q + 1, ... (step 0: all to q): split over the windows by arithmetic
+			auto run = [&](int64_t q, int64_t n, int f, int step) {
+				while (n > 0) {
+					const int64_t j = q / W, m = step ? std::min<int64_t>(n, (j + 1) * W - q) : n;
+					if (j != cur) { flush(); cur = j; }
+					cnt[f] += (uint32_t)m; q += m; n -= m;
+				}
+			};
+			for (size_t k = fb; k < fe; k++) {
+				const gsa_frag f = r.frag(b.frag_off + (int64_t)k);
+				if (f.rpos > end) break;      // (the kept columns are a prefix of the block's)
+				if (f.bseed) {
+					const int64_t n = std::min<int64_t>(f.qlen, end - f.rpos);
+					run(f.qpos, n, 0, 1);
+					if (n < f.qlen) q1.store(f.qpos + n);
+					continue;
+				}
+				const char *x1 = r.aln1.data() + f.aln_off, *x2 = r.aln2.data() + f.aln_off;
+				int64_t rp = f.rpos, qp = f.qpos;
+				for (int c = 0; c < f.aln_len; c++) {
+					if (x1[c] == '-') {      // an inserted query base: kept with the reference base consumed last in front of it
+						if (rp > end) { q1.store(qp); break; }
+						run(qp, 1, 2, 1); qp++;
+						continue;
+					}
+					if (rp >= end) { q1.store(qp); break; }
+					if (x2[c] == '-') { if (qp > 0) run(qp - 1, 1, 3, 0); }      // (a deleted base belongs to the query base consumed last)
+					else { run(qp, 1, column_class(x1[c], x2[c]) == GSA_CIGAR_EQ ? 0 : 1, 1); qp++; }
+					rp++;
+				}
+			}
+			flush();
+		};
+		if ((size_t)b.n_frag * 16 >= par_min_bytes()) par_ranges((size_t)b.n_frag, (size_t)1 << 13, piece); else piece(0, (size_t)b.n_frag);
+		const int64_t q0 = first.qpos, qe = std::min<int64_t>(q1.load(), qlen);
+		if (qe > q0 && q0 >= 0) { ev.push_back({ q0, 1 }); ev.push_back({ qe, -1 }); }
+	}
+	if (ev.empty()) return;
+	// a sweep over the sorted ends (an end in front of a start at the same position): every stretch of one depth goes to the windows it touches
+	std::sort(ev.begin(), ev.end());
+	struct Acc { int64_t j; uint32_t cov, multi; };
+	std::vector<Acc> acc;                         // the windows under some block, ascending
+	int d = 0;
+	for (size_t i = 0; i + 1 < ev.size(); i++) {
+		d += ev[i].second;
+		int64_t s = ev[i].first; const int64_t e = ev[i + 1].first;
+		while (d >= 1 && s < e) {
+			const int64_t j = s / W, m = std::min<int64_t>(e, (j + 1) * W) - s;
+			if (acc.empty() || acc.back().j != j) acc.push_back(Acc{ j, 0u, 0u });
+			acc.back().cov += (uint32_t)m; if (d >= 2) acc.back().multi += (uint32_t)m;
+			s += m;
+		}
+	}
+	for (const auto &a : acc) {
+		const int64_t lo = a.j * W, hi = std::min<int64_t>(lo + W, qlen);
+		const uint32_t *c = &bin[(size_t)a.j * 4];
+		gsa_qtrack_win w; w.start = (int32_t)lo; w.len = (int32_t)(hi - lo); w.n_cov = a.cov; w.n_multi = a.multi; w.n_eq = c[0]; w.n_x = c[1]; w.n_ins = c[2]; w.n_del = c[3];
+		win.push_back(w);
+	}
+}
+
+// <prefix>.qtrack.tsv: one line per window -- query name, BED-style start and end inside the contig, and the six counts
+void Emitter::qtrack_text(bool first, const QueryContig &q, const gsa_qtrack_win *win, int64_t n_win, const std::function<void(OutBuf &&)> &sink) const
+{
+	OutBuf o;
+	if (first) o.append("#query\tstart\tend\tcovered\tmulti\tmatch\tmismatch\tinserted\tdeleted\n");
+	for (int64_t i = 0; i < n_win; i++) {
+		const gsa_qtrack_win &t = win[i];
+		o.reserve(o.n + q.name.size() + 128);
+		char *w = o.p + o.n;
+		memcpy(w, q.name.data(), q.name.size()); w += q.name.size(); *w++ = '\t';
+		w = put_int(w, t.start); *w++ = '\t';
+		w = put_int(w, (long long)t.start + t.len); *w++ = '\t';
+		w = put_int(w, (long long)t.n_cov); *w++ = '\t';
+		w = put_int(w, (long long)t.n_multi); *w++ = '\t';
+		w = put_int(w, (long long)t.n_eq); *w++ = '\t';
+		w = put_int(w, (long long)t.n_x); *w++ = '\t';
+		w = put_int(w, (long long)t.n_ins); *w++ = '\t';
+		w = put_int(w, (long long)t.n_del); *w++ = '\n';
 		o.n = (size_t)(w - o.p);
 		if (o.n >= ((size_t)4 << 20)) { OutBuf out = std::move(o); o = OutBuf(); sink(std::move(out)); }
 	}

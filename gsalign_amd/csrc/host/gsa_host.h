@@ -139,6 +139,10 @@ void gsah_lift_regions(const HostIndex &ix, const ContigResult &r, const int64_t
 // coverage, column classes, the insertion rule -- from the records and the two gapped strings.  The comparator of gsa_ref_track, and the track of a host that holds a
 // gsa_result and no GPU context.  win: one record per window with n_cov > 0, ascending by (chr, start); empty for a summary result or W <= 0.
 void gsah_track(const HostIndex &ix, const ContigResult &r, int32_t W, std::vector<gsa_track_win> &win);
+// The per-window track of a finished contig of qlen bases over the QUERY contig at window length W, by the contract of gsa_query_track (gsa_hip.h): counted blocks, the
+// trim carried over from the reference side, column classes, the deletion rule, union and multi coverage -- from the records and the two gapped strings.  The
+// comparator of gsa_query_track.  win: one record per window with n_cov > 0, ascending by start; empty for a summary result, W <= 0 or qlen <= 0.
+void gsah_qtrack(const HostIndex &ix, const ContigResult &r, int32_t qlen, int32_t W, std::vector<gsa_qtrack_win> &win);
 
 // A finished contig painted into the caller's accumulator words[0 .. G) by the contract of gsa_project (gsa_hip.h): trimmed coverage, the CIGAR pass's columns, key | code,
 // the maximum stays (taken atomically: several threads may meet in a word) -- from the records, the two gapped strings and, for the seeds, the query contig seq (NULL: a
@@ -182,6 +186,9 @@ struct Emitter {
 	// <prefix>.track.tsv (-track W): one line per window of gsa_ref_track / gsah_track, in the order given -- reference name, start and end (BED-style: 0-based, half-open,
 	// inside the sequence), query name, covered, match, mismatch, deleted, inserted; first: the header line in front
 	void track_text(bool first, const QueryContig &q, const gsa_track_win *win, int64_t n_win, const std::function<void(OutBuf &&)> &sink) const;
+	// <prefix>.qtrack.tsv (-qtrack W): one line per window of gsa_query_track / gsah_qtrack, in the order given -- query name, start and end (BED-style) inside the
+	// contig, covered, multi, match, mismatch, inserted, deleted; first: the header line in front
+	void qtrack_text(bool first, const QueryContig &q, const gsa_qtrack_win *win, int64_t n_win, const std::function<void(OutBuf &&)> &sink) const;
 	// <prefix>.chain (-chain): a UCSC chain per block, blocks selected like OutputMAF's (-unique), from the block's UNTRIMMED triples blk / seg (gsa_block_segs; NULL: computed
 	// here, gsah_block_segs) cut by iExtension (gsah_segs_trim) --
 	//   chain <score> <tName> <tSize> + <tStart> <tEnd> <qName> <qSize> <+|-> <qStart> <qEnd> <id> / "size dt dq" per triple but the last / "size" / an empty line

@@ -368,6 +368,27 @@ long long gsah_c_track(const char *index_prefix, const gsa_result *res, int32_t 
 	return (long long)w.size();
 }
 
+// gsah_qtrack through the C API: the per-window track of one finished contig of qlen bases over the query contig at window length W, on the host -- what
+// gsa_query_track gives.  out[cap]; returns the number of windows (call with cap = 0 to size `out`), < 0 on error.  The index of the last prefix stays loaded, behind a
+// lock, as in gsah_c_lift (only its sequence table is read: the trim).
+long long gsah_c_qtrack(const char *index_prefix, const gsa_result *res, int32_t qlen, int32_t W, gsa_qtrack_win *out, long long cap)
+{
+	static std::mutex mu; static std::string have; static HostIndex *idx = nullptr;
+	std::lock_guard<std::mutex> lock(mu);
+	if (!index_prefix || !res || W < 1 || qlen < 0 || (cap > 0 && !out)) return -1;
+	if (!idx || have != index_prefix) {
+		delete idx; idx = new HostIndex; have.clear(); std::string e;
+		if (!gsah_load_index(index_prefix, *idx, e)) { delete idx; idx = nullptr; return -2; }
+		have = index_prefix;
+	}
+	ContigResult cr; cr.assign(*res);
+	std::vector<gsa_qtrack_win> w;
+	gsah_qtrack(*idx, cr, qlen, W, w);
+	const size_t m = std::min<size_t>(w.size(), cap > 0 ? (size_t)cap : 0);
+	if (m) memcpy(out, w.data(), m * sizeof(gsa_qtrack_win));
+	return (long long)w.size();
+}
+
 // gsah_project through the C API: one finished contig painted into words[n_words] (n_words = G of the index), on the host -- what gsa_project paints.  seq: the query
 // contig (its bases stand in the seeds' columns).  stat may be NULL.  Returns 0, < 0 on error (-3: n_words is not the reference's length).  The index of the last
 // prefix stays loaded, behind a lock, as in gsah_c_lift (only its sequence table is read).

@@ -10,7 +10,8 @@
 // listed in FILE (name, 1-based position; a VCF works as it is) are carried through every contig's alignment on the GPU (gsa_lift) and written to <prefix>.lift.tsv.  -liftbed FILE: the reference
 // intervals of FILE (BED) are carried through every contig's alignment on the GPU (gsa_lift_regions) and written with their class counts to <prefix>.regions.tsv.
 // -track W: the reference sequences in windows of W bases -- covered, matching, mismatching, deleted and inserted bases per window and query contig, computed on the GPU
-// (gsa_ref_track) and written to <prefix>.track.tsv.  -proj: the query in reference coordinates -- one character per reference base over all
+// (gsa_ref_track) and written to <prefix>.track.tsv.  -qtrack W: the mirror image -- every query contig in windows of W bases: covered, multiply covered, matching,
+// mismatching, inserted and deleted bases per window (gsa_query_track), written to <prefix>.qtrack.tsv.  -proj: the query in reference coordinates -- one character per reference base over all
 // query contigs, painted on the GPU into one accumulator per device (gsa_project) and written to <prefix>.proj.fa.  -chain: every alignment as a UCSC chain (for liftOver, CrossMap, bcftools +liftover), its size / dt / dq lines
 // computed on the GPU (gsa_block_segs) and written to <prefix>.chain.
 // The contigs go through gsa_align_many (the per-contig loop of GSAlign.cpp:483-548).  Round 5: a GPU worker thread only COPIES a finished
@@ -60,6 +61,7 @@ static void usage(const char *prog, int t, const gsa_params &p, int fmt)
 	fprintf(stderr, "         -lift  FILE    lift the reference positions of FILE (tab-separated: sequence name, 1-based position; '#' lines skipped, a VCF works) to the query on the GPU (gsa_lift): <prefix>.lift.tsv\n");
 	fprintf(stderr, "         -proj          project the query onto the reference on the GPU (gsa_project): one character per reference base over all query sequences -- the aligned query base, '-' deleted, 'n' not aligned: <prefix>.proj.fa\n");
 	fprintf(stderr, "         -track INT     per window of INT reference bases and query sequence: covered / matching / mismatching / deleted / inserted bases, computed on the GPU (gsa_ref_track): <prefix>.track.tsv\n");
+	fprintf(stderr, "         -qtrack INT    per window of INT bases of every query sequence: covered / multiply covered / matching / mismatching / inserted / deleted bases, computed on the GPU (gsa_query_track): <prefix>.qtrack.tsv\n");
 	fprintf(stderr, "         -liftbed FILE  lift the reference intervals of FILE (BED: sequence name, 0-based start, end, optional name) to the query on the GPU (gsa_lift_regions), with match / mismatch / deleted / inserted counts: <prefix>.regions.tsv\n");
 	fprintf(stderr, "         -chain         write every alignment as a UCSC chain (liftOver, CrossMap), its segments computed on the GPU (gsa_block_segs): <prefix>.chain [false]\n");
 	fprintf(stderr, "         -gpuvar        identify the sequence variants on the GPU (gsa_call_variants) instead of on the host [false]\n");
@@ -184,6 +186,7 @@ int main(int argc, char *argv[])
 	std::vector<int> gpus;
 	const char *index_prefix = NULL, *ref_fa = NULL, *query_fa = NULL, *out_prefix = NULL, *gnuplot_arg = NULL, *lift_file = NULL, *bed_file = NULL;
 	int track_w = 0;      // -track W (0: no track)
+	int qtrack_w = 0;     // -qtrack W (0: no query track)
 	if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(argv[0], threads, prm, fmt); return 0; }
 	if (strcmp(argv[1], "index") == 0) {
 		bool on_gpu = false; int device = 0, a = 2;
@@ -222,6 +225,11 @@ int main(int argc, char *argv[])
 			char *end = NULL; const long long w = strtoll(argv[++i], &end, 10);
 			if (end == argv[i] || *end || w < 1 || w > 0x7fffffffll) { fprintf(stderr, "-track: the window must be a number of bases from 1 to 2147483647 (got %s)\n", argv[i]); return 1; }
 			track_w = (int)w;
+		}
+		else if (a == "-qtrack" && i + 1 < argc) {
+			char *end = NULL; const long long w = strtoll(argv[++i], &end, 10);
+			if (end == argv[i] || *end || w < 1 || w > 0x7fffffffll) { fprintf(stderr, "-qtrack: the window must be a number of bases from 1 to 2147483647 (got %s)\n", argv[i]); return 1; }
+			qtrack_w = (int)w;
 		}
 		else if (a == "-gpuindex") gpuindex = true;
 		else if (a == "-memindex") memindex = true;
@@ -365,6 +373,7 @@ int main(int argc, char *argv[])
 	}
 	// (the positions go to every context, the clones included: a clone starts without)
 	if (track_w) for (gsa_ctx *c : ctxs) if (gsa_track_set(c, track_w) != GSA_OK) { fprintf(stderr, "-track: %s\n", gsa_last_error(c)); return 2; }
+	if (qtrack_w) for (gsa_ctx *c : ctxs) if (gsa_qtrack_set(c, qtrack_w) != GSA_OK) { fprintf(stderr, "-qtrack: %s\n", gsa_last_error(c)); return 2; }
 	// -proj: one accumulator per GPU -- its first context opens it, the clones on that GPU paint into the same array (without the duplicates under -unique)
 	if (want_proj) for (size_t i = 0; i < ctxs.size(); i++) {
 		gsa_ctx *first = i < gpus.size() ? NULL : ctxs[(i - gpus.size()) % gpus.size()];
@@ -375,7 +384,7 @@ int main(int argc, char *argv[])
 	if (want_regions) for (gsa_ctx *c : ctxs) if (gsa_regions_set(c, bed_beg.data(), bed_end.data(), (int64_t)bed_beg.size()) != GSA_OK) { fprintf(stderr, "-liftbed: %s\n", gsa_last_error(c)); return 2; }
 
 	const std::string regn = std::string(out_prefix) + ".regions.tsv";
-	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv", trackn = std::string(out_prefix) + ".track.tsv", chainn = std::string(out_prefix) + ".chain", projn = std::string(out_prefix) + ".proj.fa";
+	const std::string maf = std::string(out_prefix) + (fmt == 3 ? ".paf" : ".maf"), aln = std::string(out_prefix) + ".aln", vcfn = std::string(out_prefix) + ".vcf", liftn = std::string(out_prefix) + ".lift.tsv", trackn = std::string(out_prefix) + ".track.tsv", qtrackn = std::string(out_prefix) + ".qtrack.tsv", chainn = std::string(out_prefix) + ".chain", projn = std::string(out_prefix) + ".proj.fa";
 	Emitter em; em.idx = &idx; em.allow_dup = allow_dup;
 	long long n_aln = 0, tot_len = 0, tot_match = 0, n_dup = 0;
 	fprintf(stderr, "Step2. Sequence analysis for all query chromosomes\n");
@@ -392,10 +401,11 @@ int main(int argc, char *argv[])
 		std::vector<RawArr<gsa_cs_block> > sblk; std::vector<RawArr<char> > sbytes; bool want_cs = false;      // -cs: the contig's cs strings as gsa_block_cs left them
 		std::vector<RawArr<gsa_lift_hit> > lift; bool want_lift = false;      // -lift: the contig's hits as gsa_lift left them
 		std::vector<RawArr<gsa_region_hit> > regions; bool want_regions = false;      // -liftbed: the contig's hits as gsa_lift_regions left them
+		std::vector<RawArr<gsa_qtrack_win> > qtrack; bool want_qtrack = false;   // -qtrack: the contig's windows as gsa_query_track left them
 		std::vector<RawArr<gsa_track_win> > track; bool want_track = false;   // -track: the contig's windows as gsa_ref_track left them
 		std::vector<RawArr<gsa_seg_block> > gblk; std::vector<RawArr<gsa_seg> > gseg; bool want_segs = false;   // -chain: the contig's triples as gsa_block_segs left them
 	} sink;
-	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size()); sink.sblk.resize(qs.size()); sink.sbytes.resize(qs.size()); sink.want_cs = want_cs; sink.want_cig = fmt == 3; sink.lift.resize(qs.size()); sink.want_lift = want_lift; sink.track.resize(qs.size()); sink.want_track = track_w != 0;
+	sink.res.resize(qs.size()); sink.ready.assign(qs.size(), 0); sink.var.resize(qs.size()); sink.cblk.resize(qs.size()); sink.cops.resize(qs.size()); sink.sblk.resize(qs.size()); sink.sbytes.resize(qs.size()); sink.want_cs = want_cs; sink.want_cig = fmt == 3; sink.lift.resize(qs.size()); sink.want_lift = want_lift; sink.track.resize(qs.size()); sink.want_track = track_w != 0; sink.qtrack.resize(qs.size()); sink.want_qtrack = qtrack_w != 0;
 	sink.gblk.resize(qs.size()); sink.gseg.resize(qs.size()); sink.want_segs = want_chain; sink.regions.resize(qs.size()); sink.want_regions = want_regions;
 	const bool var_on_gpu = gpuvar && vcf;          // (-no_vcf: nobody reads the variants)
 	// the MAF file: created by the first contig that has alignments ("w" for contig 0, "a" afterwards: tools.cpp:158-163 -- a run whose
@@ -407,7 +417,8 @@ int main(int argc, char *argv[])
 	if (want_lift && !(lift_fp = fopen(liftn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", liftn.c_str(), strerror(errno)); }
 	FILE *reg_fp = NULL;
 	if (want_regions && !(reg_fp = fopen(regn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", regn.c_str(), strerror(errno)); }
-	FILE *track_fp = NULL;
+	FILE *track_fp = NULL, *qtrack_fp = NULL;
+	if (qtrack_w && !(qtrack_fp = fopen(qtrackn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", qtrackn.c_str(), strerror(errno)); }
 	if (track_w && !(track_fp = fopen(trackn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", trackn.c_str(), strerror(errno)); }
 	FILE *chain_fp = NULL; int64_t chain_id = 0;
 	if (want_chain && !(chain_fp = fopen(chainn.c_str(), "w"))) { out_failed = true; fprintf(stderr, "Error! cannot open [%s] for writing: %s\n", chainn.c_str(), strerror(errno)); }
@@ -419,6 +430,10 @@ int main(int argc, char *argv[])
 			if (sink.gblk[ci].size() != cr.blocks.size()) { if (!cr.blocks.empty()) { out_failed = true; fprintf(stderr, "Error! %d blocks, chain segments of %d\n", (int)cr.blocks.size(), (int)sink.gblk[ci].size()); } }
 			else if (!cr.blocks.empty()) em.chain_text(qs[ci], cr, sink.gblk[ci].data(), sink.gseg[ci].data(), &chain_id, [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, chain_fp) != o.n) out_failed = true; });
 			sink.gblk[ci].reset(); sink.gseg[ci].reset();
+		}
+		if (qtrack_fp) {      // (query contigs in file order, a contig's windows ascending; a contig without alignments has none)
+			em.qtrack_text(ci == 0, qs[ci], sink.qtrack[ci].data(), (int64_t)sink.qtrack[ci].size(), [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, qtrack_fp) != o.n) out_failed = true; });
+			sink.qtrack[ci].reset();
 		}
 		if (track_fp) {      // (query contigs in file order, a contig's windows ascending; a contig without alignments has none)
 			em.track_text(ci == 0, qs[ci], sink.track[ci].data(), (int64_t)sink.track[ci].size(), [&](OutBuf &&o) { if (o.n && fwrite(o.p, 1, o.n, track_fp) != o.n) out_failed = true; });
@@ -535,6 +550,11 @@ int main(int argc, char *argv[])
 			if (gsa_extras_segs(ex, &sg) != GSA_OK) return 1;
 			sk.gblk[(size_t)ci].assign(sg.blk, (size_t)sg.n_blocks); sk.gseg[(size_t)ci].assign(sg.seg, (size_t)sg.n_segs);
 		}
+		if (sk.want_qtrack) {
+			gsa_qtracks qt;
+			if (gsa_extras_qtrack(ex, &qt) != GSA_OK) return 1;
+			sk.qtrack[(size_t)ci].assign(qt.win, (size_t)qt.n_win);
+		}
 		if (sk.want_track) {
 			gsa_tracks tk;
 			if (gsa_extras_track(ex, &tk) != GSA_OK) return 1;
@@ -547,7 +567,7 @@ int main(int argc, char *argv[])
 	};
 	if (timing && var_on_gpu) for (gsa_ctx *c : ctxs) (void)gsa_set_profiling(c, 8);      // (the variant passes' device time, for the GSA_VARIANT_PASS line)
 	const double ta = now_s(); t_at_align = ta - T0;
-	const int rc_many = (fmt == 3 || want_lift || track_w || want_chain || want_proj || want_regions) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u) | (want_chain ? GSA_WANT_SEGS : 0u) | (want_proj ? GSA_WANT_PROJ : 0u) | (want_regions ? GSA_WANT_REGIONS : 0u), on_result_ex, &sink)
+	const int rc_many = (fmt == 3 || want_lift || track_w || qtrack_w || want_chain || want_proj || want_regions) ? gsa_align_many_ex(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, (fmt == 3 ? GSA_WANT_CIGARS : 0u) | (want_cs ? GSA_WANT_CS : 0u) | (var_on_gpu ? GSA_WANT_VARIANTS : 0u) | (want_lift ? GSA_WANT_LIFT : 0u) | (track_w ? GSA_WANT_TRACK : 0u) | (want_chain ? GSA_WANT_SEGS : 0u) | (want_proj ? GSA_WANT_PROJ : 0u) | (want_regions ? GSA_WANT_REGIONS : 0u) | (qtrack_w ? GSA_WANT_QTRACK : 0u), on_result_ex, &sink)
 	                  : var_on_gpu ? gsa_align_many_variants(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result_var, &sink)
 	                               : gsa_align_many(ctxs.data(), (int32_t)ctxs.size(), qptr.data(), qlen.data(), (int32_t)qs.size(), 0, on_result, &sink);
 	t_align = now_s() - ta;
@@ -558,6 +578,7 @@ int main(int argc, char *argv[])
 	double lift_ms = 0;       // -lift: the same of gsa_lift
 	double regions_ms = 0;    // -liftbed: the same of gsa_lift_regions
 	double track_ms = 0;      // -track: the same of gsa_ref_track
+	double qtrack_ms = 0;     // -qtrack: the same of gsa_query_track
 	double chain_ms = 0;      // -chain: the same of gsa_block_segs (its CIGAR walk included unless -cs ran it)
 	double proj_ms = 0;       // -proj: the same of gsa_project, plus the fetch, merge and write below
 	double var_dev_ms = 0; long long var_dev_n = 0;      // -gpuvar: device time of the variant passes (hipEvents), all contexts
@@ -569,6 +590,7 @@ int main(int argc, char *argv[])
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_lift_timing(c, &cm, &cn) == GSA_OK) lift_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_region_timing(c, &cm, &cn) == GSA_OK) regions_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_track_timing(c, &cm, &cn) == GSA_OK) track_ms += cm; }
+		{ double cm = 0; int64_t cn = 0; if (gsa_get_qtrack_timing(c, &cm, &cn) == GSA_OK) qtrack_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_seg_timing(c, &cm, &cn) == GSA_OK) chain_ms += cm; }
 		{ double cm = 0; int64_t cn = 0; if (gsa_get_proj_timing(c, &cm, &cn) == GSA_OK) proj_ms += cm; }
 		double vm = 0; int64_t vn = 0; if (gsa_get_variant_timing(c, &vm, &vn) == GSA_OK) { var_dev_ms += vm; var_dev_n += vn; }
@@ -607,6 +629,7 @@ int main(int argc, char *argv[])
 	if (lift_fp) { if (ferror(lift_fp) | fclose(lift_fp)) out_failed = true; lift_fp = NULL; }
 	if (reg_fp) { if (ferror(reg_fp) | fclose(reg_fp)) out_failed = true; reg_fp = NULL; }
 	if (track_fp) { if (ferror(track_fp) | fclose(track_fp)) out_failed = true; track_fp = NULL; }
+	if (qtrack_fp) { if (ferror(qtrack_fp) | fclose(qtrack_fp)) out_failed = true; qtrack_fp = NULL; }
 	if (chain_fp) { if (ferror(chain_fp) | fclose(chain_fp)) out_failed = true; chain_fp = NULL; }
 	double maf_write_s = 0; unsigned long long maf_bytes = 0;
 	// (the MAF writer still has its queue to write -- ~1 s at human scale: the VCF is sorted, formatted and written beside it, the MAF file is closed behind)
@@ -646,10 +669,10 @@ int main(int argc, char *argv[])
 		fprintf(stderr, "GSA_TIMING {\"total_s\": %.3f, \"index_build_s\": %.3f, \"index_load_s\": %.3f, \"gsa_create_s\": %.3f, \"query_load_s\": %.3f, \"query_pin_s\": %.3f, \"align_many_s\": %.3f, \"cigar_s\": %.3f, "
 		        "\"result_copy_s_sum\": %.3f, \"maf_format_s\": %.3f, \"variants_s\": %.3f, \"output_drain_after_align_s\": %.3f, \"maf_write_s\": %.3f, \"maf_bytes\": %llu, "
 		        "\"vcf_s\": %.3f, \"vcf_write_s\": %.3f, \"vcf_bytes\": %llu, \"destroy_s\": %.3f, \"host_threads\": %d, \"contexts\": %d, \"query_bp\": %lld, \"contigs\": %d, \"gbp_per_s_excl_index_build\": %.4f, "
-		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"regions_s\": %.3f, \"proj_s\": %.3f, \"chain_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
+		        "\"ref_unpack_s\": %.3f, \"reserve_s\": %.3f, \"reserve_wait_s\": %.3f, \"unpack_wait_s\": %.3f, \"align_starts_at_s\": %.3f, \"ctx_wall_ms_sum\": [%.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f, %.1f], \"alloc_ms_sum\": %.1f, \"alloc_n\": %lld, \"alloc_gb\": %.2f, \"ref_parse_s\": %.3f, \"create_from_pac_s\": %.3f, \"qtrack_s\": %.3f, \"regions_s\": %.3f, \"proj_s\": %.3f, \"chain_s\": %.3f, \"track_s\": %.3f, \"lift_s\": %.3f, \"cs_s\": %.3f}\n",
 		        total, t_build, t_index, t_create, t_query, t_pin, t_align, cigar_ms / 1e3, t_copy, t_maf_fmt, t_var, t_drain, maf_write_s, maf_bytes, t_vcf, vcf_write_s, vcf_bytes, t_destroy,
 		        HostPool::global().threads(), (int)ctxs.size(), qbp, (int)qs.size(), (double)qbp / (total - t_build) / 1e9,
-		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, regions_ms / 1e3, proj_ms / 1e3, chain_ms / 1e3, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
+		        t_unpack, t_reserve, t_reserve_wait, t_unpack_wait, t_at_align, wall_sum[0], wall_sum[1], wall_sum[2], wall_sum[3], wall_sum[4], wall_sum[5], wall_sum[6], wall_sum[7], wall_sum[8], alloc_ms, alloc_n, (double)alloc_bytes / 1e9, t_ref_parse, t_from_pac, qtrack_ms / 1e3, regions_ms / 1e3, proj_ms / 1e3, chain_ms / 1e3, track_ms / 1e3, lift_ms / 1e3, cs_ms / 1e3);      // (cs_s stays the line's last field)
 	}
 	if (timing && var_on_gpu) fprintf(stderr, "GSA_VARIANT_PASS {\"device_ms_sum\": %.3f, \"passes\": %lld, \"query_bp\": %lld}\n", var_dev_ms, var_dev_n, [&] { long long b = 0; for (const QueryContig &q : qs) b += (long long)q.seq.size(); return b; }());
 	// (everything is on disk and the GPU is released: the process ends here -- unwinding 20 GB of host buffers and the HIP runtime's own

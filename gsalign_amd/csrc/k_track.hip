@@ -61,31 +61,9 @@ __device__ __forceinline__ i32 trk_win(const TrkIn &a, const TrkBlk &b, i64 t)
 	return w < a.nbin ? (i32)w : -1;
 }
 
-// n into field f of v[4] (by selects: a run-time index would put the array into scratch)
-__device__ __forceinline__ void trk_add(u32 v[4], int f, u32 n)
-{
-#pragma unroll
-	for (int k = 0; k < 4; k++) v[k] += k == f ? n : 0u;
-}
-
-// The lanes' counts v[4] for window key (-1: none) into the dense array: reduced over runs of equal keys in neighbouring lanes first (a run starts where the key
-// differs from the lane below; equal keys further apart simply make two runs), then one atomicAdd per (run, field).  The whole wavefront calls it.
-__device__ __forceinline__ void trk_flush(const TrkIn &a, i32 key, u32 v[4])
-{
-	const int lane = threadIdx.x & 63;
-	const i32 pk = __shfl_up(key, 1);
-	const bool head = lane == 0 || pk != key;
-	const unsigned long long hm = __ballot(head);
-	if (__ballot(key >= 0) == 0ull) return;
-	const unsigned long long above = lane == 63 ? 0ull : (hm >> (lane + 1));
-	const int nh = above ? lane + __ffsll((long long)above) : 64;      // the next run's first lane
-	for (int d = 1; d < 64; d <<= 1)
-#pragma unroll
-		for (int f = 0; f < 4; f++) { const u32 x = __shfl_down(v[f], d); if (lane + d < nh) v[f] += x; }
-	if (head && key >= 0 && (i64)key < a.nbin)
-#pragma unroll
-		for (int f = 0; f < 4; f++) if (v[f]) atomicAdd(a.bin + 4 * (i64)key + f, v[f]);
-}
+// (the lanes' counts into the dense array: gsa_walk.h's win_add / win_flush, which k_qtrack.hip shares)
+__device__ __forceinline__ void trk_add(u32 v[4], int f, u32 n) { win_add(v, f, n); }
+__device__ __forceinline__ void trk_flush(const TrkIn &a, i32 key, u32 v[4]) { win_flush(a.bin, a.nbin, key, v); }
 
 // what COUNT knows of a record before it looks at a column: the covered text positions it may charge [t0, t1] (for a gap with rpos - 1 in front, where a leading
 // insertion belongs) and their two windows

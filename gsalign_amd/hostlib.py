@@ -334,6 +334,29 @@ def track(index_prefix, seq, result, W: int):
     return T
 
 
+def qtrack(index_prefix, seq, result, W: int):
+    """gsah_c_qtrack: the per-window track of one finished contig over the QUERY contig at window length W, on the host, from the records and the gapped strings -- what
+    Aligner.qtrack computes on the GPU, by the contract of gsa_query_track (include/gsa_hip.h).  result: a capi.Result, a dump dict (oracle layout) or a result dict of
+    capi.Aligner.  seq: the contig (uint8 array or bytes; only its length is read -- or the length itself); the index under index_prefix supplies the reference
+    sequences' lengths (the trim).  Returns a QTRACK_WIN_DT array: one record per window with n_cov > 0, ascending by start."""
+    keep: list = []
+    if isinstance(result, dict):
+        result = result_from_dump(result, keep) if "b_score" in result else result_from_arrays(result, keep)
+    qlen = int(seq) if isinstance(seq, (int, np.integer)) else len(seq)
+    lib = load()
+    lib.gsah_c_qtrack.restype = C.c_longlong
+    lib.gsah_c_qtrack.argtypes = [C.c_char_p, C.POINTER(capi.Result), C.c_int32, C.c_int32, C.c_void_p, C.c_longlong]
+    n = lib.gsah_c_qtrack(index_prefix.encode(), C.byref(result), qlen, int(W), None, 0)
+    if n < 0:
+        raise RuntimeError(f"gsah_c_qtrack -> {n}")
+    T = np.zeros(int(n), capi.QTRACK_WIN_DT)
+    if n:
+        n2 = lib.gsah_c_qtrack(index_prefix.encode(), C.byref(result), qlen, int(W), C.c_void_p(T.ctypes.data), int(T.size))
+        if n2 != n:
+            raise RuntimeError(f"gsah_c_qtrack -> {n2} after {n}")
+    return T
+
+
 def project(index_prefix, seq, result, words, flags: int = 0):
     """gsah_c_project: one finished contig painted into the caller's accumulator `words` (a C-contiguous uint32 array of G entries, changed in place: the maximum stays)
     on the host, from the records, the gapped strings and the query contig seq (uint8 array or bytes: its bases stand in the seeds' columns) -- what Aligner.project

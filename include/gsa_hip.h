@@ -472,11 +472,43 @@ int gsa_track_set(gsa_ctx *ctx, int32_t window);
 /* The track of the stage-8 result the context holds.  Validity, call order, k and the error codes are those of gsa_block_cigars; without a window GSA_ERR_STATE.  No counted
  * block: n_win = 0.  The counts are uint32_t: when the reference bases plus the query bases that the counted blocks of contig k span (last record's end minus first record's
  * start on either side, summed over the blocks -- no count can exceed the sum of the columns, which this bounds) exceed 2^32 - 1, GSA_ERR_LIMIT before any launch.  The answer
- * lives in buffers of its own: the four other passes return what they returned before, and so does this call after one of them.  Memory is owned by the context and valid
+ * lives in buffers of its own: the eight other passes return what they returned before, and so does this call after one of them.  Memory is owned by the context and valid
  * until the next call on it; the windows come home in one copy into pinned memory. */
 int gsa_ref_track(gsa_ctx *ctx, int32_t k, gsa_tracks *out);
 /* measurement: host wall time the calling threads spent inside gsa_ref_track on this context since it was created, and the number of calls.  Always on. */
 int gsa_get_track_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
+
+/* ---- per-window query track ----------------------------------------------------------
+ * The mirror image of the reference track: which parts of the QUERY contig align at all, how diverged are they, where are the holes, and which stretches align to two
+ * places at once?  Query contig k of qlen bases is cut into ceil(qlen / W) windows, window j covers [j W, min((j + 1) W, qlen)).  Positions are 0-based in the contig as
+ * stored, whatever the strand of a block (records hold contig positions as stored; the reference is the side that is reverse-complemented); in a bundle they are
+ * relative to contig k, as gsa_lift's qpos is.
+ *   blocks    only the blocks of contig k with bdup == 0 and a valid chr are counted: gsa_ref_track's set
+ *   columns   the CIGAR pass's classes by its rule: a seed is '=' over its length, an equal-length gap that needed no DP is classified base against base, a DP gap is
+ *             read from the op string of its DP job, a pure insertion / deletion record is one class throughout
+ *   kept      TRIMMED exactly as gsa_ref_track trims: end = last.rpos + last.rlen clamped to the end of the block's chromosome copy; an '=', 'X' or 'D' column is kept
+ *             when its reference text position is t < end, an 'I' column when the reference base consumed last in front of it in walk order is kept.  t ascends in walk
+ *             order, so the kept columns are a PREFIX of the block's columns, and the query bases of the kept '=' / 'X' / 'I' columns are one interval [q0, q1) per block
+ *   n_cov     bases of the window under at least one counted block's [q0, q1) (the union: n_cov <= len)
+ *   n_multi   bases of the window under at least two (n_multi <= n_cov)
+ *   n_eq, n_x, n_ins   kept columns of that class whose query base lies in the window, summed over ALL counted blocks: a base under two blocks counts twice,
+ *             n_eq + n_x + n_ins is the depth sum (>= n_cov, equal exactly where n_multi == 0)
+ *   n_del     kept 'D' columns (reference bases facing '-'), each charged to the query base consumed last in front of it in walk order (it exists: a gap follows a seed)
+ * One record per window with n_cov > 0, ascending by start. */
+typedef struct { int32_t start, len; uint32_t n_cov, n_multi, n_eq, n_x, n_ins, n_del; } gsa_qtrack_win;   /* 32 bytes; start 0-based inside the contig */
+typedef struct { int64_t n_win; const gsa_qtrack_win *win; } gsa_qtracks;
+/* The query-side window length W of this context from now on; 0 clears it.  A clone starts without a window.  W < 0: GSA_ERR_ARG.  Independent of gsa_track_set: both
+ * windows may be set, with different lengths.  Device memory: 16 bytes per window of the longest contig seen (allocated and cleared by the gsa_query_track that first
+ * needs them, kept clear by the pass itself) + 32 per window that comes home. */
+int gsa_qtrack_set(gsa_ctx *ctx, int32_t window);
+/* The query track of the stage-8 result the context holds.  Validity, call order, k and the error codes are those of gsa_block_cigars; without a window GSA_ERR_STATE.  No
+ * counted block: n_win = 0.  The counts are uint32_t, with gsa_ref_track's rule: when the reference bases plus the query bases that the counted blocks of contig k span
+ * exceed 2^32 - 1, GSA_ERR_LIMIT before any launch.  A DP record without a job, or a column outside its record or sequence, is counted on the device and fails the call
+ * with GSA_ERR_STATE.  The answer lives in buffers of its own: the eight other passes return what they returned before, in any call order, and so does this call after
+ * one of them.  Memory is owned by the context and valid until the next call on it; the windows come home in one copy into pinned memory. */
+int gsa_query_track(gsa_ctx *ctx, int32_t k, gsa_qtracks *out);
+/* measurement: host wall time the calling threads spent inside gsa_query_track on this context since it was created, and the number of calls.  Always on. */
+int gsa_get_qtrack_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 
 /* ---- per-block chain segments (UCSC chain files, for liftOver / CrossMap / bcftools +liftover) --------------
  * ("Chain" already names the seed-chaining stage of this library: the word for the new thing is SEGS.)
@@ -535,7 +567,7 @@ int gsa_proj_close(gsa_ctx *ctx);   /* without an accumulator: GSA_ERR_STATE */
 int gsa_proj_clear(gsa_ctx *ctx);   /* every word back to 0 (and the array no longer dirty, see gsa_project) */
 /* Paints the blocks of the stage-8 result the context holds (contig k of a bundle: the painted content does not depend on whether the contig was aligned alone or in
  * a bundle).  Validity, call order, k and the error codes are those of gsa_block_cigars; without an accumulator GSA_ERR_STATE.  No blocks: the stat is zero, the
- * words untouched.  The pass has buffers of its own: the six other passes return what they returned before, in any call order.  A DP record without a job, or a
+ * words untouched.  The pass has buffers of its own: the eight other passes return what they returned before, in any call order.  A DP record without a job, or a
  * column outside its record or sequence, is counted on the device and fails the call with GSA_ERR_STATE; the accumulator is then DIRTY, and gsa_proj_fetch and
  * gsa_project return GSA_ERR_STATE on it until gsa_proj_clear.  out may be NULL. */
 int gsa_project(gsa_ctx *ctx, int32_t k, gsa_proj_stat *out);
@@ -580,14 +612,14 @@ typedef struct { int64_t n_hits; const gsa_region_hit *hits; } gsa_region_lifts;
 int gsa_regions_set(gsa_ctx *ctx, const int64_t *beg, const int64_t *end, int64_t n);
 /* The regions of gsa_regions_set lifted through the stage-8 result the context holds.  Validity, call order, k and the error codes are those of gsa_block_cigars;
  * without regions GSA_ERR_STATE.  No blocks or no hits: n_hits = 0.  A DP record without a job, or a span the records do not reach, is counted on the device and
- * fails the call with GSA_ERR_STATE.  The answer lives in buffers of its own: the seven other passes return what they returned before, in any call order, and so
+ * fails the call with GSA_ERR_STATE.  The answer lives in buffers of its own: the eight other passes return what they returned before, in any call order, and so
  * does this call after one of them.  Memory is owned by the context and valid until the next call on it; the hits come home in one copy into pinned memory. */
 int gsa_lift_regions(gsa_ctx *ctx, int32_t k, gsa_region_lifts *out);
 /* measurement: host wall time the calling threads spent inside gsa_lift_regions on this context since it was created, and the number of calls.  Always on. */
 int gsa_get_region_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 
 /* gsa_align_many with optional passes run by the worker in front of the callback -- before the prefetch after next can touch the contig's
- * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track) | GSA_WANT_SEGS (gsa_block_segs) | GSA_WANT_PROJ (gsa_project) | GSA_WANT_REGIONS (gsa_lift_regions).  *ex and what it
+ * slot: `want` = GSA_WANT_VARIANTS (gsa_call_variants) | GSA_WANT_CIGARS (gsa_block_cigars) | GSA_WANT_CS (gsa_block_cs) | GSA_WANT_LIFT (gsa_lift) | GSA_WANT_TRACK (gsa_ref_track) | GSA_WANT_SEGS (gsa_block_segs) | GSA_WANT_PROJ (gsa_project) | GSA_WANT_REGIONS (gsa_lift_regions) | GSA_WANT_QTRACK (gsa_query_track).  *ex and what it
  * points to are valid during the callback only, like *res. */
 #define GSA_WANT_VARIANTS 1u
 #define GSA_WANT_CIGARS   2u
@@ -597,6 +629,7 @@ int gsa_get_region_timing(gsa_ctx *ctx, double *ms_sum, int64_t *n_calls);
 #define GSA_WANT_SEGS     64u  /* gsa_block_segs; implies GSA_WANT_CIGARS */
 #define GSA_WANT_PROJ     128u /* gsa_project of every contig, behind the other passes; it adds nothing behind gsa_extras; every context of ctx[] must hold an accumulator (gsa_proj_open), else GSA_ERR_STATE before any contig is aligned -- but where NO context of ctx[] holds one the bit is refused like an unknown one, GSA_ERR_ARG, as it was before the pass existed */
 #define GSA_WANT_REGIONS  256u /* gsa_lift_regions of every contig; every context of ctx[] must hold regions (gsa_regions_set), else GSA_ERR_STATE before any contig is aligned */
+#define GSA_WANT_QTRACK   512u /* gsa_query_track of every contig; every context of ctx[] must hold a query-side window (gsa_qtrack_set), else GSA_ERR_STATE before any contig is aligned */
 typedef struct { const gsa_variants *var; const gsa_cigars *cig; } gsa_extras;   /* NULL where not asked for */
 /* The contig's cs strings inside the callback of gsa_align_many_ex: the library hands the callback a LARGER object whose head is the gsa_extras
  * (which keeps its two members and its 16 bytes), and this call reaches what lies behind it -- so it is valid for the `ex` the library passed
@@ -610,6 +643,8 @@ int gsa_extras_track(const gsa_extras *ex, gsa_tracks *out);
 int gsa_extras_segs(const gsa_extras *ex, gsa_segs *out);
 /* The contig's lifted regions inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_REGIONS was not asked for). */
 int gsa_extras_regions(const gsa_extras *ex, gsa_region_lifts *out);
+/* The contig's query track inside the callback, in the same way (GSA_ERR_STATE when GSA_WANT_QTRACK was not asked for). */
+int gsa_extras_qtrack(const gsa_extras *ex, gsa_qtracks *out);
 typedef int (*gsa_result_ex_fn)(void *user, int32_t contig, const gsa_result *res, const gsa_extras *ex);
 int gsa_align_many_ex(gsa_ctx *const *ctx, int32_t n_ctx, const char *const *query, const int32_t *qlen, int32_t n,
                       uint32_t flags, uint32_t want, gsa_result_ex_fn on_result, void *user);
