@@ -2,6 +2,7 @@
 
     ref, cases = build_cases(slen)            # the default MinSeedLength
     ref, cases = build_cases(SEN_SLEN, sen=True)
+    ref, cases = build_cases(slen, sen, kmer_k=K)    # a row of the (kmer_k, MinSeedLength) grid, GRID below
 
 `ref` is a 200 kb random reference with copies of its own stretches planted in its far end (150 000 ...); it does NOT depend on slen / sen, so one index serves
 both.  `cases` is an ordered dict  name -> (query, must_be_seed_starts, must_not_be_seed_starts, [(start, expected_len, expected_freq)]):  the longest match
@@ -16,6 +17,20 @@ substitution in front of it and the hop is its length + 1; under -sen the hop be
 the start: a walk cannot jump it and leaves it base by base.
 
 Families: seg_edge_*  back_*  freq_*  text_*  len_* / n_at_* / start_at_*  resolve_*  handover_last_chunk  cand_cap_sen.
+
+The grid: which rungs of the search ladder exist depends on how MinSeedLength compares with the jump table's kmer_k, so build_cases takes the
+kmer_k that the context will be forced to (None: the text's own, 12) and GRID lists the rows.  What follows the row: text_* (kmer_k + n bases), len_k-1 / len_k,
+len_klo (whenever an N can stand behind MinSeedLength bases and inside the first kmer_k), the run of seg_edge_* (25 bases, MinSeedLength where that is more: the
+planted second copy has 26, so above 25 the listed matches are unique), and the families
+    len_between_*        exact lengths MinSeedLength + 1 and kmer_k - 1 where they lie strictly between the two: the kmer_k-entry is absent, the seed is accepted
+    len_pres_16 / _17    (MinSeedLength >= 18) the presence table answers for 16 bases: the bit is set, no seed results
+    pres_look_{1..4}     j starts in a row whose first pres_k = min(MinSeedLength, 16) bases occur nowhere (one substitution at the last of them, chosen so), then
+                         a seed of 40 bases: the look-ahead of the speculative kernel (three starts per presence line) and its fall-through on the fourth;
+                         pres_look_2_p16 (MinSeedLength > 16): the start behind the absent run matches exactly 16 bases -- present, and no seed
+    start_at_clen-k/-k+1 (kmer_k > MinSeedLength) a seed of kmer_k / kmer_k - 1 bases into the chunk's last base: s + kmer_k = clen and clen + 1
+    n_word_32_{29..32}   (MinSeedLength 30) an N at that offset from a start on the chain: the mask of the first min(MinSeedLength, 32) bases at the 32-bit edge
+MER (30) is the longest MinSeedLength there is and the resolver's hops are matches of 38 - 40 bases, so freq_* and resolve_hop_* hold on every row as they are.
+A construction that has no place on a row (a 7-mer that occurs once in 400 kb) is named in DROPPED; nothing is left out silently.
 """
 from __future__ import annotations
 
@@ -137,26 +152,62 @@ class _Q:
         return np.ascontiguousarray(self.q)
 
 
+class NoPlace(AssertionError):
+    """a construction has no place in this text"""
+
+
 def _unique_start(ref, text, a, s0, n, step=1):
     """the first start s >= s0 (s0, s0 + step, ...) at which ref[a + s : a + s + n) occurs once in the text"""
     for s in range(s0, s0 + 4000 * step, step):
         if count_in(text, ref[a + s:a + s + n].tobytes(), 2) == 1:
             return s
-    raise AssertionError("dense_cases: no unique stretch")
+    raise NoPlace("dense_cases: no unique stretch")
+
+
+def longest_in(text: bytes, qb: bytes, s: int, end: int):
+    """(length, occurrences) of the longest match of qb[s : end) in the text, base by base"""
+    L = 0
+    while s + L < end and qb[s + L] in b"ACGT" and text.find(qb[s:s + L + 1]) >= 0:
+        L += 1
+    return L, (count_in(text, qb[s:s + L]) if L else 0)
+
+
+# the rows: kmer_k -> (MinSeedLength, -sen) ...; -sen forces MinSeedLength 10
+GRID = {
+    12: ((10, False), (11, False), (12, False), (13, False), (14, False), (16, False), (17, False), (30, False), (SEN_SLEN, True)),
+    15: ((10, False), (13, False), (14, False), (15, False), (16, False), (30, False), (SEN_SLEN, True)),
+    8: ((10, False), (15, False), (30, False), (SEN_SLEN, True)),
+}
+# (kmer_k, MinSeedLength, sen) -> the constructions that have no place on that row: a match of exactly 7 bases that occurs once does not exist in 400 kb
+# (a 7-mer is expected 24 times).  build_cases fails if a name listed here CAN be placed, and if one not listed cannot.
+DROPPED = {(8, slen, sen): ("len_k-1",) for slen, sen in GRID[8]}
+NEW_FAMILIES = ("len_between_", "len_pres_", "pres_look_", "start_at_clen-k", "n_word_32_")
+
+
+def cases_digest(ref, cases) -> str:
+    """sha256 over the reference and every case: name, query bytes, both start lists, the triples"""
+    import hashlib
+    h = hashlib.sha256(np.ascontiguousarray(ref).tobytes())
+    for name, (q, on, off, trip) in cases.items():
+        h.update(repr((name, [int(x) for x in on], [int(x) for x in off], [tuple(int(x) for x in t) for t in trip])).encode()); h.update(q.tobytes())
+    return h.hexdigest()
 
 
 _cache = {}
 
 
-def build_cases(slen: int = DEFAULT_SLEN, sen: bool = False):
-    """(ref, cases) for MinSeedLength slen; sen: the chain hops 5 behind a seed (pass SEN_SLEN with it)."""
-    key = (slen, sen)
+def build_cases(slen: int = DEFAULT_SLEN, sen: bool = False, kmer_k: int | None = None):
+    """(ref, cases) for MinSeedLength slen; sen: the chain hops 5 behind a seed (pass SEN_SLEN with it); kmer_k: the jump table's k-mer length when the
+    context is forced to one (None: the one the library picks for this text)."""
+    key = (slen, sen, kmer_k)
     if key in _cache:
         return _cache[key]
     if "ref" not in _cache:
         _cache["ref"] = make_ref(); _cache["text"] = text_of(_cache["ref"])
     ref, text = _cache["ref"], _cache["text"]
-    S, K = slen, kmer_k_for(2 * REF_LEN)
+    S, K = slen, kmer_k or kmer_k_for(2 * REF_LEN)
+    PK = min(S, 16)                                # build_presence: pres_k
+    drop = DROPPED.get((kmer_k, slen, sen), ()) if kmer_k else ()
     cases = {}
 
     def add(name, Q, on, off, trip):
@@ -168,22 +219,28 @@ def build_cases(slen: int = DEFAULT_SLEN, sen: bool = False):
         return list(always) + ([] if sen else list(dflt))
 
     # ---- sweep segments: a match that starts 3 bases left of a segment's first start E and runs 25 bases into it ----
+    R = max(25, S)                                 # (the plant holds 26 bases: a longer run meets the second copy on its way and ends unique)
     for seg in SEGS:
         E = SEG_E[seg]
         for dup in (False, True):
             a = A_SEG[seg] if dup else A_FREE
-            f = 2 if dup else 1
+            f = 2 if dup and R == 25 else 1
             sfx = "_dup" if dup else ""
-            Q = _Q(ref, a, CHUNK, sen, [(E - 60, E + 90)]); Q.enter(E - 3); Q.stop(E - 3, E + 25)
-            add(f"seg_edge_{seg}{sfx}", Q, [E - 3], both([E]), [(E - 3, 28, 1), (E - 1, 26, 1), (E, 25, f), (E + 1, 24, f)])
+            Q = _Q(ref, a, CHUNK, sen, [(E - 60, E + 90)]); Q.enter(E - 3); Q.stop(E - 3, E + R)
+            add(f"seg_edge_{seg}{sfx}", Q, [E - 3], both([E]), [(E - 3, R + 3, 1), (E - 1, R + 1, 1), (E, R, f), (E + 1, R - 1, f)])
             # the left neighbour does not extend: the left lane's search from scratch at its last start E - 1 meets a substituted base, E is on the chain
-            Q = _Q(ref, a, CHUNK, sen, [(E - 60, E + 90)]); Q.enter(E); Q.stop(E, E + 25)
-            add(f"seg_edge_{seg}{sfx}_noext", Q, [E], [], [(E, 25, f), (E + 1, 24, f)])
+            Q = _Q(ref, a, CHUNK, sen, [(E - 60, E + 90)]); Q.enter(E); Q.stop(E, E + R)
+            add(f"seg_edge_{seg}{sfx}_noext", Q, [E], [], [(E, R, f), (E + 1, R - 1, f)])
 
     # ---- M_BACK: the start of the text, the forward / reverse seam, a word edge of the query words ----
     Q = _Q(ref, 0, CHUNK, sen)
     add("back_text_start", Q, [0], [], [(0, 70, 1), (1, 69, 1)])
-    Q = _Q(ref, 0, CHUNK - 7, sen); Q.q = np.concatenate([rot(ref[1000:1007]), Q.q])      # seven unrelated bases in front: the 32 starts of a backward step reach past text position 0
+    for u in range(1000, 1400):                    # (the first seven from which no match reaches MinSeedLength, so that start 7 is on the chain: at 15 those of 1000)
+        Q = _Q(ref, 0, CHUNK - 7, sen); Q.q = np.concatenate([rot(ref[u:u + 7]), Q.q])      # seven unrelated bases in front: the 32 starts of a backward step reach past text position 0
+        if sen or all(longest_in(text, Q.q[:40].tobytes(), i, 40)[0] < S for i in range(7)):
+            break
+    else:
+        raise NoPlace("back_text_start_off")
     add("back_text_start_off", Q, both([7]), [], [(7, 70, 1), (8, 69, 1)])
     G = REF_LEN
     tx =np.frombuffer(text, np.uint8)
@@ -219,7 +276,16 @@ def build_cases(slen: int = DEFAULT_SLEN, sen: bool = False):
     # ---- the search ladder's switches ----
     def short(name, n, nbase=None, klo=False):
         """a match of exactly n bases, unique, at a start that is on the chain; nbase: an N ends it instead of a substitution"""
-        s0 = _unique_start(ref, text, A_FREE, 3000, n)
+        try:
+            s0 = 2999
+            while True:                            # (the first unique place; the next one where no base ends the match there -- short k-mers: all three go on somewhere)
+                s0 = _unique_start(ref, text, A_FREE, s0 + 1, n)
+                if nbase is not None or any((ref[A_FREE + s0:A_FREE + s0 + n].tobytes() + bytes(rot(ref[A_FREE + s0 + n:A_FREE + s0 + n + 1], r))) not in text for r in (1, 2, 3)):
+                    break
+        except NoPlace:
+            assert name in drop, (name, "has no place on row", (kmer_k, slen, sen), "and is not in DROPPED")
+            return
+        assert name not in drop, (name, "is in DROPPED and can be placed on row", (kmer_k, slen, sen))
         Q = _Q(ref, A_FREE, CHUNK, sen, [(s0 - 60, s0 + 90)]); Q.enter(s0)
         if nbase is None:
             Q.stop(s0, s0 + n)
@@ -229,14 +295,52 @@ def build_cases(slen: int = DEFAULT_SLEN, sen: bool = False):
 
     short("len_min-1", S - 1); short("len_min", S)
     short("len_k-1", K - 1); short("len_k", K)
-    if sen and S + 1 < K:
+    if (sen or kmer_k) and S + 1 < K:
         short("len_klo", S + 1, nbase=True)        # an N inside the first kmer_k bases: the long table is out of reach, the short one (kmer_lo_k = MinSeedLength) is not
+    if kmer_k:
+        for name, n in (("len_between_min+1", S + 1), ("len_between_k-1", K - 1)):
+            if S < n < K:                          # the presence bit is set, the kmer_k-entry says "absent", the walk from the first base finds a seed
+                short(name, n)
+        if S >= 18:
+            short("len_pres_16", 16); short("len_pres_17", 17)      # present by their 16 bases and no seeds
+        if S == 30:
+            for o in (29, 30, 31, 32):
+                short(f"n_word_32_{o}", o, nbase=True)
     short("n_at_L-1", S - 1, nbase=True); short("n_at_L", S, nbase=True)
-    for name, n in (("start_at_clen-min", S), ("start_at_clen-min+1", S - 1)):
+    ends = [("start_at_clen-min", S), ("start_at_clen-min+1", S - 1)]
+    if kmer_k and K > S:
+        ends += [("start_at_clen-k", K), ("start_at_clen-k+1", K - 1)]      # s + kmer_k = clen: the last start with a table entry; clen + 1: the first without
+    for name, n in ends:
         s = CHUNK - n
         a = A_FREE + _unique_start(ref, text, A_FREE + s, 0, n)
         Q = _Q(ref, a, 2 * CHUNK, sen, [(s - 60, CHUNK + 60)]); Q.enter(s)
         add(name, Q, [s] if n >= S else [], [] if n >= S else [s], [(s, n, 1)])
+
+    # ---- the presence table ahead of a walk: j starts whose first pres_k bases occur nowhere, then one that is a seed (p16: present by 16 bases, 16 < MinSeedLength) ----
+    def pres_look(name, j, p16=False):
+        for e in range(4000, 8000, 7):
+            for r in (1, 2, 3):
+                Q = _Q(ref, A_FREE, CHUNK, sen, [(e - 60, e + j + 120)]); Q.enter(e); Q.sub(e + j - 1, r)
+                if all(Q.q[e + i:e + i + PK].tobytes() not in text for i in range(j)):
+                    break
+            else:
+                continue
+            n = 16 if p16 else 40
+            Q.stop(e + j, e + j + n)
+            qb = Q.finish(text).tobytes()
+            if count_in(text, qb[e + j:e + j + n], 2) != 1:
+                continue
+            trip = [(e + i,) + longest_in(text, qb, e + i, CHUNK) for i in range(j)] + [(e + j, n, 1)]
+            assert all(t[1] < PK for t in trip[:j])
+            add(name, Q, [] if p16 else [e + j], list(range(e, e + j)) + ([e + j] if p16 else []), trip)
+            return
+        raise NoPlace(name)
+
+    if kmer_k:
+        for j in (1, 2, 3, 4):
+            pres_look(f"pres_look_{j}", j)
+        if S > 16:
+            pres_look("pres_look_2_p16", 2, p16=True)
 
     # ---- k_dense_resolve: blocks of RS_B positions ----
     p = RS_B * 50
